@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: decoded frames/s of CRC-aided SCL, N=1024 K=512 CRC-24C L=8.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cascl_1024_l8|cascl_4096_l32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cascl_1024_l8|cascl_4096_l32] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 --config cascl_4096_l32 is BASELINE.json's config 5 (N=4096 K=2048 CA-SCL L=32, 2^15 frames per GPU per step = 2^18
@@ -10,6 +10,11 @@ over 8 GPUs); the default line (config 4) is unchanged by it.
 Started without a launcher and with --gpus N > 1, the process that parsed the arguments touches no GPU: it starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child, passes rank 0's JSON line through and
 exits with the child's code.  Started by a launcher, --gpus must equal WORLD_SIZE.
+
+--dump-outputs DIR writes, after the timed steps, the decisions the last step returned (out_bits, int32 [B][N/32], as
+float64) to DIR/out_bits.npy and the frames kept to DIR/frame_index.npy (every frame up to 64 MB, else a fixed seeded
+sample; with N ranks each writes its own shard as *_rank<r>.npy).  The inputs depend only on the arguments (seeded
+generator), so two builds run with the same arguments can be compared output for output.
 
 A "step" is one pass of the decode hot path (one kernel launch through the C ABI,
 polar_decode_device) over one batch of synthetic BPSK-AWGN frames per GPU, inputs (channel LLRs)
@@ -54,6 +59,8 @@ CONFIGS = {
                            over8="2^18 over 8 GPUs", lane_ops=(2.5e7, 3.9e7), traffic_key="cfg5"),
 }
 N, K = 1024, 512   # the headline shape (cpu_baseline, fer_sweep)
+DUMP_BYTES_MAX = 64 << 20   # --dump-outputs: bytes written in all (over every rank)
+DUMP_SEED = 20261004        # --dump-outputs: which frames are kept when the output is larger than that
 
 
 def host_cpu_model():
@@ -189,7 +196,26 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU: launcher, rendezvous (gloo), barriers, reductions and the JSON relay only; nothing is "
                          "decoded and `value` is null (the world-size-2 CPU test of the N-rank path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (out_bits) to DIR/<name>.npy in float64, "
+                         f"at most {DUMP_BYTES_MAX >> 20} MB in all (a fixed, seeded sample of frames when larger)")
     return ap.parse_args(argv)
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BYTES_MAX, seed=DUMP_SEED, index_name="frame_index"):
+    """--dump-outputs: arrays = {name: [B, ...] array, same B}; each goes to dirpath/<name>.npy as float64 (exact for the
+    int32 words a decode returns), and <index_name>.npy says which frames (rows) were kept.  All B rows when they fit in
+    `budget` bytes together with the index, else the same fixed, seeded sample of rows from every array, in frame order."""
+    import numpy as np
+    B = len(next(iter(arrays.values())))
+    row_bytes = 8 * (1 + sum(int(np.prod(a.shape[1:])) for a in arrays.values()))
+    keep = min(B, (budget - 128 * (1 + len(arrays))) // row_bytes)   # 128: the header of a .npy file this size
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(seed).choice(B, keep, replace=False))
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, f"{index_name}.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}.npy"), np.asarray(a)[rows].astype(np.float64))
+    return rows
 
 
 def launch(args, argv):
@@ -210,6 +236,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch(args, argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -336,6 +364,11 @@ def run(args):
 
     # FER of the last step (outside the timed region): device compare + RCCL sum of two counters
     last = args.steps - 1
+    if args.dump_outputs:
+        # what the last timed step returned, read back before the kernel-level figures below reuse outs[0]
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"out_bits" + sfx: outs[last % len(decs)].cpu().numpy()},
+                     budget=DUMP_BYTES_MAX // world, index_name="frame_index" + sfx)
     decs[last % len(decs)].count_errors_device(outs[last % len(decs)], batches[last & 1][1], counters)
     torch.cuda.synchronize()
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)

@@ -12,6 +12,8 @@ stores inputs + outputs:
 
     <name>.npz : sigma[F], y[F][N] f64, u[F][N] u8 (sent), u_hat[F][N] u8 (reference decision),
                  pm[F] f64 (metric of the chosen path; 0 for SC/BP)
+    sim4242_<name>.npz : the same fields but u, for the frames test_oracle_matches_compiled_reference decodes
+                 (make_sim4242(): O.Sim(4242), 1.0 and 2.5 dB)
 
 BPr_128_main_seed7.txt is the first 43 lines (three Eb/N0 points) of `oracle/_ref/BPr_128_main 7`, the compiled
 BPr_128.c main() with its time() seed pinned to 7 (4 minutes of CPU for all seven points).
@@ -74,6 +76,31 @@ def make_vectors(only=None):
                             u_hat=np.array(uhs, dtype=np.uint8), pm=np.array(pms))
         nerr = sum(int((a != b).any()) for a, b in zip(us, uhs))
         print(f"{name}: {len(sig)} frames, {nerr} in error")
+
+
+def make_sim4242(only=None):
+    """sim4242_<name>.npz: the compiled reference's answers on the frames tests/test_oracle_golden.py's
+    test_oracle_matches_compiled_reference decodes -- O.Sim(4242), 1.0 then 2.5 dB, every frame through one Ref in that
+    order -- so that the test runs where oracle/_ref cannot be built.  sigma[F], y[F][N] f64, u_hat[F][N] u8, pm[F]."""
+    for name, (N, K, taps, algo, L) in O.REF_PROGRAMS.items():
+        if only and name not in only:
+            continue
+        code = O.Code(N, K, taps, systematic=name in O.SYSTEMATIC_PROGRAMS)
+        ref = O.Ref(name)
+        sim = O.Sim(4242)
+        nfr = 6 if (N == 1024 and algo != "SC") else 40
+        if algo == "BP" and N == 1024:
+            nfr = 2
+        sig, ys, uhs, pms = [], [], [], []
+        for db in (1.0, 2.5):
+            s = O.sigma_from_db(db)
+            for _ in range(nfr):
+                _, y = sim.frame(code, s)
+                uh, pm = ref.decode(y, s)
+                sig.append(s); ys.append(y); uhs.append(uh); pms.append(pm)
+        np.savez_compressed(os.path.join(HERE, f"sim4242_{name}.npz"), sigma=np.array(sig), y=np.array(ys),
+                            u_hat=np.array(uhs, dtype=np.uint8), pm=np.array(pms))
+        print(f"sim4242_{name}: {len(sig)} frames")
 
 
 def check_systematic_rows(name, code):
@@ -270,6 +297,7 @@ if __name__ == "__main__":
     only = sys.argv[1:] or None          # optional: names of the programs to regenerate ("ties": only the tie files)
     if only != ["ties"]:
         make_vectors(only)
+        make_sim4242(only)
     make_ties(only)
     if not only or "BPr_128" in only:
         make_bpr()

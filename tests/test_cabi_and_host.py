@@ -212,6 +212,32 @@ def test_bench_launches_its_own_ranks_under_gloo():
     assert body.index('os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")') < body.index("import torch")
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: what the timed path returned, as float64 .npy, exact, within the byte budget; a larger output
+    is cut to the same seeded sample of frames every time.  --steps 0 is refused (it must be the number of timed steps)."""
+    import bench
+    rng = np.random.default_rng(1)
+    words = rng.integers(-2 ** 31, 2 ** 31, size=(1000, 32), dtype=np.int64).astype(np.int32)
+    rows = bench.dump_outputs(str(tmp_path / "all"), {"out_bits": words})
+    got = np.load(tmp_path / "all" / "out_bits.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int32), words) and len(rows) == 1000
+    assert np.array_equal(np.load(tmp_path / "all" / "frame_index.npy"), np.arange(1000))
+    budget = 100 * 33 * 8 + 2 * 128                # room for 100 frames of 32 words plus their index, and two headers
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"out_bits": words}, budget=budget)
+    idx = np.load(tmp_path / "a" / "frame_index.npy").astype(np.int64)
+    assert len(idx) == 100 and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "out_bits.npy").astype(np.int32), words[idx])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= budget
+    for f in ("frame_index.npy", "out_bits.npy"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--rehearse-cpu"] + bad,
+                             capture_output=True, text=True, timeout=120)
+        assert out.returncode != 0 and "--steps must be >= 1" in out.stderr
+
+
 def test_fn_matrix_file_format(tmp_path):
     """The N x N 0/1 matrix the reference reads from stdin (SCL_1024.c:207-217): written, read back the reference's way,
     recognised as the Kronecker power; a damaged copy is counted and rejected; its rows ARE the butterfly encoder."""

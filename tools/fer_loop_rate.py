@@ -1,7 +1,7 @@
 """Developer tool: rate of the whole Monte-Carlo loop body on the device (polar_fer_batch: generate -> decode -> count)
 against the decode alone, and of the generator alone (polar_generate_device)."""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import polardecoding_amd as pa
 for name, mk, B in (("CASCL_1024_L8", lambda: pa.CASCL(1024, 512, L=8), 1 << 18), ("BP_1024_50it", lambda: pa.BP(1024, 512, iterMax=50), 1 << 16),

@@ -1,7 +1,7 @@
 """Developer tool: many queued launches in a row on one context, every result compared with the first one (a lost or doubly
 decoded job, or a counter that is not back at zero, would show as a different or missing frame)."""
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import polardecoding_amd as pa
 from polardecoding_amd.synth import make_batch

@@ -1,7 +1,7 @@
 """Single-launch rate of the headline kernel against the batch size: how much of a launch is head + tail?
 B = k x 6144 fills every resident wavefront (768 workgroups x 4 wavefronts x 2 codewords) exactly k times."""
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import polardecoding_amd as pa
 sigma = 10 ** (-2.0 / 20)
