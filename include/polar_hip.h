@@ -51,6 +51,7 @@ extern "C" {
                                     the 2L candidate metrics did not single out L survivors and the kernel ranked on
                                     the full doubles (f64 list kernels that pre-rank on 32-bit keys; same result either
                                     way -- the bit lets the tests see that rare path run)                              */
+#define POLAR_FLAG_BP_CONVERGED 0x8u /* BP: the stop criterion held at the last round trip run (polar_bp_set_stop)       */
 
 typedef struct polar_ctx polar_ctx;
 
@@ -174,6 +175,33 @@ int polar_bp_readout_device(polar_ctx *ctx, const void *d_in, int in_is_f32, dou
  * u [B][N] sent bits (0/1 ints), E [ncp][n+1] accumulated (+=), u_hat [B][N] (may be NULL). */
 int polar_bp_readout_batch(polar_ctx *ctx, const double *in, double sigma, size_t B, const int *u,
                            const int *checkpoints, int ncp, unsigned long long *E, int *u_hat);
+
+/* --- BP early termination (opt-in; the reference always runs iterMax round trips, BP_1024.c:393) -------------------
+ * One round trip t (1-based) is one R sweep followed by one L sweep (BP_1024.c:393-416).  After round trip t:
+ *   u_hat_j = the reference's final decision (BP_1024.c:417-425): 0 at a frozen position, else 0 if l[0][j] + r[0][j] >= 0,
+ *             else 1;
+ *   x_hat_j = 0 if l[n][j] + r[n][j] >= 0, else 1, where l[n] is the channel LLR in the message type and r[n] is what the
+ *             R sweep of round trip t writes at stage n (operand order as written).
+ * Rule POLAR_BP_STOP_G (the G-matrix criterion of Yuan & Parhi) stops a frame after the first t at which
+ * u_hat F^{(x)n} == x_hat over GF(2), F^{(x)n} in natural order (the encoder of SCL_1024.c:242-250); the frame's output is
+ * that u_hat.  A frame with no such t <= iterMax runs iterMax round trips and its output is exactly that of
+ * POLAR_BP_STOP_NONE.  The rows the check reads (r[n], l[0]) are read by no message update, so a frame that stops after t
+ * has the decisions of the fixed-iteration decoder with bp_iters = t, bit for bit (in f64 those of the reference's BP()
+ * with iterMax = t; in f32 the same operations in float).
+ * The rule belongs to the ctx and is honoured by polar_decode, polar_decode_batch(_y), polar_decode_device,
+ * polar_fer_batch and polar_stop_rule_batch_y; in polar_decode_batch(_y)'s flags it sets POLAR_FLAG_BP_CONVERGED.
+ * polar_bp_readout_* return POLAR_EINVAL while a rule is set (their checkpoints need every round trip).  polar_group_* and
+ * polar_fer_multi_gpu build their contexts from a polar_cfg and always run POLAR_BP_STOP_NONE. */
+#define POLAR_BP_STOP_NONE 0 /* default: iterMax round trips (the reference)                          */
+#define POLAR_BP_STOP_G 1    /* stop at the first round trip with u_hat F == x_hat (above)             */
+/* POLAR_EINVAL: not a BP ctx, or an unknown rule */
+int polar_bp_set_stop(polar_ctx *ctx, int rule);
+/* polar_decode_device for a BP ctx, plus per frame: d_iters (nullable) [B] round trips run, d_flags (nullable) [B]
+ * POLAR_FLAG_BP_CONVERGED or 0.  With POLAR_BP_STOP_NONE d_iters is filled with iterMax and d_flags with 0. */
+int polar_bp_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
+                           uint32_t *d_uhat_bits, uint32_t *d_iters, uint32_t *d_flags);
+/* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N], iters / flags (nullable) [B]. */
+int polar_bp_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *iters, unsigned *flags);
 
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at

@@ -6,10 +6,10 @@ per-frame decode functions (``SCdecode`` / ``BP`` / ``SCLdecode`` / ``CASCL``), 
 device buffers and multi-GPU sharding.  There is no CPU fallback: everything raises if the HIP library
 is missing.
 """
-from .api import (ALGO_BP, ALGO_CASCL, ALGO_SC, ALGO_SCL, CRC6_TAPS, CRC24C_TAPS, F32, F64, FLAG_CRC_PASS,
-                  FLAG_RERANK, FLAG_TIE, BP, CASCL, Decoder, Group, PolarError, SCdecode, SCLdecode, decode, lib_path, load_crc_matrix, load_library,
+from .api import (ALGO_BP, ALGO_CASCL, ALGO_SC, ALGO_SCL, BP_STOP_G, BP_STOP_NONE, CRC6_TAPS, CRC24C_TAPS, F32, F64,
+                  FLAG_BP_CONVERGED, FLAG_CRC_PASS, FLAG_RERANK, FLAG_TIE, BP, CASCL, Decoder, Group, PolarError, SCdecode, SCLdecode, decode, lib_path, load_crc_matrix, load_library,
                   q_sequence, save_crc_matrix)
 
 __all__ = ["Decoder", "Group", "SCdecode", "BP", "SCLdecode", "CASCL", "decode", "PolarError", "load_library", "lib_path",
            "q_sequence", "load_crc_matrix", "save_crc_matrix", "ALGO_SC", "ALGO_BP", "ALGO_SCL", "ALGO_CASCL", "F64", "F32", "CRC6_TAPS", "CRC24C_TAPS",
-           "FLAG_TIE", "FLAG_CRC_PASS", "FLAG_RERANK"]
+           "FLAG_TIE", "FLAG_CRC_PASS", "FLAG_RERANK", "FLAG_BP_CONVERGED", "BP_STOP_NONE", "BP_STOP_G"]

@@ -16,7 +16,9 @@ import numpy as np
 
 ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL = 0, 1, 2, 3
 F64, F32 = 0, 1
-FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK = 1, 2, 4
+FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
+BP_STOP_NONE, BP_STOP_G = 0, 1   # polar_bp_set_stop: iterMax round trips / stop at the first with u_hat F == x_hat
+_BP_STOP_RULES = {None: BP_STOP_NONE, "none": BP_STOP_NONE, "g": BP_STOP_G, BP_STOP_NONE: BP_STOP_NONE, BP_STOP_G: BP_STOP_G}
 CRC6_TAPS = (0, 5, 6)  # g(D) = D^6 + D^5 + 1 (CASCL_128.c:3)
 CRC24C_TAPS = (0, 1, 2, 4, 8, 12, 13, 15, 17, 20, 21, 23, 24)  # CASCL_1024_L8.c:2-4
 
@@ -82,6 +84,9 @@ def load_library(testing=False):
     L.polar_stop_rule_cut_device.argtypes = [vp, vp, C.c_size_t, C.c_uint, C.c_size_t, vp]
     L.polar_stop_rule_batch_y.argtypes = [vp, dp, C.c_double, vp, C.c_size_t, C.c_uint, C.c_size_t, C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.polar_bp_set_stop.argtypes = [vp, C.c_int]
+    L.polar_bp_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
+    L.polar_bp_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
     L.polar_bp_readout_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, ip, C.c_int, vp, vp]
     L.polar_generate_device.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp, C.c_int,
                                         C.c_int, vp]
@@ -174,6 +179,7 @@ class Decoder:
             cfg.info_order = _ptr(io, C.c_int)
         self._crc_file = os.fsencode(crc_file) if crc_file is not None else None   # g(D) and r from a generator-matrix file
         self._cfg, self._cfg_keep = cfg, (taps, io)   # kept for polar_fer_multi_gpu (the arrays the struct points to must stay alive)
+        self.bp_stop = BP_STOP_NONE
         self._create()
         A, Lr = C.c_int(), C.c_int()
         self._lib.polar_ctx_info(self._h, None, None, C.byref(A), C.byref(Lr), None, None)
@@ -196,6 +202,8 @@ class Decoder:
         self.close()
         self._lib = lib
         self._create()
+        if self.bp_stop != BP_STOP_NONE:
+            self.set_bp_stop(self.bp_stop)
 
     @property
     def info_order(self):
@@ -220,6 +228,15 @@ class Decoder:
             msg = self._lib.polar_strerror(rc).decode()
             det = self._lib.polar_last_error(self._h).decode()
             raise PolarError(f"{what}: {msg} {det} (rc={rc})")
+
+    def set_bp_stop(self, rule):
+        """BP early termination (polar_bp_set_stop): None / "none" / BP_STOP_NONE runs iterMax round trips (the reference),
+        "g" / BP_STOP_G stops a frame at the first round trip whose decisions form a codeword (u_hat F == x_hat)."""
+        if rule not in _BP_STOP_RULES:
+            raise ValueError(f"unknown BP stop rule {rule!r}: None, 'none' or 'g'")
+        code = _BP_STOP_RULES[rule]
+        self._check(self._lib.polar_bp_set_stop(self._h, code), "polar_bp_set_stop")
+        self.bp_stop = code
 
     @property
     def kernel_name(self):
@@ -292,6 +309,37 @@ class Decoder:
             C.c_void_p(pm.data_ptr()) if pm is not None else None,
             C.c_void_p(flags.data_ptr()) if flags is not None else None), "polar_decode_device")
         return out_bits
+
+    def decode_bp_device(self, d_in, sigma=0.0, out_bits=None, iters=None, flags=None):
+        """polar_bp_decode_device: like decode_device, plus per frame the round trips run (`iters`, int32 [B]) and
+        FLAG_BP_CONVERGED (`flags`, int32 [B]); both optional tensors.  Returns out_bits."""
+        import torch
+        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
+        B = d_in.numel() // self.N
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        for t in (iters, flags):
+            if t is not None and (t.numel() < B or t.element_size() != 4 or not t.is_contiguous()):
+                raise ValueError("iters / flags must be contiguous 32-bit tensors of at least B elements")
+        self._check(self._lib.polar_bp_decode_device(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B, C.c_void_p(out_bits.data_ptr()),
+            C.c_void_p(iters.data_ptr()) if iters is not None else None,
+            C.c_void_p(flags.data_ptr()) if flags is not None else None), "polar_bp_decode_device")
+        return out_bits
+
+    def decode_bp_batch(self, llr):
+        """polar_bp_decode_batch: llr [B][N] -> (u_hat [B][N] int32, iters [B] uint32, flags [B] uint32)."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        B = llr.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        it = np.zeros(B, dtype=np.uint32)
+        fl = np.zeros(B, dtype=np.uint32)
+        self._check(self._lib.polar_bp_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
+                                                    _ptr(it, C.c_uint), _ptr(fl, C.c_uint)), "polar_bp_decode_batch")
+        return uh, it, fl
 
     def generate_device(self, seed, first_frame, snr_db, out, u_bits=None, out_is_y=False):
         """Device-side transmit chain (throughput mode): fills `out` [B][N] (float64/float32 LLRs, or y) and
@@ -423,9 +471,13 @@ def SCdecode(N, K, **kw):
     return Decoder(N, K, ALGO_SC, L=1, **kw)
 
 
-def BP(N, K, iterMax=100, **kw):
-    """BP_1024.c:372 -- ``BP(y, u_hat)``; iterMax is BP_1024.c:16."""
-    return Decoder(N, K, ALGO_BP, L=1, bp_iters=iterMax, **kw)
+def BP(N, K, iterMax=100, early_stop=None, **kw):
+    """BP_1024.c:372 -- ``BP(y, u_hat)``; iterMax is BP_1024.c:16.  early_stop="g": stop a frame at the first round trip
+    whose decisions form a codeword (Decoder.set_bp_stop); None: iterMax round trips, as the reference."""
+    dec = Decoder(N, K, ALGO_BP, L=1, bp_iters=iterMax, **kw)
+    if early_stop is not None:
+        dec.set_bp_stop(early_stop)
+    return dec
 
 
 def SCLdecode(N, K, L=8, **kw):

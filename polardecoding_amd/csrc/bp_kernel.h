@@ -48,7 +48,46 @@ __device__ __forceinline__ void bp_sync(int stage_a, int stage_b)
     else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-template <typename R, typename IN>
+// ---- stop rule POLAR_BP_STOP_G (include/polar_hip.h): after a round trip, u_hat F^{(x)n} == x_hat? ----------------------
+// x = u F^{(x)n} in natural order (gen_kernel.h, SCL_1024.c:242-250): x[j] ^= x[j + s] for every j with bit s clear, s = 1,
+// 2, .. N/2.  In a 32-bit word of decisions (bit j & 31 of word j >> 5) the strides below 32 are shifts under a mask.
+__device__ __forceinline__ uint32_t bp_encode_word(uint32_t v)
+{
+    v ^= (v >> 1) & 0x55555555u;
+    v ^= (v >> 2) & 0x33333333u;
+    v ^= (v >> 4) & 0x0F0F0F0Fu;
+    v ^= (v >> 8) & 0x00FF00FFu;
+    v ^= (v >> 16) & 0x0000FFFFu;
+    return v;
+}
+// One wavefront: the N/32 <= 128 words of u_hat and x_hat (LDS) -> does u_hat F == x_hat hold?  Wave-uniform result.  Lane l
+// holds words l and l + 64; strides of 32..1024 elements are lane exchanges, 2048 is the lane's own pair.
+__device__ __forceinline__ bool bp_g_holds(const uint32_t *u, const uint32_t *x, int NW)
+{
+    const int lane = threadIdx.x & 63;
+    uint32_t v0 = lane < NW ? bp_encode_word(u[lane]) : 0u;
+    uint32_t v1 = lane + 64 < NW ? bp_encode_word(u[lane + 64]) : 0u;
+    for (int sw = 1; sw < NW && sw < 64; sw <<= 1) {
+        const uint32_t o0 = (uint32_t)__shfl_xor((int)v0, sw), o1 = (uint32_t)__shfl_xor((int)v1, sw);
+        if (!(lane & sw)) {
+            v0 ^= o0;
+            v1 ^= o1;
+        }
+    }
+    if (NW > 64) v0 ^= v1;
+    const uint32_t x0 = lane < NW ? x[lane] : 0u, x1 = lane + 64 < NW ? x[lane + 64] : 0u;
+    return __ballot(v0 != x0 || v1 != x1) == 0;
+}
+// round trips run and BP_FLAG_CONVERGED of one frame, where the caller asked for them
+__device__ __forceinline__ void bp_put_stats(const BpParams &P, int frame, int iters, bool conv)
+{
+    if (P.iters_out) P.iters_out[frame] = (uint32_t)iters;
+    if (P.flags_out) P.flags_out[frame] = conv ? BP_FLAG_CONVERGED : 0u;
+}
+
+// STOP (stop rule G): l[0] in every round trip, r[n] formed by the last R stage as the hard decisions x_hat (into LDS
+// bits, the row itself is not stored), then one wave checks u_hat F == x_hat and publishes a workgroup-uniform flag.
+template <typename R, typename IN, bool STOP = false>
 __global__ __launch_bounds__(512) void k_bp(BpParams P)
 {
     const int N = P.N, n = P.n, NW = N >> 5;
@@ -58,7 +97,9 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
     R *lm = ch + N;                       // rows 1..n-1 of l
     R *rm = lm + (size_t)(n - 1) * N;     // rows 1..n-1 of r
     uint32_t *obits = reinterpret_cast<uint32_t *>(rm + (size_t)(n - 1) * N);  // [NW]
-    unsigned char *lut_mem = reinterpret_cast<unsigned char *>(obits + NW);
+    uint32_t *xbits = obits + NW;         // STOP: [NW] x_hat, then the stop flag
+    int *stopf = reinterpret_cast<int *>(xbits + NW);
+    unsigned char *lut_mem = reinterpret_cast<unsigned char *>(STOP ? reinterpret_cast<uint32_t *>(stopf + 4) : obits + NW);
     lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
     Lut<R>::build(lut_mem, tid, nt);
     Lut<R> lut;
@@ -78,12 +119,16 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
             rm[i] = R(0);  // BP_1024.c:384-386
         }
         for (int i = tid; i < NW; i += nt) obits[i] = 0;
+        if constexpr (STOP)
+            for (int i = tid; i < NW; i += nt) xbits[i] = 0;
         __syncthreads();
 
+        int done = P.iters;
+        bool conv = false;
         for (int it = 0; it < P.iters; ++it) {
             const bool last = (it + 1 == P.iters);
-            // R sweep (BP_1024.c:395-404); stage n-1 only produces r[n], which nobody reads
-            for (int i = 0; i + 1 < n; ++i) {
+            // R sweep (BP_1024.c:395-404); stage n-1 only produces r[n], which nobody reads (but the stop rule)
+            for (int i = 0; i + (STOP ? 0 : 1) < n; ++i) {
                 const int s = 1 << i;
                 for (int b = tid; b < N / 2; b += nt) {
                     const int j = bp_elem(b, i, n);
@@ -99,13 +144,19 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
                     const R l0 = lrow[j], l1 = lrow[j + s];
                     const R a = BP_CHK<R>(r0, l1 + r1, lut);
                     const R c = r1 + BP_CHK<R>(r0, l0, lut);
-                    rm[(size_t)i * N + j] = a;
-                    rm[(size_t)i * N + j + s] = c;
+                    if (STOP && i + 1 == n) {
+                        // x_hat: (l[n] + r[n] >= 0) -> 0
+                        if (!(l0 + a >= R(0))) atomicOr(&xbits[j >> 5], 1u << (j & 31));
+                        if (!(l1 + c >= R(0))) atomicOr(&xbits[(j + s) >> 5], 1u << ((j + s) & 31));
+                    } else {
+                        rm[(size_t)i * N + j] = a;
+                        rm[(size_t)i * N + j + s] = c;
+                    }
                 }
-                bp_sync(i, i + 1);  // next: R stage i+1, or L stage n-1 = i+1
+                bp_sync(i, i + 1);  // next: R stage i+1, or L stage n-1
             }
-            // L sweep (BP_1024.c:406-415); l[0] is needed only for the final decision
-            for (int i = n - 1; i >= (last ? 0 : 1); --i) {
+            // L sweep (BP_1024.c:406-415); l[0] is needed only for the decision
+            for (int i = n - 1; i >= ((STOP || last) ? 0 : 1); --i) {
                 const int s = 1 << i;
                 for (int b = tid; b < N / 2; b += nt) {
                     const int j = bp_elem(b, i, n);
@@ -137,17 +188,35 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
                 }
                 if (i > 0) bp_sync(i, i - 1);  // after L stage 1 comes R stage 0 of the next iteration
             }
+            if constexpr (STOP) {
+                __syncthreads();
+                if (tid < 64) {
+                    const bool hold = bp_g_holds(obits, xbits, NW);
+                    if (!hold && !last)   // the next round trip ORs its decisions in afresh
+                        for (int w = tid; w < NW; w += 64) obits[w] = xbits[w] = 0;
+                    if (tid == 0) *stopf = hold;
+                }
+                __syncthreads();
+                if (*stopf) {
+                    done = it + 1;
+                    conv = true;
+                    break;
+                }
+            }
         }
         __syncthreads();
         for (int i = tid; i < NW; i += nt) P.out_bits[(size_t)frame * NW + i] = obits[i];
+        if (STOP && tid == 0) bp_put_stats(P, frame, done, conv);
         __syncthreads();
     }
 }
 
+
 template <typename R>
-constexpr size_t bp_lds_bytes(int N, int n)
+constexpr size_t bp_lds_bytes(int N, int n, bool stop = false)
 {
-    return sizeof(R) * (size_t)N * (1 + 2 * (n - 1)) + sizeof(uint32_t) * (size_t)(N / 32) + 16 + Lut<R>::bytes;
+    return sizeof(R) * (size_t)N * (1 + 2 * (n - 1)) + sizeof(uint32_t) * (size_t)(N / 32) * (stop ? 2 : 1) + (stop ? 16 : 0) +
+           16 + Lut<R>::bytes;
 }
 
 // ---- BP with per-stage read-outs (reference: BPr, BPr_128.c:373-575) -------------------------
@@ -261,14 +330,17 @@ constexpr size_t bp_readout_lds_bytes(int N, int n)
 // ---- BP for block lengths whose messages do not fit one CU's LDS (N > 1024): same schedule, rows in a per-workgroup
 // slice of a global scratch buffer (plain stores, sc1 loads, a workgroup barrier after every stage).  Correct and
 // complete rather than fast: no reference program and no BASELINE config uses BP above N = 1024.
-template <typename R, typename IN>
+// Every row is kept here, so the stop rule (STOP) reads r[n] and l[0] as they are.
+template <typename R, typename IN, bool STOP = false>
 __global__ __launch_bounds__(512) void k_bp_global(BpParams P, R *scratch)
 {
     const int N = P.N, n = P.n, NW = N >> 5;
     const int tid = threadIdx.x, nt = blockDim.x;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *obits = reinterpret_cast<uint32_t *>(smem);   // [NW]
-    unsigned char *lut_mem = reinterpret_cast<unsigned char *>(obits + NW);
+    uint32_t *xbits = obits + NW;                            // STOP: [NW] x_hat, then the stop flag
+    int *stopf = reinterpret_cast<int *>(xbits + NW);
+    unsigned char *lut_mem = reinterpret_cast<unsigned char *>(STOP ? reinterpret_cast<uint32_t *>(stopf + 4) : obits + NW);
     lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
     Lut<R>::build(lut_mem, tid, nt);
     Lut<R> lut;
@@ -293,7 +365,11 @@ __global__ __launch_bounds__(512) void k_bp_global(BpParams P, R *scratch)
             RM(0, j) = ((P.frozen[j >> 5] >> (j & 31)) & 1) ? R(999) : R(0);
         }
         for (int i = tid; i < NW; i += nt) obits[i] = 0;
+        if constexpr (STOP)
+            for (int i = tid; i < NW; i += nt) xbits[i] = 0;
         __syncthreads();
+        int done = P.iters;
+        bool conv = false;
         for (int it = 0; it < P.iters; ++it) {
             for (int i = 0; i < n; ++i) {
                 const int s = 1 << i;
@@ -315,6 +391,26 @@ __global__ __launch_bounds__(512) void k_bp_global(BpParams P, R *scratch)
                 }
                 __syncthreads();
             }
+            if constexpr (STOP) {
+                for (int j = tid; j < N; j += nt) {
+                    const bool fr = (P.frozen[j >> 5] >> (j & 31)) & 1;
+                    if (!fr && !(ld(&LM(0, j)) + ld(&RM(0, j)) >= R(0))) atomicOr(&obits[j >> 5], 1u << (j & 31));
+                    if (!(ld(&LM(n, j)) + ld(&RM(n, j)) >= R(0))) atomicOr(&xbits[j >> 5], 1u << (j & 31));
+                }
+                __syncthreads();
+                if (tid < 64) {
+                    const bool hold = bp_g_holds(obits, xbits, NW);
+                    if (!hold)   // the decision below (or of the next round trip) ORs the bits in afresh
+                        for (int w = tid; w < NW; w += 64) obits[w] = xbits[w] = 0;
+                    if (tid == 0) *stopf = hold;
+                }
+                __syncthreads();
+                if (*stopf) {
+                    done = it + 1;
+                    conv = true;
+                    break;
+                }
+            }
         }
         for (int j = tid; j < N; j += nt) {
             const bool fr = (P.frozen[j >> 5] >> (j & 31)) & 1;
@@ -322,6 +418,7 @@ __global__ __launch_bounds__(512) void k_bp_global(BpParams P, R *scratch)
         }
         __syncthreads();
         for (int i = tid; i < NW; i += nt) P.out_bits[(size_t)frame * NW + i] = obits[i];
+        if (STOP && tid == 0) bp_put_stats(P, frame, done, conv);
         __syncthreads();
     }
 #undef LM

@@ -59,7 +59,12 @@ struct BpR4Cfg {
     static constexpr size_t off_dn = off_lut + ((Lut<R>::bytes + 15) / 16) * 16;
     static constexpr size_t off_st = off_dn + sizeof(R) * 64;
     static constexpr size_t lds_bytes = off_st + Stair<R>::bytes;
+    // stop rule G: the 32 words of u_hat and the 32 of x_hat behind the tables
+    static constexpr size_t off_stop = ((lds_bytes + 15) / 16) * 16;
+    static constexpr size_t lds_bytes_stop = off_stop + 2 * sizeof(uint32_t) * NW;
 };
+// the stop rule must not cost the f64 kernel its third codeword per CU (160 KB of LDS, 16 bytes of static LDS each)
+static_assert(3 * (BpR4Cfg<double>::lds_bytes_stop + 16) <= 160 * 1024, "k_bp_r4<double, double, true>: LDS of three codewords per CU");
 
 template <typename R, typename IN>
 struct BpR4 {
@@ -138,6 +143,20 @@ struct BpR4 {
         }
         // G == 4: stage 9 would only produce r[10], which nobody reads
     }
+    // stop rule: sweepR<4> and stage 9, whose r[10] is not stored, only its hard decisions x_hat = (l[10] + r[10] >= 0) ? 0 : 1
+    // at the elements t + 256 k (bit k of the result)
+    __device__ __forceinline__ uint32_t sweepR4_xhat()
+    {
+        sweepR<4>();
+        R o[4];
+        bfR(Ri[4][0], Ri[4][2], ch[0], ch[2], o[0], o[2]);
+        bfR(Ri[4][1], Ri[4][3], ch[1], ch[3], o[1], o[3]);
+        uint32_t x = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (!(ch[k] + o[k] >= R(0))) x |= 1u << k;
+        return x;
+    }
 
     // ---- left-going sweep, group G: stages 2G+1 then 2G ----
     template <int G, bool LAST>
@@ -179,7 +198,20 @@ struct BpR4 {
 
 __device__ __forceinline__ void bp_wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
-template <typename R, typename IN>
+// decisions of elements 4t .. 4t+3 of this thread (bits 0..3) -> word t >> 3 of u_hat, valid in lanes with t & 7 == 0
+__device__ __forceinline__ uint32_t bp_r4_pack(uint32_t bits, int t)
+{
+    uint32_t w = bits << (4 * (t & 7));
+    w |= (uint32_t)__shfl_xor((int)w, 1);
+    w |= (uint32_t)__shfl_xor((int)w, 2);
+    w |= (uint32_t)__shfl_xor((int)w, 4);
+    return w;
+}
+
+// STOP (stop rule G): stage 9 forms x_hat (ballots into 32 LDS words), l[0] is computed in every round trip, and after the
+// left-going sweep every wave encodes the 32 words of u_hat and compares: the same LDS words give every wave the same answer,
+// so the break is workgroup-uniform with one barrier more per round trip.
+template <typename R, typename IN, bool STOP = false>
 __global__ __launch_bounds__(256, (BpR4Cfg<R>::MIN_BLOCKS)) void k_bp_r4(BpParams P)
 {
     using C = BpR4Cfg<R>;
@@ -203,6 +235,8 @@ __global__ __launch_bounds__(256, (BpR4Cfg<R>::MIN_BLOCKS)) void k_bp_r4(BpParam
 #else
     s.st.bind(smem + C::off_st);
 #endif
+    uint32_t *uw = reinterpret_cast<uint32_t *>(smem + C::off_stop);   // STOP: [32] u_hat, [32] x_hat
+    uint32_t *xw = uw + NW;
     {
         const int e = 4 * s.t;
         s.fz = (P.frozen[e >> 5] >> (e & 31)) & 0xFu;
@@ -232,30 +266,58 @@ __global__ __launch_bounds__(256, (BpR4Cfg<R>::MIN_BLOCKS)) void k_bp_r4(BpParam
         }
 
         uint32_t bits = 0;
+        int done = P.iters;
+        bool conv = false;
         for (int it = 0; it < P.iters; ++it) {
             s.template sweepR<0>(); bp_wave_fence();
             s.template sweepR<1>(); bp_wave_fence();
             s.template sweepR<2>(); bp_wave_fence();
             s.template sweepR<3>();
             __syncthreads();
-            s.template sweepR<4>();
+            if constexpr (STOP) {
+                // x_hat of elements 256 k + 64 w + lane: words 8 k + 2 w and 8 k + 2 w + 1
+                const uint32_t xk = s.sweepR4_xhat();
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint64_t m = __ballot((xk >> k) & 1u);
+                    if ((s.t & 63) == 0) {
+                        xw[8 * k + 2 * (s.t >> 6)] = (uint32_t)m;
+                        xw[8 * k + 2 * (s.t >> 6) + 1] = (uint32_t)(m >> 32);
+                    }
+                }
+            } else {
+                s.template sweepR<4>();
+            }
             s.template sweepL<4, false>(bits);
             __syncthreads();
             s.template sweepL<3, false>(bits); bp_wave_fence();
             s.template sweepL<2, false>(bits); bp_wave_fence();
             s.template sweepL<1, false>(bits); bp_wave_fence();
-            if (it + 1 == P.iters) s.template sweepL<0, true>(bits);
-            else s.template sweepL<0, false>(bits);
-            bp_wave_fence();
+            if constexpr (STOP) {
+                s.template sweepL<0, true>(bits);
+                const uint32_t w = bp_r4_pack(bits, s.t);
+                if ((s.t & 7) == 0) uw[s.t >> 3] = w;
+                __syncthreads();
+                // u_hat / x_hat of round trip it + 1 are read before this wave reaches the next round trip's barrier, and
+                // rewritten only after it
+                if (bp_g_holds(uw, xw, NW)) {
+                    done = it + 1;
+                    conv = true;
+                    break;
+                }
+            } else {
+                if (it + 1 == P.iters) s.template sweepL<0, true>(bits);
+                else s.template sweepL<0, false>(bits);
+                bp_wave_fence();
+            }
         }
         // decisions of elements 4t .. 4t+3: eight lanes make one output word
-        uint32_t w = bits << (4 * (s.t & 7));
-        w |= (uint32_t)__shfl_xor((int)w, 1);
-        w |= (uint32_t)__shfl_xor((int)w, 2);
-        w |= (uint32_t)__shfl_xor((int)w, 4);
+        const uint32_t w = bp_r4_pack(bits, s.t);
         if ((s.t & 7) == 0) P.out_bits[(size_t)frame * NW + (s.t >> 3)] = w;
+        if (STOP && s.t == 0) bp_put_stats(P, frame, done, conv);
         __syncthreads();   // the LDS rows are cleared for the next frame
     }
 }
+
 
 }  // namespace polar

@@ -18,6 +18,7 @@
 #pragma once
 #include "polar_lut.h"
 #include "polar_params.h"
+#include "bp_kernel.h"   // bp_put_stats
 
 namespace polar {
 
@@ -120,7 +121,23 @@ struct BpW128 {
     }
 };
 
-template <typename R, typename IN>
+// x = u F^{(x)7} (gen_kernel.h) on a wave-uniform 128-bit word pair: strides 1..32 are shifts under a mask inside each half,
+// stride 64 adds the upper half to the lower.  Ballot results live in scalar registers, so this is scalar code.
+__device__ __forceinline__ void bpw_encode(uint64_t &lo, uint64_t &hi)
+{
+    constexpr uint64_t M[6] = {0x5555555555555555ull, 0x3333333333333333ull, 0x0F0F0F0F0F0F0F0Full,
+                               0x00FF00FF00FF00FFull, 0x0000FFFF0000FFFFull, 0x00000000FFFFFFFFull};
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        lo ^= (lo >> (1 << i)) & M[i];
+        hi ^= (hi >> (1 << i)) & M[i];
+    }
+    lo ^= hi;
+}
+
+// STOP (stop rule G): stage 6 of the right-going sweep forms x_hat (r[7] itself is not kept), l[0] is computed in every round
+// trip, and the check u_hat F == x_hat is on two pairs of ballots: wave-uniform, no barrier.
+template <typename R, typename IN, bool STOP = false>
 __global__ __launch_bounds__(256, (BpW128Cfg<R>::MIN_WAVES_PER_SIMD)) void k_bp_w128(BpParams P)
 {
     using C = BpW128Cfg<R>;
@@ -156,6 +173,8 @@ __global__ __launch_bounds__(256, (BpW128Cfg<R>::MIN_WAVES_PER_SIMD)) void k_bp_
                 s.lm[i][e] = R(0);               // BP_128.c:340-342
             }
         R l0v[2] = {R(0), R(0)};
+        int done = P.iters;
+        bool conv = false;
         for (int it = 0; it < P.iters; ++it) {
             // right-going sweep (BP_128.c:357-366); stage 6 would only produce r[7], which nobody reads
             s.template stage_r<0>(!(lane & 1));
@@ -164,6 +183,13 @@ __global__ __launch_bounds__(256, (BpW128Cfg<R>::MIN_WAVES_PER_SIMD)) void k_bp_
             s.template stage_r<3>(!(lane & 8));
             s.template stage_r<4>(!(lane & 16));
             s.template stage_r<5>(!(lane & 32));
+            uint64_t xm0 = 0, xm1 = 0;
+            if constexpr (STOP) {   // stage 6: r[7] of the lane's own pair, then x_hat = (l[7] + r[7] >= 0) ? 0 : 1
+                const R a = s.chk(s.rm[5][0], s.ch[1] + s.rm[5][1]);
+                const R c = s.rm[5][1] + s.chk(s.rm[5][0], s.ch[0]);
+                xm0 = __ballot(!(s.ch[0] + a >= R(0)));
+                xm1 = __ballot(!(s.ch[1] + c >= R(0)));
+            }
             // left-going sweep (BP_128.c:368-377)
             s.stage_l6();
             R t[2];
@@ -172,7 +198,19 @@ __global__ __launch_bounds__(256, (BpW128Cfg<R>::MIN_WAVES_PER_SIMD)) void k_bp_
             s.template stage_l<3>(!(lane & 8), t);  s.lm[2][0] = t[0]; s.lm[2][1] = t[1];
             s.template stage_l<2>(!(lane & 4), t);  s.lm[1][0] = t[0]; s.lm[1][1] = t[1];
             s.template stage_l<1>(!(lane & 2), t);  s.lm[0][0] = t[0]; s.lm[0][1] = t[1];
-            if (it + 1 == P.iters) s.template stage_l<0>(!(lane & 1), l0v);   // l[0] is needed only for the decision
+            if constexpr (STOP) {
+                s.template stage_l<0>(!(lane & 1), l0v);
+                uint64_t u0 = __ballot(!f0 && !(l0v[0] + s.r0[0] >= R(0)));
+                uint64_t u1 = __ballot(!f1 && !(l0v[1] + s.r0[1] >= R(0)));
+                bpw_encode(u0, u1);
+                if (u0 == xm0 && u1 == xm1) {
+                    done = it + 1;
+                    conv = true;
+                    break;
+                }
+            } else {
+                if (it + 1 == P.iters) s.template stage_l<0>(!(lane & 1), l0v);   // l[0] is needed only for the decision
+            }
         }
         // BP_128.c:379-387: frozen -> 0, else (l[0] + r[0] >= 0) -> 0
         const bool b0 = !f0 && !(l0v[0] + s.r0[0] >= R(0));
@@ -182,6 +220,7 @@ __global__ __launch_bounds__(256, (BpW128Cfg<R>::MIN_WAVES_PER_SIMD)) void k_bp_
             const uint64_t m = (lane < 2) ? m0 : m1;
             P.out_bits[(size_t)frame * C::NW + lane] = (uint32_t)(m >> (32 * (lane & 1)));
         }
+        if (STOP && lane == 0) bp_put_stats(P, frame, done, conv);
     }
 }
 

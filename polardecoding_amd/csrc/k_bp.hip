@@ -6,13 +6,13 @@
 
 namespace {
 
-// N = 1024: the register-blocked kernel (bp_r4.h), two f64 codewords per CU
+// N = 1024: the register-blocked kernel (bp_r4.h), three f64 codewords per CU; P.stop: its stop-rule instantiation
 template <typename R, typename IN>
 int launch_bp_r4(polar_ctx *c, const polar::BpParams &P)
 {
     using Cfg = polar::BpR4Cfg<R>;
-    auto kern = polar::k_bp_r4<R, IN>;
-    const size_t lds = Cfg::lds_bytes;
+    auto kern = P.stop ? polar::k_bp_r4<R, IN, true> : polar::k_bp_r4<R, IN>;
+    const size_t lds = P.stop ? Cfg::lds_bytes_stop : Cfg::lds_bytes;
     HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int occ = 0;
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, Cfg::THREADS, lds));
@@ -34,7 +34,7 @@ template <typename R, typename IN>
 int launch_bp_w128(polar_ctx *c, const polar::BpParams &P)
 {
     using Cfg = polar::BpW128Cfg<R>;
-    auto kern = polar::k_bp_w128<R, IN>;
+    auto kern = P.stop ? polar::k_bp_w128<R, IN, true> : polar::k_bp_w128<R, IN>;
     const size_t lds = Cfg::lds_bytes;
     int occ = 0;
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * Cfg::WAVES, lds));
@@ -57,11 +57,12 @@ int launch_bp(polar_ctx *c, const polar::BpParams &P)
 {
     if (P.N == 1024 && !c->force_generic) return launch_bp_r4<R, IN>(c, P);
     if (P.N == 128 && !c->force_generic) return launch_bp_w128<R, IN>(c, P);
-    auto kern = polar::k_bp<R, IN>;
-    const size_t lds = polar::bp_lds_bytes<R>(P.N, P.n);
+    const bool stop = P.stop != 0;
+    auto kern = stop ? polar::k_bp<R, IN, true> : polar::k_bp<R, IN>;
+    const size_t lds = polar::bp_lds_bytes<R>(P.N, P.n, stop);
     if (lds > 160 * 1024) {   // messages do not fit a CU's LDS: rows in global scratch
-        auto kg = polar::k_bp_global<R, IN>;
-        const size_t lds_g = 4 * (size_t)(P.N / 32) + 16 + polar::Lut<R>::bytes;
+        auto kg = stop ? polar::k_bp_global<R, IN, true> : polar::k_bp_global<R, IN>;
+        const size_t lds_g = 4 * (size_t)(P.N / 32) * (stop ? 2 : 1) + (stop ? 16 : 0) + 16 + polar::Lut<R>::bytes;
         int grid = (int)std::min<long long>((long long)P.B, (long long)2 * c->num_cu);
         if (grid < 1) grid = 1;
         int rc = ensure(c, c->scratch, sizeof(R) * 2 * (size_t)(P.n + 1) * P.N * (size_t)grid);

@@ -87,7 +87,7 @@ bool fast_ok(const polar_ctx *c, int in_is_f32)
 }
 
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
-                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen)
+                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
 {
     if (!c || !d_in || !d_bits) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
@@ -99,7 +99,14 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
         P.in = d_in; P.sigma = sigma; P.out_bits = d_bits; P.frozen = d_frozen;
         P.N = g.N; P.n = c->n; P.B = (int)B; P.iters = g.bp_iters;
         if (d_pm) HIP_TRY(c, hipMemsetAsync(d_pm, 0, B * sizeof(double), c->stream));
-        if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, B * sizeof(uint32_t), c->stream));
+        P.stop = c->bp_stop;
+        if (P.stop != POLAR_BP_STOP_NONE) {   // the kernel writes both for every frame
+            P.iters_out = d_iters;
+            P.flags_out = d_flags;
+        } else {
+            if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, B * sizeof(uint32_t), c->stream));
+            if (d_iters) HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), g.bp_iters, B, c->stream));
+        }
         return polar_tu::bp(c, P, f32, in_is_f32 != 0);
     }
     polar::SclParams P{};
@@ -138,7 +145,8 @@ void refresh_kernel_name(polar_ctx *c)
     const char *ty = g.dtype == POLAR_F32 ? "float" : "double";
     char nm[128];
     if (g.algo == POLAR_ALGO_BP)
-        snprintf(nm, sizeof nm, (g.N == 1024 && !c->force_generic) ? "k_bp_r4<%s>" : (g.N == 128 && !c->force_generic) ? "k_bp_w128<%s>" : "k_bp<%s>", ty);
+        snprintf(nm, sizeof nm, (g.N == 1024 && !c->force_generic) ? "k_bp_r4<%s>%s" : (g.N == 128 && !c->force_generic) ? "k_bp_w128<%s>%s" : "k_bp<%s>%s",
+                 ty, c->bp_stop == POLAR_BP_STOP_G ? " (stop rule G)" : "");
     else
         snprintf(nm, sizeof nm, "k_scl_generic<%s,L=%d>", ty, g.L);
     if (g.algo != POLAR_ALGO_BP && g.algo != POLAR_ALGO_SC && !c->force_generic && c->n >= 9 && g.L >= 2)
@@ -182,7 +190,7 @@ void unpack_words(const uint32_t *w, int NW, int *out)
 #define POLAR_HOST_THREADS 6   // 4 -> 6: end_to_end 4.4 -> 4.6-4.7 M frames/s; 8 and 12 no more (run 35)
 #endif
 int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char *frozen_mask, size_t B,
-               int *u_hat, double *pm_out, unsigned *flags)
+               int *u_hat, double *pm_out, unsigned *flags, unsigned *iters = nullptr)
 {
     if (!c || !in || !u_hat) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
@@ -201,6 +209,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     int rc;
     if ((rc = ensure(c, c->pm, B * sizeof(double)))) return rc;
     if ((rc = ensure(c, c->flags, B * sizeof(uint32_t)))) return rc;
+    if (iters && (rc = ensure(c, c->bp_iters, B * sizeof(uint32_t)))) return rc;
     // Chunked pipeline: while chunk k is decoded, chunk k+1 crosses PCIe on a second stream and the decisions of
     // chunk k-1 are unpacked to the caller's int array by helper threads.  The input is pageable caller memory: a
     // hipMemcpyAsync from it is a single-threaded staging copy inside the runtime (about 18 GB/s) that blocks this thread.
@@ -319,7 +328,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         // h_bits[s] / bits2[s] were last used by chunk k-2, whose unpacking ran during the copy above
         if (worker.joinable()) worker.join();
         rc = decode_device_impl(c, c->in2[s].p, 0, sigma, nf, (uint32_t *)c->bits2[s].p, (double *)c->pm.p + f0,
-                                (uint32_t *)c->flags.p + f0, d_frozen);
+                                (uint32_t *)c->flags.p + f0, d_frozen, iters ? (uint32_t *)c->bp_iters.p + f0 : nullptr);
         if (rc) return fail_join(rc);
         if (hipEventRecord(c->ev_free[s], c->stream) != hipSuccess) return fail_join(POLAR_EDEVICE);
         if (hipMemcpyAsync(c->h_bits[s], c->bits2[s].p, nf * NW * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) !=
@@ -336,6 +345,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     unpack_chunk(nch - 1);
     if (pm_out) HIP_TRY(c, hipMemcpyAsync(pm_out, c->pm.p, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (flags) HIP_TRY(c, hipMemcpyAsync(flags, c->flags.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (iters) HIP_TRY(c, hipMemcpyAsync(iters, c->bp_iters.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return POLAR_OK;
 }
@@ -343,6 +353,8 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
 }  // namespace
 
 extern "C" {
+
+static_assert(polar::BP_FLAG_CONVERGED == POLAR_FLAG_BP_CONVERGED, "kernel and C ABI flag bit");
 
 const char *polar_version(void) { return "polar_hip 0.1 (gfx950)"; }
 
@@ -478,7 +490,7 @@ void polar_destroy(polar_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
-    for (Buf *b : {&c->in, &c->bits, &c->pm, &c->flags, &c->scratch, &c->gen_llr, &c->gen_u, &c->gen_cnt, &c->in2[0],
+    for (Buf *b : {&c->in, &c->bits, &c->pm, &c->flags, &c->bp_iters, &c->scratch, &c->gen_llr, &c->gen_u, &c->gen_cnt, &c->in2[0],
                    &c->in2[1], &c->bits2[0], &c->bits2[1], &c->scratch_b})
     {
         if (b->p) (void)hipFree(b->p);
@@ -614,12 +626,35 @@ int polar_decode_llr(const double *llr_in, const unsigned char *frozen_mask, int
     return host_batch(c, llr_in, 0.0, nullptr, 1, u_hat, nullptr, nullptr);
 }
 
+int polar_bp_set_stop(polar_ctx *c, int rule)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BP || (rule != POLAR_BP_STOP_NONE && rule != POLAR_BP_STOP_G)) return POLAR_EINVAL;
+    c->bp_stop = rule;
+    refresh_kernel_name(c);
+    return POLAR_OK;
+}
+
+int polar_bp_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                           uint32_t *d_iters, uint32_t *d_flags)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BP) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, nullptr, d_flags, c->d_frozen, d_iters);
+}
+
+int polar_bp_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, unsigned *iters, unsigned *flags)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BP) return POLAR_EINVAL;
+    return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, nullptr, flags, iters);
+}
+
 int polar_bp_readout_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B,
                             const uint32_t *d_u_bits, const int *checkpoints, int ncp, unsigned long long *d_E,
                             uint32_t *d_uhat_bits)
 {
     if (!c || !d_in || !d_u_bits || !checkpoints || !d_E) return POLAR_EINVAL;
     if (c->cfg.algo != POLAR_ALGO_BP || ncp < 1 || ncp > 8 || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (c->bp_stop != POLAR_BP_STOP_NONE) return POLAR_EINVAL;   // the checkpoints need every frame to run all round trips
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     polar::BpReadoutParams P{};
@@ -639,7 +674,7 @@ int polar_bp_readout_batch(polar_ctx *c, const double *in, double sigma, size_t 
                            int ncp, unsigned long long *E, int *u_hat)
 {
     if (!c || !in || !u || !checkpoints || !E) return POLAR_EINVAL;
-    if (ncp < 1 || ncp > 8) return POLAR_EINVAL;
+    if (ncp < 1 || ncp > 8 || c->bp_stop != POLAR_BP_STOP_NONE) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     const int N = c->cfg.N, NW = c->NW, n = c->n;

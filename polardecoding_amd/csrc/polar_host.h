@@ -38,6 +38,8 @@ struct polar_ctx {
     bool own_stream = false;
     int num_cu = 0;
     Buf in, bits, pm, flags;              // staging for the host-pointer entry points
+    Buf bp_iters;                         // polar_bp_decode_batch: round trips per frame
+    int bp_stop = POLAR_BP_STOP_NONE;     // polar_bp_set_stop
     Buf in2[2], bits2[2];                 // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;

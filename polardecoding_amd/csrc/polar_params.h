@@ -27,7 +27,11 @@ struct BpParams {
     const uint32_t *frozen;  // [N/32]
     int N, n, B, iters;
     unsigned *queue;         // as in SclParams
+    int stop;                // POLAR_BP_STOP_*: 0 = iters round trips; 1 = stop at the first round trip with u_hat F = x_hat
+    uint32_t *iters_out;     // [B] round trips run per frame, or null
+    uint32_t *flags_out;     // [B] BP_FLAG_CONVERGED when the stop criterion held at the last round trip run, or null
 };
+constexpr uint32_t BP_FLAG_CONVERGED = 0x8u;   // POLAR_FLAG_BP_CONVERGED
 
 // BP with per-stage read-outs (reference: BPr, BPr_128.c:373-575), see bp_kernel.h
 struct BpReadoutParams {

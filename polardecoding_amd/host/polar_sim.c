@@ -175,14 +175,15 @@ static const int CRC6[] = {0, 5, 6};
 static void usage(void)
 {
     fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
-                    "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n");
+                    "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
+                    "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n");
     exit(2);
 }
 
 int main(int argc, char **argv)
 {
     int N = 1024, K = 512, L = 8, algo = POLAR_ALGO_CASCL, ble = 100, batch = 4096, dtype = POLAR_F64, bp_iters = 100;
-    int fast = 0, sys = 0, bpr = 0, gpus = 1;
+    int fast = 0, sys = 0, bpr = 0, gpus = 1, bp_stop = POLAR_BP_STOP_NONE;
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
     double lo = 1.0, hi = 3.0, step = 0.5;
@@ -213,6 +214,11 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--fast")) { fast = 1; }
         else if (!strcmp(a, "--gpus") && v) { gpus = atoi(v); i++; }   /* --fast only: frames sharded over the GPUs of the node */
         else if (!strcmp(a, "--sys")) { sys = 1; }
+        else if (!strcmp(a, "--bp-stop") && v) {   /* polar_bp_set_stop */
+            if (strcmp(v, "g")) usage();
+            bp_stop = POLAR_BP_STOP_G;
+            i++;
+        }
         else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : POLAR_F64; i++; }
         else if (!strcmp(a, "--snr-list") && v) {
             const char *q = v;
@@ -296,6 +302,11 @@ int main(int argc, char **argv)
     polar_ctx *ctx = NULL;
     int rc = (c.gc) ? polar_create_crc_file(&cfg, crcfile, &ctx) : polar_create(&cfg, &ctx);
     if (rc) { fprintf(stderr, "polar_create: %s\n", polar_strerror(rc)); return 1; }
+    if (bp_stop != POLAR_BP_STOP_NONE) {
+        /* the read-outs need fixed iterations; a polar_group builds its contexts from cfg and has no stop rule */
+        if (bpr || (fast && gpus > 1)) { fprintf(stderr, "--bp-stop: not with --algo bpr or --gpus > 1\n"); return 1; }
+        if ((rc = polar_bp_set_stop(ctx, bp_stop)) != 0) { fprintf(stderr, "--bp-stop: %s\n", polar_strerror(rc)); return 1; }
+    }
     /* the library built the frozen set from the 5G sequence like the reference (I[i] = Q[N-(K+r)+i]);
        the encoder needs the same I[] */
     c.I = (int *)malloc(sizeof(int) * (size_t)c.A);
@@ -343,7 +354,12 @@ int main(int argc, char **argv)
         return 0;
     }
     static const int CP[6] = {3, 6, 10, 20, 40, 80};        /* BPr_128.c:18-23 */
-    int *ui = bpr ? (int *)malloc(sizeof(int) * (size_t)batch * N) : NULL;
+    int *ui = (bpr || bp_stop) ? (int *)malloc(sizeof(int) * (size_t)batch * N) : NULL;
+    /* --bp-stop: the round trips of the counted frames come from a second decode of those frames (statistics only) */
+    double *llr = bp_stop ? (double *)malloc(sizeof(double) * (size_t)batch * N) : NULL;
+    unsigned *its = bp_stop ? (unsigned *)malloc(sizeof(unsigned) * (size_t)batch) : NULL;
+    if ((bpr || bp_stop) && !ui) { fprintf(stderr, "out of memory\n"); return 1; }
+    if (bp_stop && (!llr || !its)) { fprintf(stderr, "out of memory\n"); return 1; }
     int nlog = 0;
     while ((1 << nlog) < N) nlog++;
     for (int ip = 0; ip < npts; ip++) {
@@ -353,6 +369,8 @@ int main(int argc, char **argv)
         int errblock = 0;
         unsigned long long E[6 * 16];
         memset(E, 0, sizeof E);
+        unsigned long long it_sum = 0;
+        unsigned it_max = 0;
         while (errblock < ble || run < min_run) {
             make_batch(&g, &c, sigma, batch, u, y, after, pairs, mf);
             for (size_t k = 0; k < (size_t)batch * (N / 32); k++) { /* sent bits, packed like the decisions */
@@ -376,6 +394,15 @@ int main(int argc, char **argv)
                 rc = polar_bp_readout_batch(ctx, y, sigma, (size_t)f, ui, CP, 6, E, NULL);
                 if (rc) { fprintf(stderr, "readout: %s (%s)\n", polar_strerror(rc), polar_last_error(ctx)); return 1; }
             }
+            if (bp_stop && f > 0) {
+                for (size_t k = 0; k < (size_t)f * N; k++) llr[k] = 2 * y[k] / sigma / sigma;   /* the kernel's llr_from_y */
+                rc = polar_bp_decode_batch(ctx, llr, (size_t)f, ui, its, NULL);
+                if (rc) { fprintf(stderr, "bp_decode: %s (%s)\n", polar_strerror(rc), polar_last_error(ctx)); return 1; }
+                for (int k = 0; k < f; k++) {
+                    it_sum += its[k];
+                    if (its[k] > it_max) it_max = its[k];
+                }
+            }
             if (errblock >= ble && run >= min_run) g = after[f - 1]; /* rewind to just after the frame that ended the point */
         }
         if (bpr) { /* BPr_128.c:227-258 */
@@ -398,8 +425,12 @@ int main(int argc, char **argv)
                    (double)errblock / (run / 10000.0));
         }
         fflush(stdout);
+        if (bp_stop)
+            fprintf(stderr, "bp-stop g: bSNR = %.2lf\trun = %ld\tmean iterations = %.3lf\tmax iterations = %u\n", db, run,
+                    run ? (double)it_sum / run : 0.0, it_max);
     }
     polar_destroy(ctx);
+    free(ui); free(llr); free(its);
     free(y); free(u); free(ubits); free(after); free(c.I); free(qorder);
     return 0;
 }
