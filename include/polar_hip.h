@@ -203,6 +203,35 @@ int polar_bp_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, doub
 /* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N], iters / flags (nullable) [B]. */
 int polar_bp_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *iters, unsigned *flags);
 
+/* --- adaptive CA-SCL (opt-in; Li, Chen and Liu, 2012): re-decode only the CRC-failing frames with larger lists ----------
+ * A rule belongs to a POLAR_ALGO_CASCL context, including ones made by polar_create_crc_file and ones with crc_systematic
+ * set.  The rule is a list of list sizes stages[0] < stages[1] < ... < stages[m-1] = cfg.L: each stage is a power of two,
+ * 1 <= m <= 6, and cfg.L >= 2 whenever m > 1.  Each stage s defines a decision for every frame:
+ *   L_s >= 2: the decision, path metric and flags of the fixed CA-SCL decoder of this context with list size L_s -- bit for
+ *             bit what polar_create returns with the same cfg and L = L_s.  The frame passes if POLAR_FLAG_CRC_PASS is set.
+ *   L_s = 1 (first stage only): the decision of POLAR_ALGO_SC with the same info_order[0 .. K+r), the CRC positions treated
+ *             as information bits.  The frame passes if XOR over {j : u_hat_j = 1} of crc_tab[j] is 0 (crc_tab[I[i]] =
+ *             D^i mod g(D)), the same test the list kernels apply.  The reported metric is 0.0; the reported flags are the
+ *             SC context's flags, with POLAR_FLAG_CRC_PASS added on a pass.
+ * A frame's output is the output of the first stage at which it passes.  A frame that passes at no stage takes the output
+ * of the last stage (L_max), with its flags, so POLAR_FLAG_CRC_PASS is clear.  A frame that is not re-decoded is never
+ * touched again.  The single-stage rule {cfg.L} is exactly the default decoder; so is clearing the rule (n = 0); in both
+ * cases no new kernel runs.  dtype POLAR_F32 runs every stage in f32 (compare with the library's own fixed-L f32 contexts).
+ * The rule is honoured by polar_decode, polar_decode_batch(_y), polar_decode_device, polar_fer_batch,
+ * polar_stop_rule_batch_y and polar_time_decode_device.  polar_group_* and polar_fer_multi_gpu build their contexts from a
+ * polar_cfg and always run the default decoder.
+ * Between stages the host reads the count of failing frames (one 4-byte copy and a stream sync per stage) and stops after a
+ * stage with zero failures; a decode with a rule set while the ctx stream is capturing a graph returns POLAR_EINVAL. */
+/* POLAR_EINVAL: not a CA-SCL ctx, or a malformed list.  n = 0 restores the default. */
+int polar_cascl_set_stages(polar_ctx *ctx, const int *stages, int n);
+/* polar_decode_device for a CA-SCL ctx, plus per frame d_list (nullable) [B]: the list size of the stage that decided it
+ * (1 for SC; cfg.L without a rule).  d_pm, d_flags, d_list are nullable. */
+int polar_cascl_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
+                              uint32_t *d_uhat_bits, double *d_pm, uint32_t *d_flags, uint32_t *d_list);
+/* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N]; pm, flags, list (nullable) [B]. */
+int polar_cascl_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, double *pm, unsigned *flags,
+                             unsigned *list);
+
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at
  * Eb/N0 = snr_db (sigma = 10^(-snr_db/20), rate 1/2 as in the reference, :237) -> d_out[B][N] (double, or float

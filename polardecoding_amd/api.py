@@ -88,6 +88,9 @@ def load_library(testing=False):
     L.polar_bp_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
     L.polar_bp_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
     L.polar_bp_readout_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, ip, C.c_int, vp, vp]
+    L.polar_cascl_set_stages.argtypes = [vp, ip, C.c_int]
+    L.polar_cascl_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp, vp]
+    L.polar_cascl_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, dp, up, up]
     L.polar_generate_device.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp, C.c_int,
                                         C.c_int, vp]
     L.polar_fer_batch.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, C.POINTER(C.c_ulonglong),
@@ -180,6 +183,7 @@ class Decoder:
         self._crc_file = os.fsencode(crc_file) if crc_file is not None else None   # g(D) and r from a generator-matrix file
         self._cfg, self._cfg_keep = cfg, (taps, io)   # kept for polar_fer_multi_gpu (the arrays the struct points to must stay alive)
         self.bp_stop = BP_STOP_NONE
+        self.cascl_stages = ()
         self._create()
         A, Lr = C.c_int(), C.c_int()
         self._lib.polar_ctx_info(self._h, None, None, C.byref(A), C.byref(Lr), None, None)
@@ -204,6 +208,8 @@ class Decoder:
         self._create()
         if self.bp_stop != BP_STOP_NONE:
             self.set_bp_stop(self.bp_stop)
+        if self.cascl_stages:
+            self.set_cascl_stages(self.cascl_stages)
 
     @property
     def info_order(self):
@@ -237,6 +243,14 @@ class Decoder:
         code = _BP_STOP_RULES[rule]
         self._check(self._lib.polar_bp_set_stop(self._h, code), "polar_bp_set_stop")
         self.bp_stop = code
+
+    def set_cascl_stages(self, stages):
+        """Adaptive CA-SCL (polar_cascl_set_stages): decode with the first list size, re-decode only the frames whose chosen
+        path fails the CRC with the next, up to cfg.L (stages[-1] must equal L; 1 = SC).  () or None restores the default."""
+        st = np.asarray(list(stages) if stages else [], dtype=np.int32)
+        self._check(self._lib.polar_cascl_set_stages(self._h, _ptr(st, C.c_int) if st.size else None, int(st.size)),
+                    "polar_cascl_set_stages")
+        self.cascl_stages = tuple(int(x) for x in st) if st.size > 1 else ()
 
     @property
     def kernel_name(self):
@@ -329,6 +343,43 @@ class Decoder:
             C.c_void_p(iters.data_ptr()) if iters is not None else None,
             C.c_void_p(flags.data_ptr()) if flags is not None else None), "polar_bp_decode_device")
         return out_bits
+
+    def decode_cascl_device(self, d_in, sigma=0.0, out_bits=None, pm=None, flags=None, list_size=None):
+        """polar_cascl_decode_device: like decode_device, plus per frame the list size of the stage that decided it
+        (`list_size`, int32 [B], 1 = SC); pm (float64 [B]), flags and list_size are optional tensors.  Returns out_bits."""
+        import torch
+        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
+        B = d_in.numel() // self.N
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        for t in (flags, list_size):
+            if t is not None and (t.numel() < B or t.element_size() != 4 or not t.is_contiguous()):
+                raise ValueError("flags / list_size must be contiguous 32-bit tensors of at least B elements")
+        if pm is not None and (pm.numel() < B or pm.dtype != torch.float64 or not pm.is_contiguous()):
+            raise ValueError("pm must be a contiguous float64 tensor of at least B elements")
+        self._check(self._lib.polar_cascl_decode_device(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B, C.c_void_p(out_bits.data_ptr()),
+            C.c_void_p(pm.data_ptr()) if pm is not None else None,
+            C.c_void_p(flags.data_ptr()) if flags is not None else None,
+            C.c_void_p(list_size.data_ptr()) if list_size is not None else None), "polar_cascl_decode_device")
+        return out_bits
+
+    def decode_cascl_batch(self, llr):
+        """polar_cascl_decode_batch: llr [B][N] -> (u_hat [B][N] int32, pm [B] float64, flags [B] uint32,
+        list size [B] uint32)."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        B = llr.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        pm = np.zeros(B, dtype=np.float64)
+        fl = np.zeros(B, dtype=np.uint32)
+        ls = np.zeros(B, dtype=np.uint32)
+        self._check(self._lib.polar_cascl_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
+                                                       _ptr(pm, C.c_double), _ptr(fl, C.c_uint), _ptr(ls, C.c_uint)),
+                    "polar_cascl_decode_batch")
+        return uh, pm, fl, ls
 
     def decode_bp_batch(self, llr):
         """polar_bp_decode_batch: llr [B][N] -> (u_hat [B][N] int32, iters [B] uint32, flags [B] uint32)."""
@@ -485,14 +536,20 @@ def SCLdecode(N, K, L=8, **kw):
     return Decoder(N, K, ALGO_SCL, L=L, **kw)
 
 
-def CASCL(N, K, L=8, crc_taps=CRC24C_TAPS, crc_file=None, **kw):
+def CASCL(N, K, L=8, crc_taps=CRC24C_TAPS, crc_file=None, stages=None, **kw):
     """CASCL_1024_L8.c:601 -- ``CASCL(y, u_hat)``; r and g(D) are CASCL_1024_L8.c:2-4, :19.
     ``systematic=True`` is CASCL_1024_sys.c: same decoder, systematic CRC in the generator, K-bit error metric.
     ``crc_file``: r and g(D) from a generator-matrix file instead (the reference's CRC_6.dat; ``Gc`` of
-    CASCL_1024_sys.c:48-561 in the same layout) -- polar_create_crc_file."""
+    CASCL_1024_sys.c:48-561 in the same layout) -- polar_create_crc_file.
+    ``stages``: adaptive CA-SCL, e.g. ``CASCL(1024, 512, L=32, stages=(1, 8, 32))`` (Decoder.set_cascl_stages);
+    None: every frame decoded with list size L."""
     if crc_file is not None:
-        return Decoder(N, K, ALGO_CASCL, L=L, crc_taps=None, crc_file=crc_file, **kw)
-    return Decoder(N, K, ALGO_CASCL, L=L, crc_taps=crc_taps, **kw)
+        dec = Decoder(N, K, ALGO_CASCL, L=L, crc_taps=None, crc_file=crc_file, **kw)
+    else:
+        dec = Decoder(N, K, ALGO_CASCL, L=L, crc_taps=crc_taps, **kw)
+    if stages is not None:
+        dec.set_cascl_stages(stages)
+    return dec
 
 
 def decode(llr_in, frozen_mask, N, L):

@@ -86,8 +86,9 @@ bool fast_ok(const polar_ctx *c, int in_is_f32)
     return true;
 }
 
-int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
-                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
+// the fixed decoder of ctx c (its cfg.L / algo): the kernel selection every entry point uses
+int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
+                 double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
 {
     if (!c || !d_in || !d_bits) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
@@ -138,6 +139,98 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
     return polar_tu::scl_generic(c, P, f32, in32);
 }
 
+// The stage contexts run on this ctx's stream with its test-only kernel choices (include/polar_hip_testing.h).
+void refresh_kernel_name(polar_ctx *c);
+void sync_stage_ctx(polar_ctx *c)
+{
+    for (polar_ctx *s : c->stage_ctx) {
+        if (!s) continue;
+        s->stream = c->stream;
+        s->force_generic = c->force_generic;
+        s->force_spill = c->force_spill;
+        s->use_fast2 = c->use_fast2;
+        s->use_fast4 = c->use_fast4;
+        s->big_split = c->big_split;
+    }
+}
+
+// Adaptive CA-SCL (polar_cascl_set_stages): stage 0 decodes the whole batch into the caller's outputs; every later stage
+// gathers the rows of the frames that failed the stage before (stable compaction of the flags words), decodes them with
+// its list size and scatters the results back.  One 4-byte copy and a stream sync per later stage: the failing count.
+int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
+                   double *d_pm, uint32_t *d_flags, uint32_t *d_list)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the per-stage syncs cannot be captured
+    sync_stage_ctx(c);
+    const std::vector<int> &st = c->cascl_stages;
+    const int m = (int)st.size(), N = c->cfg.N, NW = c->NW;
+    const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
+    // later stages run in chunks of at most 256 MiB of gathered input
+    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
+    int rc;
+    // every buffer of the call, before its first launch
+    if (!d_flags) {
+        if ((rc = ensure(c, c->ad_flags, B * sizeof(uint32_t)))) return rc;
+        d_flags = (uint32_t *)c->ad_flags.p;
+    }
+    for (Buf *b : {&c->ad_idx[0], &c->ad_idx[1], &c->ad_sflags})
+        if ((rc = ensure(c, *b, B * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->ad_in, CH * row))) return rc;
+    if ((rc = ensure(c, c->ad_bits, CH * NW * sizeof(uint32_t)))) return rc;
+    if (d_pm && (rc = ensure(c, c->ad_pm, CH * sizeof(double)))) return rc;
+
+    polar_ctx *s0 = c->stage_ctx[0] ? c->stage_ctx[0] : c;
+    if ((rc = decode_fixed(s0, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, s0->d_frozen))) return rc;
+    if (st[0] == 1 && (rc = polar_tu::ad_crc_check(c, d_bits, d_flags, B))) return rc;
+    if (d_list) HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_list), st[0], B, c->stream));
+    const uint32_t *cur_idx = nullptr, *cur_flags = d_flags;
+    size_t n = B;
+    for (int s = 1; s < m; ++s) {
+        uint32_t *idx = (uint32_t *)c->ad_idx[(s - 1) & 1].p;
+        if ((rc = polar_tu::ad_compact(c, cur_flags, cur_idx, n, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p)))
+            return rc;
+        uint32_t h = 0;
+        HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        n = h;
+        if (n == 0) break;
+        polar_ctx *sc = c->stage_ctx[(size_t)s] ? c->stage_ctx[(size_t)s] : c;
+        uint32_t *sflags = (uint32_t *)c->ad_sflags.p;
+        for (size_t off = 0; off < n; off += CH) {
+            const size_t nc = std::min(CH, n - off);
+            if ((rc = polar_tu::ad_gather(c, d_in, c->ad_in.p, idx + off, nc, row))) return rc;
+            if ((rc = decode_fixed(sc, c->ad_in.p, in_is_f32, sigma, nc, (uint32_t *)c->ad_bits.p,
+                                   d_pm ? (double *)c->ad_pm.p : nullptr, sflags + off, sc->d_frozen)))
+                return rc;
+            if ((rc = polar_tu::ad_scatter(c, (uint32_t *)c->ad_bits.p, (double *)c->ad_pm.p, sflags + off, idx + off, nc,
+                                           d_bits, d_pm, d_flags, d_list, st[(size_t)s])))
+                return rc;
+        }
+        cur_idx = idx;
+        cur_flags = sflags;
+    }
+    return POLAR_OK;
+}
+
+// every decode of the C ABI: the fixed decoder, or for a CA-SCL ctx with a stage rule the adaptive one.
+// d_iters: BP round trips per frame; CA-SCL: the list size that decided each frame.
+int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
+                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
+{
+    if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
+        if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+        if (B == 0) return POLAR_OK;
+        if (!c->cascl_stages.empty()) return cascl_adaptive(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
+        if (d_iters) HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), c->cfg.L, B, c->stream));
+        d_iters = nullptr;
+    }
+    return decode_fixed(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters);
+}
+
 // the kernel instantiation decode_device_impl will launch for this ctx (mirrors its choices)
 void refresh_kernel_name(polar_ctx *c)
 {
@@ -156,6 +249,17 @@ void refresh_kernel_name(polar_ctx *c)
     if (fast_ok(c, g.dtype == POLAR_F32))
         snprintf(nm, sizeof nm, "k_scl_fast%s<%s,N=%d,L=8>", (g.N == 1024 && c->use_fast4) ? "4" : (g.N == 1024 && c->use_fast2) ? "2" : "", ty, g.N);
     c->kernel_name = nm;
+    if (!c->cascl_stages.empty()) {
+        sync_stage_ctx(c);
+        std::string a = "adaptive CA-SCL:";
+        for (size_t i = 0; i < c->cascl_stages.size(); ++i) {
+            polar_ctx *s = c->stage_ctx[i];
+            if (s) refresh_kernel_name(s);
+            a += (i ? " -> L=" : " L=") + std::to_string(c->cascl_stages[i]) + " " + (s ? s->kernel_name : std::string(nm));
+        }
+        a += "; glue k_ad_crc_check, k_ad_fail_count/scan/write, k_ad_gather, k_ad_scatter";
+        c->kernel_name = a;
+    }
 }
 
 std::vector<uint32_t> pack_mask(const unsigned char *m, int N, bool invert)
@@ -503,6 +607,10 @@ void polar_destroy(polar_ctx *c)
         if (c->ev_free[i]) (void)hipEventDestroy(c->ev_free[i]);
         if (c->ev_out[i]) (void)hipEventDestroy(c->ev_out[i]);
     }
+    for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
+    for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
+                   &c->ad_pm, &c->ad_sflags})
+        if (b->p) (void)hipFree(b->p);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
     if (c->ev_b) (void)hipEventDestroy(c->ev_b);
@@ -632,6 +740,61 @@ int polar_bp_set_stop(polar_ctx *c, int rule)
     c->bp_stop = rule;
     refresh_kernel_name(c);
     return POLAR_OK;
+}
+
+int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || n < 0 || n > 6 || (n > 0 && !stages)) return POLAR_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const int L = stages[i];
+        if (L < 1 || L > 32 || (L & (L - 1)) || (i && L <= stages[i - 1])) return POLAR_EINVAL;
+    }
+    if (n > 0 && stages[n - 1] != c->cfg.L) return POLAR_EINVAL;
+    if (n > 1 && c->cfg.L < 2) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    std::vector<polar_ctx *> subs;
+    if (n > 1) {
+        subs.assign((size_t)n, nullptr);   // the last stage (L = cfg.L) is this ctx's own decoder
+        for (int i = 0; i + 1 < n; ++i) {
+            polar_cfg g = c->cfg;          // crc_taps / info_order point into c
+            g.L = stages[i];
+            if (stages[i] == 1) {          // SC over I[0..K+r): the CRC positions decoded as information bits
+                g.algo = POLAR_ALGO_SC;
+                g.K = c->A;
+                g.crc_r = 0;
+                g.crc_taps = nullptr;
+                g.n_taps = 0;
+                g.crc_systematic = 0;
+            }
+            int rc = polar_create(&g, &subs[(size_t)i]);
+            if (!rc) rc = polar_set_stream(subs[(size_t)i], c->stream);
+            if (rc) {
+                for (polar_ctx *s : subs) polar_destroy(s);
+                return rc;
+            }
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // no queued work still uses the old stage contexts
+    for (polar_ctx *s : c->stage_ctx) polar_destroy(s);
+    c->stage_ctx = subs;
+    c->cascl_stages = n > 1 ? std::vector<int>(stages, stages + n) : std::vector<int>();
+    refresh_kernel_name(c);
+    return POLAR_OK;
+}
+
+int polar_cascl_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                              double *d_pm, uint32_t *d_flags, uint32_t *d_list)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, d_pm, d_flags, c->d_frozen, d_list);
+}
+
+int polar_cascl_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, double *pm, unsigned *flags,
+                             unsigned *list)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, pm, flags, list);
 }
 
 int polar_bp_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
@@ -815,7 +978,8 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
     // Two halves on two streams (own decode scratch each): the generator of one half and the partly filled last
     // pass of its decode overlap the other half's decode.  Frame i of the batch is the same frame either way
     // (the generator is counter-based), and the two counters are atomics.
-    const size_t half = (B >= 32768) ? (B / 2 + 63) / 64 * 64 : B;
+    // (not with an adaptive CA-SCL rule: its stage buffers belong to one stream and it syncs between stages)
+    const size_t half = (B >= 32768 && c->cascl_stages.empty()) ? (B / 2 + 63) / 64 * 64 : B;
     if (half < B && !c->stream_b) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming));

@@ -40,6 +40,13 @@ struct polar_ctx {
     Buf in, bits, pm, flags;              // staging for the host-pointer entry points
     Buf bp_iters;                         // polar_bp_decode_batch: round trips per frame
     int bp_stop = POLAR_BP_STOP_NONE;     // polar_bp_set_stop
+    // adaptive CA-SCL (polar_cascl_set_stages): list sizes of the stages (empty = the fixed decoder) and one context per
+    // stage (an SC context for L = 1, null for L = cfg.L: this context's own fixed decoder)
+    std::vector<int> cascl_stages;
+    std::vector<polar_ctx *> stage_ctx;
+    Buf ad_flags;                         // per-frame flags when the caller passes none
+    Buf ad_idx[2], ad_blk, ad_cnt;        // failing-frame lists (ping-pong), compaction block counts, device count
+    Buf ad_in, ad_bits, ad_pm, ad_sflags; // a later stage's gathered input and outputs
     Buf in2[2], bits2[2];                 // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
@@ -127,6 +134,14 @@ int scl_fast(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool 
 int scl_fast2(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast2.hip: N = 1024, two per wave (headline)
 int bp(polar_ctx *c, const polar::BpParams &P, bool r32, bool in32);                       // k_bp.hip
 int bp_readout(polar_ctx *c, const polar::BpReadoutParams &P, bool r32, bool in32);        // k_bp.hip
+// k_adaptive.hip: the glue of the adaptive CA-SCL decoder (adaptive_kernel.h)
+int ad_crc_check(polar_ctx *c, const uint32_t *d_bits, uint32_t *d_flags, size_t B);      // CRC syndrome of SC decisions
+size_t ad_blocks(size_t n);                                                               // compaction blocks for n frames
+int ad_compact(polar_ctx *c, const uint32_t *d_flags, const uint32_t *d_idx_in, size_t n, uint32_t *d_blk,
+               uint32_t *d_idx_out, uint32_t *d_count);                                   // d_blk: 2 * ad_blocks(n) words
+int ad_gather(polar_ctx *c, const void *d_src, void *d_dst, const uint32_t *d_idx, size_t n, size_t row_bytes);
+int ad_scatter(polar_ctx *c, const uint32_t *s_bits, const double *s_pm, const uint32_t *s_flags, const uint32_t *d_idx,
+               size_t n, uint32_t *d_bits, double *d_pm, uint32_t *d_flags, uint32_t *d_list, int L);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

@@ -176,7 +176,8 @@ static void usage(void)
 {
     fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
                     "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
-                    "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n");
+                    "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
+                    "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n");
     exit(2);
 }
 
@@ -184,6 +185,7 @@ int main(int argc, char **argv)
 {
     int N = 1024, K = 512, L = 8, algo = POLAR_ALGO_CASCL, ble = 100, batch = 4096, dtype = POLAR_F64, bp_iters = 100;
     int fast = 0, sys = 0, bpr = 0, gpus = 1, bp_stop = POLAR_BP_STOP_NONE;
+    int stages[6], nstages = 0;   /* --stages: polar_cascl_set_stages */
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
     double lo = 1.0, hi = 3.0, step = 0.5;
@@ -217,6 +219,17 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--bp-stop") && v) {   /* polar_bp_set_stop */
             if (strcmp(v, "g")) usage();
             bp_stop = POLAR_BP_STOP_G;
+            i++;
+        }
+        else if (!strcmp(a, "--stages") && v) {
+            const char *q = v;
+            while (*q) {
+                char *end;
+                if (nstages == 6) usage();
+                stages[nstages++] = (int)strtol(q, &end, 10);
+                if (end == q) usage();
+                q = (*end == ',') ? end + 1 : end;
+            }
             i++;
         }
         else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : POLAR_F64; i++; }
@@ -306,6 +319,11 @@ int main(int argc, char **argv)
         /* the read-outs need fixed iterations; a polar_group builds its contexts from cfg and has no stop rule */
         if (bpr || (fast && gpus > 1)) { fprintf(stderr, "--bp-stop: not with --algo bpr or --gpus > 1\n"); return 1; }
         if ((rc = polar_bp_set_stop(ctx, bp_stop)) != 0) { fprintf(stderr, "--bp-stop: %s\n", polar_strerror(rc)); return 1; }
+    }
+    if (nstages > 0) {
+        /* a polar_group builds its contexts from cfg and runs the fixed decoder */
+        if (fast && gpus > 1) { fprintf(stderr, "--stages: not with --gpus > 1\n"); return 1; }
+        if ((rc = polar_cascl_set_stages(ctx, stages, nstages)) != 0) { fprintf(stderr, "--stages: %s\n", polar_strerror(rc)); return 1; }
     }
     /* the library built the frozen set from the 5G sequence like the reference (I[i] = Q[N-(K+r)+i]);
        the encoder needs the same I[] */
