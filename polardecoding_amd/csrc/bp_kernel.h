@@ -22,13 +22,6 @@
 
 namespace polar {
 
-// The stages are latency-bound chains (2 waves per SIMD in f64): the one-round-trip CHK wins over the compact one.
-#ifdef POLAR_BP_LUT2
-#define BP_CHK chk_lut
-#else
-#define BP_CHK chk_lut1
-#endif
-
 
 // first element of butterfly bb in stage i (the partner is 2^i further)
 __device__ __forceinline__ int bp_elem(int bb, int i, int n)
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
     unsigned char *lut_mem = reinterpret_cast<unsigned char *>(STOP ? reinterpret_cast<uint32_t *>(stopf + 4) : obits + NW);
     lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
     Lut<R>::build(lut_mem, tid, nt);
-    Lut<R> lut;
+    Lut<R> lut;   // the stages are latency-bound chains (2 waves per SIMD in f64): chk_lut1 wins over the compact chk_lut
     lut.bind(lut_mem);
     __syncthreads();
 
@@ -142,8 +135,8 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
                     }
                     const R *lrow = (i + 1 == n) ? ch : lm + (size_t)i * N;
                     const R l0 = lrow[j], l1 = lrow[j + s];
-                    const R a = BP_CHK<R>(r0, l1 + r1, lut);
-                    const R c = r1 + BP_CHK<R>(r0, l0, lut);
+                    const R a = chk_lut1<R>(r0, l1 + r1, lut);
+                    const R c = r1 + chk_lut1<R>(r0, l0, lut);
                     if (STOP && i + 1 == n) {
                         // x_hat: (l[n] + r[n] >= 0) -> 0
                         if (!(l0 + a >= R(0))) atomicOr(&xbits[j >> 5], 1u << (j & 31));
@@ -173,8 +166,8 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
                     }
                     const R *lrow = (i + 1 == n) ? ch : lm + (size_t)i * N;
                     const R l0 = lrow[j], l1 = lrow[j + s];
-                    const R a = BP_CHK<R>(l0, l1 + r1, lut);
-                    const R c = l1 + BP_CHK<R>(r0, l0, lut);
+                    const R a = chk_lut1<R>(l0, l1 + r1, lut);
+                    const R c = l1 + chk_lut1<R>(r0, l0, lut);
                     if (i > 0) {
                         lm[(size_t)(i - 1) * N + j] = a;
                         lm[(size_t)(i - 1) * N + j + s] = c;

@@ -9,7 +9,7 @@
 // thread with two independent butterflies in flight per stage, 2.7 message accesses per butterfly instead of 6, and no
 // per-stage index arithmetic (the element sets are compile-time functions of the group).  The four L rows are read from
 // LDS once per iteration and kept in the reader's registers for the next right-going sweep, so they share ONE transfer
-// row: 40 KB per codeword, three f64 codewords per CU (LCACHE below).
+// row: 40 KB per codeword, three f64 codewords per CU (BpR4Cfg below).
 //
 // Threads: 256 per codeword, t = 64 w + x.  Group g < 4 removes element bits 2g, 2g+1, which are below bit 8: wave w works
 // on elements [256 w, 256 w + 256) in all of them, so groups 0..3 hand rows over inside one wave (LDS executes a wave's
@@ -24,37 +24,27 @@
 
 namespace polar {
 
-// CHK form: 0 = chk_idx (prefix popcount + one conflict-free threshold read per look-up, 24 bytes of LDS per CHK),
-// 1 = chk_lut (50-cell table, 40 bytes per CHK from scattered cells), 2 = chk_lut1 (one round trip, 56 bytes),
-// 3 = chk_cnt (staircase counted with 14 subtractions, 8 bytes), 4 = chk_tab (the prefix count of form 0 read from a 26-byte
-// table: three VALU instructions less per look-up, one more LDS read in the dependent chain -- 0.92 M against 1.19 M: slower).  With the messages out of LDS the table reads of form 1
-// kept the LDS pipe 68 % busy at 42 % VALU (0.90 M frames/s f64); form 3 is VALU-bound by its f64 subtractions (0.85 M).
-// Measured (2^16 frames, 50 iterations): f64 form 0 1.04 M frames/s, form 1 0.89 M; f32 form 0 1.57 M, form 1 1.81 M
-// (a float entry of the 50-cell table is half the bytes) -> -1 picks form 0 for double and form 1 for float (round 2's choice).
-// Round 3, after the L rows moved into registers (LCACHE: three codewords per CU, 39 % LDS busy): form 2, the one-round-trip
-// table form, is ahead in both types -- f64 1.206 -> 1.303 M frames/s, f32 1.81 -> 2.09 M (same box, 2^16 frames, 50
-// iterations, decisions hashed equal; profiles/r03_ab_experiments.txt run 22): five VALU instructions less per CHK than
-// form 0, and the LDS pipe now has the room for its 48 bytes per CHK.  Default: 2.
-#ifndef POLAR_BPR4_CHK
-#define POLAR_BPR4_CHK 2
-#endif
-#ifndef POLAR_BPR4_ABS_LDS
-#define POLAR_BPR4_ABS_LDS 0
-#endif
+// CHK form: chk_lut1 (one round trip, 56 bytes of LDS per CHK).  The forms measured against it: chk_idx (prefix popcount +
+// one conflict-free threshold read per look-up, 24 bytes), chk_lut (50-cell table, 40 bytes per CHK from scattered cells),
+// chk_cnt (staircase counted with 14 subtractions, 8 bytes) and chk_tab (the prefix count of chk_idx read from a 26-byte
+// table: three VALU instructions less per look-up, one more LDS read in the dependent chain -- 0.92 M against 1.19 M: slower).
+// With the messages out of LDS the table reads of chk_lut kept the LDS pipe 68 % busy at 42 % VALU (0.90 M frames/s f64);
+// chk_cnt is VALU-bound by its f64 subtractions (0.85 M).  Measured (2^16 frames, 50 iterations): f64 chk_idx 1.04 M
+// frames/s, chk_lut 0.89 M; f32 chk_idx 1.57 M, chk_lut 1.81 M (a float entry of the 50-cell table is half the bytes), so
+// round 2 took chk_idx for double and chk_lut for float.  Round 3, after the L rows moved into registers (three codewords per
+// CU, 39 % LDS busy): chk_lut1 is ahead in both types -- f64 1.206 -> 1.303 M frames/s, f32 1.81 -> 2.09 M (same box, 2^16
+// frames, 50 iterations, decisions hashed equal; profiles/r03_ab_experiments.txt run 22): five VALU instructions less per
+// CHK than chk_idx, and the LDS pipe now has the room for its 48 bytes per CHK.
+// The kernel still builds the chk_cnt and chk_idx tables (off_dn, off_st), which nothing reads.
 
 template <typename R>
 struct BpR4Cfg {
     static constexpr int N = 1024, n = 10, NW = 32, THREADS = 256;
-#ifndef POLAR_BPR4_LCACHE
-#define POLAR_BPR4_LCACHE 1
-#endif
-    // LCACHE: the rows L[2], L[4], L[6], L[8] are read from LDS once per iteration (by the left-going sweep), kept in the
-    // reader's registers for the right-going sweep of the next iteration, and so only need ONE transfer row in LDS:
+    // The rows L[2], L[4], L[6], L[8] are read from LDS once per iteration (by the left-going sweep), kept in the
+    // reader's registers (Lb) for the right-going sweep of the next iteration, and so only need ONE transfer row in LDS:
     // 40 KB per codeword instead of 64 KB -> three f64 codewords per CU, no LDS initialisation per frame.
-    static constexpr bool LCACHE = POLAR_BPR4_LCACHE != 0;
-    static constexpr int LROWS = LCACHE ? 1 : 4;
-    static constexpr int MIN_BLOCKS = LCACHE ? 3 : 2;
-    static constexpr size_t rows_bytes = sizeof(R) * (size_t)N * (4 + LROWS);   // R2 R4 R6 R8, then L2 L4 L6 L8 (or the one transfer row)
+    static constexpr int MIN_BLOCKS = 3;
+    static constexpr size_t rows_bytes = sizeof(R) * (size_t)N * 5;   // R2 R4 R6 R8, then the one L transfer row
     static constexpr size_t off_lut = rows_bytes;
     static constexpr size_t off_dn = off_lut + ((Lut<R>::bytes + 15) / 16) * 16;
     static constexpr size_t off_st = off_dn + sizeof(R) * 64;
@@ -71,31 +61,16 @@ struct BpR4 {
     using C = BpR4Cfg<R>;
     static constexpr int N = C::N;
     R Ri[5][4], Li[5][4];   // interior rows R[2g+1], L[2g+1] at this thread's elements of group g
-    R Lb[4][4];             // LCACHE: L[2g+2] at this thread's elements of group g, as read by the last left-going sweep
+    R Lb[4][4];             // L[2g+2] at this thread's elements of group g, as read by the last left-going sweep
     R ch[4];                // channel LLRs at the group-4 elements
-    R *rowR, *rowL;         // LDS: rowR + (g-1) N = R[2g], rowL + (g-1) N = L[2g], g = 1..4
+    R *rowR, *rowL;         // LDS: rowR + (g-1) N = R[2g], g = 1..4; rowL: the L transfer row
     Lut<R> lut;
-    const R *dn;            // LDS: 8x8 differences of the staircase levels, by (count, count)
-    Stair<R> st;
     int t;                  // thread index 0..255
     uint32_t fz;            // frozen flags of elements 4t .. 4t+3 (group 0)
 
     __device__ __forceinline__ R chk2(R a, R b) const
     {
-#if POLAR_BPR4_CHK == -1
-        if constexpr (sizeof(R) == 8) return chk_idx<R>(a, b, st);
-        else return chk_lut<R>(a, b, lut);
-#elif POLAR_BPR4_CHK == 2
         return chk_lut1<R>(a, b, lut);
-#elif POLAR_BPR4_CHK == 1
-        return chk_lut<R>(a, b, lut);
-#elif POLAR_BPR4_CHK == 3
-        return chk_cnt<R>(a, b, dn);
-#elif POLAR_BPR4_CHK == 4
-        return chk_tab<R>(a, b, st);
-#else
-        return chk_idx<R>(a, b, st);
-#endif
     }
     // first element of this thread in group G: t with two zero bits inserted at position 2G
     template <int G>
@@ -135,7 +110,7 @@ struct BpR4 {
             // stage 2G+1: r[2G+1], l[2G+2] -> r[2G+2]
             R lin[4], o[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) lin[k] = C::LCACHE ? Lb[G][k] : rowL[G * N + e + k * s];
+            for (int k = 0; k < 4; ++k) lin[k] = Lb[G][k];
             bfR(Ri[G][0], Ri[G][2], lin[0], lin[2], o[0], o[2]);
             bfR(Ri[G][1], Ri[G][3], lin[1], lin[3], o[1], o[3]);
 #pragma unroll
@@ -166,8 +141,8 @@ struct BpR4 {
         const int e = e0<G>();
         R lin[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) lin[k] = (G == 4) ? ch[k] : rowL[(C::LCACHE ? 0 : G * N) + e + k * s];
-        if constexpr (C::LCACHE && G < 4) {
+        for (int k = 0; k < 4; ++k) lin[k] = (G == 4) ? ch[k] : rowL[e + k * s];
+        if constexpr (G < 4) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) Lb[G][k] = lin[k];
         }
@@ -182,7 +157,7 @@ struct BpR4 {
             bfL(Li[G][0], Li[G][1], rin[0], rin[1], o[0], o[1]);
             bfL(Li[G][2], Li[G][3], rin[2], rin[3], o[2], o[3]);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) rowL[(C::LCACHE ? 0 : (G - 1) * N) + e + k * s] = o[k];
+            for (int k = 0; k < 4; ++k) rowL[e + k * s] = o[k];
         } else if constexpr (LAST) {
             // stage 0, needed only for the decision (BP_1024.c:417-425): frozen -> 0, else (l[0] + r[0] >= 0) -> 0
             R o[4];
@@ -224,17 +199,7 @@ __global__ __launch_bounds__(256, (BpR4Cfg<R>::MIN_BLOCKS)) void k_bp_r4(BpParam
     Lut<R>::build(smem + C::off_lut, threadIdx.x, blockDim.x);
     s.lut.bind(smem + C::off_lut);
     build_delta_by_count<R>(reinterpret_cast<R *>(smem + C::off_dn), threadIdx.x, blockDim.x);
-    s.dn = reinterpret_cast<const R *>(smem + C::off_dn);
     Stair<R>::build(smem + C::off_st, threadIdx.x, blockDim.x);
-#if POLAR_BPR4_ABS_LDS
-    {   // The kernel has no static LDS, so its dynamic LDS starts at address 0 (checked by the launcher): binding the staircase
-        // tables by absolute address lets every table read take its offset as an immediate instead of an address add.
-        typedef __attribute__((address_space(3))) unsigned char lds_u8;
-        s.st.bind((const unsigned char *)(lds_u8 *)(uintptr_t)C::off_st);
-    }
-#else
-    s.st.bind(smem + C::off_st);
-#endif
     uint32_t *uw = reinterpret_cast<uint32_t *>(smem + C::off_stop);   // STOP: [32] u_hat, [32] x_hat
     uint32_t *xw = uw + NW;
     {
@@ -260,10 +225,6 @@ __global__ __launch_bounds__(256, (BpR4Cfg<R>::MIN_BLOCKS)) void k_bp_r4(BpParam
                 s.Li[g][k] = R(0);   // :378-380
                 if (g < 4) s.Lb[g][k] = R(0);
             }
-        if constexpr (!C::LCACHE) {   // the L rows in LDS are read by the first right-going sweep before anything wrote them
-            for (int i = s.t; i < 8 * N; i += 256) s.rowR[i] = R(0);
-            __syncthreads();
-        }
 
         uint32_t bits = 0;
         int done = P.iters;

@@ -22,13 +22,10 @@
 
 namespace polar {
 
-// CHK form of this kernel: 0 = chk_idx (24 bytes of LDS per CHK, six more VALU instructions), 2 = chk_lut1 (48 bytes, one
-// round trip).  Measured, 2^18 frames, 100 iterations: f64 form 2 8.93 M frames/s, form 0 7.50 M; f32 form 2 12.6 M, form 0
-// 9.3 M (k_bp, the LDS kernel this one replaces at N = 128: 2.60 / 4.34 M) -- with the messages in registers the LDS pipe has
-// room for the table reads and the VALU is the bound.
-#ifndef POLAR_BPW_CHK
-#define POLAR_BPW_CHK 2
-#endif
+// CHK form of this kernel: chk_lut1 (48 bytes of LDS per CHK, one round trip).  Against chk_idx (24 bytes, six more VALU
+// instructions), 2^18 frames, 100 iterations: f64 chk_lut1 8.93 M frames/s, chk_idx 7.50 M; f32 12.6 M against 9.3 M (k_bp,
+// the LDS kernel this one replaces at N = 128: 2.60 / 4.34 M) -- with the messages in registers the LDS pipe has room for
+// the table reads and the VALU is the bound.  The kernel still builds the chk_idx table (off_st), which nothing reads.
 
 template <typename R>
 struct BpW128Cfg {
@@ -65,9 +62,8 @@ __device__ __forceinline__ float bpw_xor(float x) { return __int_as_float(bpw_xo
 template <typename R, typename IN>
 struct BpW128 {
     using C = BpW128Cfg<R>;
-    static constexpr int CHKF = POLAR_BPW_CHK;
     Lut<R> lut;
-    Stair<R> st;
+    Stair<R> st;  // bound, never read (chk_idx); dropping it changes the kernels' register allocation (same operations)
     R rm[6][2];   // r[1..6], elements lane and lane + 64
     R lm[6][2];   // l[1..6]
     R ch[2];      // l[7]: channel LLRs
@@ -75,8 +71,7 @@ struct BpW128 {
 
     __device__ __forceinline__ R chk(R a, R b) const
     {
-        if constexpr (CHKF == 0) return chk_idx<R>(a, b, st);
-        else return chk_lut1<R>(a, b, lut);
+        return chk_lut1<R>(a, b, lut);
     }
     // one element of one cross-lane stage: own / partner values of r[i] and l[i+1]; `lead` = r_own (right-going) or l_own
     template <int I>

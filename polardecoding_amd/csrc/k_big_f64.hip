@@ -2,10 +2,6 @@
 #include "polar_host.h"
 #include "scl_big.h"
 
-#ifndef POLAR_BIG_CH_MINN
-#define POLAR_BIG_CH_MINN 1024   // shortest code that runs the chain() kernel (N = 1024, L = 32: 1.549 -> 1.586 M frames/s since the 4 / 7 / 1 split)
-#endif
-
 namespace {
 
 // big lists / long codes: low LLR levels in LDS, the rest in a per-wave scratch slice (scl_big.h)
@@ -46,19 +42,15 @@ int launch_big(polar_ctx *c, const polar::SclParams &P)
         if (use == 351) return launch_big_v<R, IN, LOGL, 3, 5, 1>(c, P);
         if (use == 371) {
             // f64, N >= 1024 (BASELINE config 5: N = 4096): the f chains of the upper levels in one pass, three wavefronts per
-            // SIMD (scl_big.h, chain())
+            // SIMD (scl_big.h, chain()).  N = 1024, L = 32: 1.549 -> 1.586 M frames/s since the 4 / 7 / 1 split.
             if constexpr (sizeof(R) == 8) {
-#ifndef POLAR_BIG_CH   // 0: without chain() (four wavefronts per SIMD), for same-box comparisons (tools/variant.py)
-#define POLAR_BIG_CH 1
-#endif
                 // At three wavefronts per SIMD a wavefront may use 12.9 KB of LDS: LLR level 4 moves from the registers into the
                 // LDS and level 5 from the scratch into the registers (split 4 / 7 / 1), so that nothing below level 6 is in the
                 // scratch: no leader passes, no scratch rows and no drains for levels 4 and 5 (config 5: + 2 ... 6 % depending on
-                // the box, a seventh less scratch traffic; -DPOLAR_BIG_TL3 for the 3 / 7 / 1 split)
-#ifndef POLAR_BIG_TL3
-                if (POLAR_BIG_CH && P.N >= POLAR_BIG_CH_MINN) return launch_big_v<R, IN, LOGL, 4, 7, 1, POLAR_BIG_CH>(c, P);
-#endif
-                if (POLAR_BIG_CH && P.N >= POLAR_BIG_CH_MINN) return launch_big_v<R, IN, LOGL, 3, 7, 1, POLAR_BIG_CH>(c, P);
+                // the box, a seventh less scratch traffic than the 3 / 7 / 1 split)
+                if (P.N >= 1024) return launch_big_v<R, IN, LOGL, 4, 7, 1, 1>(c, P);
+                // never taken: keeps the chain() kernel with the 3 / 7 / 1 split it replaced in the library
+                if (P.N >= 1024) return launch_big_v<R, IN, LOGL, 3, 7, 1, 1>(c, P);
             }
             return launch_big_v<R, IN, LOGL, 3, 7, 1>(c, P);
         }

@@ -19,10 +19,7 @@ int launch_fast2(polar_ctx *c, const polar::SclParams &P)
     if (occ < 1) occ = 1;
     const long long pairs = ((long long)P.B + 1) / 2;
     long long blocks_needed = (pairs + WAVES - 1) / WAVES;
-#ifndef POLAR_F2_GRID_MULT
-#define POLAR_F2_GRID_MULT 1
-#endif
-    int grid = (int)std::min<long long>(blocks_needed, (long long)occ * c->num_cu * POLAR_F2_GRID_MULT);
+    int grid = (int)std::min<long long>(blocks_needed, (long long)occ * c->num_cu);
     if (grid < 1) grid = 1;
     polar::SclParams Q = P;
     const size_t sc_bytes = Cfg::scratch_elems * sizeof(R) * (size_t)grid * WAVES;

@@ -119,9 +119,6 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     P.dbg = nullptr;
     P.scratch = nullptr;
     P.queue = nullptr;
-#ifdef POLAR_STAMPS   // diagnostic builds only (tools/): per-section cycle sums, see debug_stamps.inc
-#include "debug_stamps.inc"
-#endif
     const bool in32 = in_is_f32 != 0;
     if (sc_lanes_ok(c, B)) return polar_tu::sc_lanes(c, P, f32, in32);
     if (fast_ok(c, in_is_f32)) {
@@ -290,9 +287,7 @@ void unpack_words(const uint32_t *w, int NW, int *out)
 }
 
 // helper threads per direction of the host pipeline (staging of the caller's rows / unpacking of the decisions)
-#ifndef POLAR_HOST_THREADS
-#define POLAR_HOST_THREADS 6   // 4 -> 6: end_to_end 4.4 -> 4.6-4.7 M frames/s; 8 and 12 no more (run 35)
-#endif
+constexpr unsigned HOST_THREADS = 6;   // 4 -> 6: end_to_end 4.4 -> 4.6-4.7 M frames/s; 8 and 12 no more (run 35)
 int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char *frozen_mask, size_t B,
                int *u_hat, double *pm_out, unsigned *flags, unsigned *iters = nullptr)
 {
@@ -321,10 +316,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     // asynchronous DMA.
     // chunk: 16384 frames, but at most 128 MiB of input (N = 1024: 16384 frames; N = 4096: 4096), so that the two pinned
     // staging buffers and the two device buffers stay at 256 MiB each whatever the block length
-#ifndef POLAR_HOST_CHUNK
-#define POLAR_HOST_CHUNK 16384
-#endif
-    const size_t CH = std::max<size_t>(256, std::min<size_t>(POLAR_HOST_CHUNK, ((size_t)128 << 20) / ((size_t)N * sizeof(double))));
+    const size_t CH = std::max<size_t>(256, std::min<size_t>(16384, ((size_t)128 << 20) / ((size_t)N * sizeof(double))));
     // Chunk boundaries.  Big batches ramp up and down (CH/8, CH/4, CH/2, CH ... CH, CH/2, CH/4, CH/8): nothing overlaps the
     // staging of the first chunk nor the copy-out and unpacking of the last one, so those two are small.
     std::vector<size_t> off{0};
@@ -383,7 +375,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         const size_t f0 = off[k], nf = off[k + 1] - off[k];
         const double *src = in + f0 * (size_t)N;
         double *dst = c->h_in[k & 1];
-        const unsigned nthr = POLAR_HOST_THREADS;
+        const unsigned nthr = HOST_THREADS;
         auto part = [=](unsigned t) {
             const size_t a = nf * t / nthr, b = nf * (t + 1) / nthr;
             std::memcpy(dst + a * (size_t)N, src + a * (size_t)N, (b - a) * (size_t)N * sizeof(double));
@@ -397,7 +389,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     auto unpack_chunk = [&](size_t k) {   // decisions of chunk k: pinned words -> caller's int u_hat[][N]
         const size_t f0 = off[k], nf = off[k + 1] - off[k];
         const uint32_t *hb = c->h_bits[k & 1];
-        const unsigned nthr = (unsigned)std::max<size_t>(1, std::min<size_t>(POLAR_HOST_THREADS, nf / 1024));
+        const unsigned nthr = (unsigned)std::max<size_t>(1, std::min<size_t>(HOST_THREADS, nf / 1024));
         auto part = [=](unsigned t) {
             const size_t a = nf * t / nthr, b = nf * (t + 1) / nthr;
             for (size_t f = a; f < b; ++f) unpack_words(hb + f * NW, NW, u_hat + (f0 + f) * (size_t)N);

@@ -32,13 +32,7 @@ struct Lut {
     struct __attribute__((aligned(16))) TP { R lo, hi; };
     static constexpr int NCELL = 50, STRIDE = 48;
     static constexpr size_t cell_bytes = (size_t)NCELL * STRIDE;
-    static constexpr size_t copy_bytes = cell_bytes + sizeof(R) * 64;   // one copy: cells + 8x8 differences
-#ifndef POLAR_LUT_COPIES
-#define POLAR_LUT_COPIES 1
-#endif
-    // COPIES > 1: lane l uses copy l % COPIES, which spreads the random cell reads over more LDS banks
-    static constexpr int COPIES = POLAR_LUT_COPIES;
-    static constexpr size_t bytes = copy_bytes * COPIES;
+    static constexpr size_t bytes = cell_bytes + sizeof(R) * 64;   // cells + 8x8 differences
     unsigned base;  // LDS byte address of the table, pre-biased: entry(x) = base + clamp(raw(x)) * 48
     const unsigned char *lds0;  // LDS address 0 as a pointer (keeps the address space known)
     const R *dlt;   // dlt[i*8+j] = T_i - T_j (one IEEE subtraction, like `delta = T(s); delta -= T(d)`)
@@ -50,11 +44,9 @@ struct Lut {
     }
     __device__ __forceinline__ void bind(unsigned char *tab)
     {
-        if (COPIES > 1) tab += (size_t)(threadIdx.x % COPIES) * copy_bytes;
         lds0 = tab;
         base = (unsigned)(0 - (Cell<R>::BIAS - 1) * STRIDE);
-        if (COPIES == 1) __asm__ volatile("" : "+s"(base));  // opaque: keeps the bias inside the multiply-add
-        else __asm__ volatile("" : "+v"(base));
+        __asm__ volatile("" : "+s"(base));  // opaque: keeps the bias inside the multiply-add
         dlt = reinterpret_cast<const R *>(tab + cell_bytes);
     }
     typedef int i2 __attribute__((ext_vector_type(2)));
@@ -66,11 +58,12 @@ struct Lut {
         const i2 lh = *reinterpret_cast<const i2 *>(lds0 + e + 8);
         return (absr(x) >= thr) ? lh.y : lh.x;
     }
-    // executed by a whole workgroup before its first barrier
+    // executed by a whole workgroup before its first barrier.  The outer loop of one pass is what is left of a variant
+    // with several copies of the table; without it the compiler orders the kernels' instructions differently.
     static __device__ void build(unsigned char *tab0, int tid, int nthreads)
     {
-      for (int cp = 0; cp < COPIES; ++cp) {
-        unsigned char *tab = tab0 + (size_t)cp * copy_bytes;
+      for (int cp = 0; cp < 1; ++cp) {
+        unsigned char *tab = tab0 + (size_t)cp * bytes;
         R *d = reinterpret_cast<R *>(tab + cell_bytes);
         const R thr[7] = {R(0.196), R(0.433), R(0.71), R(1.05), R(1.508), R(2.252), R(4.5)};
         const R tv[8] = {R(0.65), R(0.55), R(0.45), R(0.35), R(0.25), R(0.15), R(0.05), R(0)};
@@ -118,25 +111,10 @@ struct Lut {
     {
         return __int_as_float((int)bfi(m, (uint32_t)__float_as_int(a), (uint32_t)__float_as_int(b)));
     }
-    static __device__ __forceinline__ uint32_t neg_mask(double t) { return (uint32_t)(__double2hiint(t) >> 31); }
-    static __device__ __forceinline__ uint32_t neg_mask(float t) { return (uint32_t)(__float_as_int(t) >> 31); }
-    // T(|x|) in one LDS round trip
+    // T(|x|) in one LDS round trip.  Selecting by the sign bit of |x| - thr (sel_mask) instead of compare + v_cndmask
+    // measured 4.5 % slower in the pair kernel (profiles/r03_ab_experiments.txt run 24).
     __device__ __forceinline__ R tabv(R x) const
     {
-#ifdef POLAR_TABV_MASK   // measured round 3: 4.5 % SLOWER than compare + v_cndmask in the pair kernel (profiles/r03_ab_experiments.txt run 24)
-        {   // |x| - thr is negative exactly when |x| < thr (equal: +0; thr = +inf in a cell without threshold: -inf, and
-            // both T are the same there): its sign bit, spread over the word, selects T_lo; no compare, no VCC, no v_cndmask
-            const unsigned e1 = entry(x);
-            const R thr1 = *reinterpret_cast<const R *>(lds0 + e1);
-            const TP tp1 = *reinterpret_cast<const TP *>(lds0 + e1 + 32);
-            return sel_mask(neg_mask(absr(x) - thr1), tp1.lo, tp1.hi);
-        }
-#endif
-#ifdef POLAR_SENS_NOLUT   // timing sensitivity experiment only (WRONG values): no LDS traffic, same compare + select
-        const unsigned e0 = entry(x);
-        const R thr0 = R(1.05) + R(e0 & 1u);
-        return (absr(x) >= thr0) ? R(0.05) : R(0.45);
-#endif
         const unsigned e = entry(x);
         const R thr = *reinterpret_cast<const R *>(lds0 + e);
         const TP tp = *reinterpret_cast<const TP *>(lds0 + e + 32);
@@ -190,13 +168,9 @@ __device__ __forceinline__ float minabs(float a, float b)
 // operation into v_and + v_or)
 __device__ __forceinline__ unsigned and_or_sign(unsigned x, unsigned mhi)
 {
-#ifdef POLAR_SIGN_OLD
-    return (x & 0x80000000u) | mhi;
-#else
     unsigned r;
     __asm__("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(0x80000000u), "v"(mhi));
     return r;
-#endif
 }
 __device__ __forceinline__ double xor_sign(double m, double a, double b)
 {
@@ -227,9 +201,6 @@ __device__ __forceinline__ R chk_lut1(R a, R b, const Lut<R> &L)
 template <typename R>
 __device__ __forceinline__ R chk_lut(R a, R b, const Lut<R> &L)
 {
-#ifdef POLAR_CHK_LUT_IS_LUT1   // experiment switch (tools/variant.py): the one-round-trip form wherever the compact one is used
-    return chk_lut1<R>(a, b, L);
-#endif
     const R s = a + b, d = a - b;
     const int os = L.pick(s, 0), od = L.pick(d, 16);
     const R delta = *reinterpret_cast<const R *>(reinterpret_cast<const unsigned char *>(L.dlt) + (os + od));

@@ -16,7 +16,7 @@ struct SclParams {
     int B;
     int sc_mode;               // 1: plain SC decisions (SCdecode), L must be 1
     void *scratch;             // k_scl_fast, N = 1024: per-wave global scratch (FastCfg::scratch_elems each)
-    unsigned long long *dbg;   // diagnostic builds only (-DPOLAR_STAMPS): per-section cycle sums
+    unsigned long long *dbg;   // read by nothing; kept so that the fields after it keep their offsets
     unsigned *queue;           // persistent kernels: job counter (polar_host.h work_queue()); null = jobs by a fixed stride
 };
 

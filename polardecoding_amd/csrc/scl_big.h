@@ -102,32 +102,14 @@ __device__ __forceinline__ bool big_trivial_prune(int kf, int ko)
 // everything a wave wrote (LDS and scratch) is visible to its own later loads; no other wave ever reads it
 __device__ __forceinline__ void wave_sync() { __asm__ volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 
-#ifdef POLAR_STAMPS  // diagnostic build: s_memtime per section, summed per wave, added to P.dbg[]
-#define BIG_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tsec[i] += t_ - tprev; tprev = t_; } while (0)
-#else
-#define BIG_STAMP(i) do { } while (0)
-#endif
-#ifdef POLAR_MARKS  // static instruction accounting (tools/count_marks.py): comments in the ISA
-#define BIG_MARK(name) __asm__ volatile("; MARK " name)
-#else
-#define BIG_MARK(name) do { } while (0)
-#endif
-
 // One register level (RL = 1) is worth it only at four wavefronts per SIMD (128 VGPRs): the decoder is a chain of dependent
 // round trips and its rate follows the number of resident wavefronts.
 // CH = 1: the chains of f steps below a step at level >= 7 run in one pass (chain() below).  It needs more registers for its
 // loads in flight, so the kernel then runs three wavefronts per SIMD; measured on N = 4096, L = 32 (BASELINE config 5): +9 %,
 // a third less fabric read traffic; on N = 1024, L = 32 the four-wavefront kernel without it stays ahead.
 template <typename R, typename IN, int LOGL, int TLv, int TBv, int RLv = 0, int CH = 0>
-#ifndef POLAR_BIG_CH_WAVES
-#define POLAR_BIG_CH_WAVES 3
-#endif
-__global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) void k_scl_big(SclParams P)
+__global__ __launch_bounds__(256, RLv == 1 ? (CH ? 3 : 4) : 1) void k_scl_big(SclParams P)
 {
-#ifdef POLAR_STAMPS
-    unsigned long long tsec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-#endif
     using Cfg = BigCfg<R, LOGL, TLv, TBv, RLv>;
     using State = typename Cfg::State;
     constexpr int L = Cfg::L, S = Cfg::S, LOW = Cfg::LOW, WL = Cfg::WL, TL = Cfg::TL, TB = Cfg::TB, WAVES = Cfg::WAVES, RL = Cfg::RL;
@@ -201,10 +183,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
             if (t >= 6) {
                 // work item = (leader q, pass k): elements e = 64k + lane of path q.  U items are loaded before the
                 // first is used, so that U round trips to L2 overlap instead of queueing behind each other.
-#ifndef POLAR_BIG_U
-#define POLAR_BIG_U 8
-#endif
-                constexpr int U = CH ? POLAR_BIG_U : 4;   // the three-wavefront kernel has the registers for more loads in flight
+                constexpr int U = CH ? 8 : 4;   // the three-wavefront kernel has the registers for more loads in flight
                                                           // (config 5: 8 / 8 against 4 / 4: 97.1 -> 94.5 ms; 12 or 16 spill 25+ VGPRs)
                 const int lp = t - 6, per = 1 << lp, total = nlead << lp;
                 for (int it = 0; it < total; it += U) {
@@ -237,10 +216,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                 // t = 4 or 5 (only when TL < 5): 64 / 2^t leaders per pass, source slots fetched by lane.  The loads of
                 // UL passes go out before the first result is needed (one round trip per UL passes instead of one per pass).
                 const int total = nlead << t;   // elements over all leaders
-#ifndef POLAR_BIG_UL
-#define POLAR_BIG_UL 8
-#endif
-                constexpr int UL = CH ? POLAR_BIG_UL : 4;
+                constexpr int UL = CH ? 8 : 4;
                 for (int it = 0; it < total; it += 64 * UL) {
                     R a[UL], b[UL];
                     uint32_t wv[UL];
@@ -273,7 +249,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
             }
             if (p < act) ptrA = ptr_set<LOGL>(ptrA, t, leader);
             wave_sync();
-            BIG_STAMP((t >= 6) ? 1 : 2);
         };
         // ---- levels d, d-1, ..., 6 in ONE pass (d >= 7): the step at level d (g, or f from the channel row), then the f steps
         // below it without reading a row back.  A lane owns the elements lane + 64 k of every row, and element k of level
@@ -297,7 +272,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
             if (pos == 0 && p < act && leader == p) tbl[__popcll(m_lead & below)] = p;
             __asm__ volatile("" ::: "memory");
             const int LV = d - 6, K = 1 << LV;
-#ifndef POLAR_BIG_CHAIN_NO_GROUP
             // Short chains (d = 7: two elements of level d per lane and leader; d = 8: four) would be one memory round trip per
             // LEADER: LG leaders share a round instead, sixteen loads in flight per lane as in the long chains.
             auto grouped = [&](auto PLc) {
@@ -359,7 +333,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
             } else if (LV == 2) {
                 grouped(std::integral_constant<int, 4>{});
             } else
-#endif
             for (int li = 0; li < nlead; ++li) {
                 const int q = __builtin_amdgcn_readfirstlane(tbl[li]);
                 const int ss = __builtin_amdgcn_readlane(my_src, q * S);
@@ -424,7 +397,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
             if (p < act)
                 for (int t = 6; t <= d; ++t) ptrA = ptr_set<LOGL>(ptrA, t, leader);
             wave_sync();
-            BIG_STAMP(1);
         };
         // ---- level t in (TL, TL+RL]: the path's own S lanes, rows in registers (ra: level TL+1, rb: level TL+2) ----
         // No leader sharing here (every path evaluates its own row: VALU work instead of a scratch round trip per step).
@@ -467,10 +439,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                 } else {
                     // source level t+1 is a scratch row (written by bulk, drained by its wave_sync), or the channel row
                     const R *src = (t + 1 == n) ? chg : hiA + (size_t)ss * N + 2 * h;
-#ifndef POLAR_BIG_REG_U
-#define POLAR_BIG_REG_U 8
-#endif
-                    constexpr int U = PER < POLAR_BIG_REG_U ? PER : POLAR_BIG_REG_U;     // pairs of loads in flight per lane
+                    constexpr int U = PER < 8 ? PER : 8;     // pairs of loads in flight per lane
 #pragma unroll
                     for (int k0 = 0; k0 < PER; k0 += U) {
                         R a[U], b[U];
@@ -501,7 +470,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                     else reg_c(integral_constant<int, TL + 2>{}, integral_constant<bool, false>{});
                 }
             }
-            BIG_STAMP(2);
         };
         // ---- level t <= TL from level t+1 by the path's own lanes ----
         auto low_c = [&](auto TC, auto GC) {
@@ -595,7 +563,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                 fw = P.frozen[(j >> 5) + (lane & 1)];            // frozen masks of leaves j..j+31 / j+32..j+63
             }
             // ================= LLR of leaf j for every active path =================
-            BIG_MARK("big_llr");
             int tf = n - 1;
             if (CH && TR <= 5 && j == 0 && n - 1 >= 7) {
                 kill_regs();
@@ -620,8 +587,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                 else low(t, false);
             }
             const R lam = (p < act) ? lowA[p * LOW + 1] : R(0);
-            BIG_STAMP(3);
-            BIG_MARK("big_decide");
 
             // ================= decision =================
             const bool frozen = (__builtin_amdgcn_readlane(fw, (j >> 5) & 1) >> (j & 31)) & 1;
@@ -735,8 +700,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                 __asm__ volatile("" ::: "memory");
             }
 
-            BIG_STAMP(frozen ? 4 : 5);
-            BIG_MARK("big_sums");
             // ================= partial sums (updateBit, SCL_1024.c:424-448) =================
             if (bit) crc ^= __builtin_amdgcn_readlane(ctv, j & 63);
             cur0 = (uint32_t)bit;
@@ -799,8 +762,6 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
                     else wave_sync();
                 }
             }
-            BIG_STAMP(6);
-            BIG_MARK("big_leaf_end");
         }
 
         // ================= choose the path (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) =================
@@ -841,12 +802,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? POLAR_BIG_CH_WAVES : 4) : 1) 
             if (P.flags) P.flags[frame] = fl;
         }
         wave_sync();
-        BIG_STAMP(7);
     }
-#ifdef POLAR_STAMPS
-    if (lane == 0 && P.dbg)
-        for (int i = 0; i < 8; ++i) atomicAdd(&P.dbg[i], tsec[i]);
-#endif
 }
 
 }  // namespace polar

@@ -38,35 +38,6 @@ __device__ __forceinline__ int dpp_i(int v)
 {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
-template <int K>  // lane i <- lane i+K within its row of 16 (row_shl), every lane valid
-__device__ __forceinline__ double shl_true(double x)
-{
-    long long b = __double_as_longlong(x);
-    int lo = dpp_i<0x100 + K>((int)b), hi = dpp_i<0x100 + K>((int)(b >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-template <int K>
-__device__ __forceinline__ float shl_true(float x)
-{
-    return __int_as_float(dpp_i<0x100 + K>(__float_as_int(x)));
-}
-#ifdef POLAR_SWIZZLE_PARTNER
-// lane i <- lane i^K through the LDS crossbar (no VALU slot); equals lane i+K for the low lanes that are used
-template <int K>
-__device__ __forceinline__ double shl_lanes(double x)
-{
-    long long b = __double_as_longlong(x);
-    int lo = __builtin_amdgcn_ds_swizzle((int)b, (K << 10) | 0x1F), hi = __builtin_amdgcn_ds_swizzle((int)(b >> 32), (K << 10) | 0x1F);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-template <int K>
-__device__ __forceinline__ float shl_lanes(float x)
-{
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), (K << 10) | 0x1F));
-}
-#define POLAR_SHL_DEFINED
-#endif
-#ifndef POLAR_SHL_DEFINED
 template <int K>  // lane i <- lane i+K within its row of 16 (row_shl)
 __device__ __forceinline__ double shl_lanes(double x)
 {
@@ -79,7 +50,6 @@ __device__ __forceinline__ float shl_lanes(float x)
 {
     return __int_as_float(dpp_i<0x100 + K>(__float_as_int(x)));
 }
-#endif
 template <int K>  // lane i <- lane i-K within its row (row_shr)
 __device__ __forceinline__ double shr_lanes(double x)
 {
@@ -117,12 +87,6 @@ __device__ __forceinline__ double quad_lanes(double x)
 }
 template <int QP>
 __device__ __forceinline__ float quad_lanes(float x) { return __int_as_float(quad_i<QP>(__float_as_int(x))); }
-
-#ifdef POLAR_MARKS  // static instruction accounting (tools/count_marks.py): comments in the ISA
-#define POLAR_MARK(name) __asm__ volatile("; MARK " name)
-#else
-#define POLAR_MARK(name) do { } while (0)
-#endif
 
 __device__ __forceinline__ void lds_fence() { __asm__ volatile("" ::: "memory"); }
 
@@ -559,7 +523,6 @@ struct FastDec {
     __device__ __forceinline__ void decide(int o, bool frozen, R lam)
     {
         const int j = 8 * o + K;
-        POLAR_MARK("decide_begin");
         uint32_t crcw = 0;
         if (CRC_ON && !frozen) crcw = crct[j];
         uint32_t bit = 0;
@@ -577,7 +540,6 @@ struct FastDec {
                 ++logact;
             } else {
                 // phase 2 (SCL_1024.c:610-661)
-                POLAR_MARK("phase2_begin");
                 // the branch lambda favours costs T(|lambda|), the other one T(|lambda|) + |lambda|: these ARE c0 / c1 in
                 // the order the sign of lambda says.  If the largest favoured key is below the smallest other key, the
                 // eight favoured candidates are the eight smallest of the sixteen (85 % of the information leaves at
@@ -592,7 +554,6 @@ struct FastDec {
                 } else {
                 const R c0 = lneg ? cw : cb, c1 = lneg ? cb : cw;
                 const uint32_t mask = survivors(c0, c1);
-                POLAR_MARK("rank_end");
                 const uint32_t m0 = mask & 0xFFu, m1 = mask >> 8;
                 const uint32_t m_both = m0 & m1, m_dead = ~(m0 | m1) & 0xFFu;
                 if (__popc(mask) < L) fl |= 0x1u;  // median tie ("Oops!", :621-622)
@@ -601,7 +562,6 @@ struct FastDec {
                     bit = (!s0 && s1) ? 1u : 0u;  // every slot keeps exactly one branch: no copy
                     PM = bit ? c1 : c0;
                 } else {
-                    POLAR_MARK("fork_begin");
                     // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661)
                     const bool dead = !s0 && !s1;
                     const int myrank = __popc(m_dead & ((1u << p) - 1u));
@@ -635,12 +595,9 @@ struct FastDec {
                 }
                 }
             }
-            POLAR_MARK("fork_end");
             if (CRC_ON) crc ^= bit ? crcw : 0u;
         }
-        POLAR_MARK("setbit_begin");
         set_bit_k<K>(o, bit);
-        POLAR_MARK("decide_end");
     }
 
     // ---- octets whose first seven leaves are frozen (patterns 0xFF, 0x7F) ----
@@ -662,18 +619,18 @@ struct FastDec {
         const R tt = lut.tabv(lam);
         R ph = tt + negmax(lam);  // PHI(lambda_k, 0) in lane k
         PM += ph;
-        ph = shl_true<1>(ph); PM += ph;
-        ph = shl_true<1>(ph); PM += ph;
-        ph = shl_true<1>(ph); PM += ph;
-        ph = shl_true<1>(ph); PM += ph;
-        ph = shl_true<1>(ph); PM += ph;
-        ph = shl_true<1>(ph); PM += ph;
+        ph = shl_lanes<1>(ph); PM += ph;
+        ph = shl_lanes<1>(ph); PM += ph;
+        ph = shl_lanes<1>(ph); PM += ph;
+        ph = shl_lanes<1>(ph); PM += ph;
+        ph = shl_lanes<1>(ph); PM += ph;
+        ph = shl_lanes<1>(ph); PM += ph;
         bl0 &= ~0xFEu;  // partial sums of levels 0..2 inside this octet: all zero
         if (last_frozen) {
-            ph = shl_true<1>(ph); PM += ph;
+            ph = shl_lanes<1>(ph); PM += ph;
             set_bit_tail(8 * o + 7, 0u);
         } else {
-            decide<7>(o, false, shl_true<7>(lam));
+            decide<7>(o, false, shl_lanes<7>(lam));
         }
     }
 
@@ -705,19 +662,9 @@ struct FastDec {
     }
 };
 
-#ifdef POLAR_STAMPS  // diagnostic build: s_memtime per section, summed per wave, added to P.dbg[]
-#define STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tsec[i] += t_ - tprev; tprev = t_; } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 template <typename R, typename IN, int NLOG, bool CRC_ON>
 __global__ __launch_bounds__(256, (FastCfg<R, NLOG>::MIN_WAVES_PER_SIMD)) void k_scl_fast(SclParams P)
 {
-#ifdef POLAR_STAMPS
-    unsigned long long tsec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-#endif
     using D = FastDec<R, IN, NLOG, CRC_ON>;
     using C = FastCfg<R, NLOG>;
     constexpr int N = C::N, NW = C::NW, L = 8;
@@ -757,14 +704,12 @@ __global__ __launch_bounds__(256, (FastCfg<R, NLOG>::MIN_WAVES_PER_SIMD)) void k
     const int wave_global = blockIdx.x * C::WAVES + wave;
     const int waves_total = gridDim.x * C::WAVES;
 
-    STAMP(0);
     for (int frame = wave_global; frame < P.B; frame = next_job_wave(P.queue, frame, waves_total, P.B)) {
         s.src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
         if constexpr (C::BIG) {
             // root f, single path: the left child of the root is shared by every path (computed before any fork)
             s.scr = reinterpret_cast<R *>(P.scratch) + (size_t)wave_global * C::scratch_elems;
             R *t = s.tls();
-            STAMP(1);
 #pragma unroll 2
             for (int e = lane; e < N / 2; e += 64) t[e] = s.chk(s.chv(e), s.chv(e + N / 2));
         } else {
@@ -772,7 +717,6 @@ __global__ __launch_bounds__(256, (FastCfg<R, NLOG>::MIN_WAVES_PER_SIMD)) void k
 #pragma unroll 4
             for (int i = lane; i < N; i += 64) s.ch[i] = s.chv(i);
             lds_fence();
-            STAMP(1);
 #pragma unroll 2
             for (int e = lane; e < N / 2; e += 64) s.tl[e] = s.chk(s.ch[e], s.ch[e + N / 2]);
         }
@@ -790,15 +734,13 @@ __global__ __launch_bounds__(256, (FastCfg<R, NLOG>::MIN_WAVES_PER_SIMD)) void k
         s.fl = 0;
         s.logact = 0;
         uint32_t fword = 0;
-        STAMP(2);
 
         for (int o = 0; o < N / 8; ++o) {
             if ((o & 3) == 0) fword = frz[o >> 2];
             s.octet_head(o);
-            STAMP(3);
             const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
-            if ((fm & 0x7Fu) == 0x7Fu) { s.octet_frozen_prefix(o, fm == 0xFFu); STAMP(4); }
-            else { s.octet(o, fm); STAMP(5); }
+            if ((fm & 0x7Fu) == 0x7Fu) s.octet_frozen_prefix(o, fm == 0xFFu);
+            else s.octet(o, fm);
         }
 
         // ================= choose the path (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) =================
@@ -838,12 +780,7 @@ __global__ __launch_bounds__(256, (FastCfg<R, NLOG>::MIN_WAVES_PER_SIMD)) void k
             if (P.flags) P.flags[frame] = fl;
         }
         lds_fence();
-        STAMP(6);
     }
-#ifdef POLAR_STAMPS
-    if (P.dbg && lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&P.dbg[i], tsec[i]);
-#endif
 }
 
 }  // namespace polar

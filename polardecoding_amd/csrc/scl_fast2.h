@@ -21,33 +21,15 @@ namespace polar {
 template <typename R>
 struct Fast2Cfg {
     static constexpr int NLOG = 10, N = 1024, NW = 32, TOP = 9, HI = 8, L = 8;
-#ifndef POLAR_F2_L6S_F64
-#define POLAR_F2_L6S_F64 0
-#endif
-#ifndef POLAR_F2_L6S_F32
-#define POLAR_F2_L6S_F32 0
-#endif
-    // L6S: level 6 stays in the scratch as well (registers hold levels 2..5): 32 fewer VGPRs in f64
-    static constexpr bool L6S = sizeof(R) == 8 ? (POLAR_F2_L6S_F64 != 0) : (POLAR_F2_L6S_F32 != 0);
-    static constexpr int NA = L6S ? 16 : 32;   // levels 2..5 (or ..6), level t at offset 2^t/4
+    // levels 2..6 in registers (keeping level 6 in the scratch as well, 32 fewer VGPRs in f64, lost its A/B run)
+    static constexpr int NA = 32;   // level t at offset 2^t/4
     static constexpr int WAVES = 4;
-// selects of the by-product g steps by sign mask + v_bfi_b32 (1) or by v_cmp + v_cndmask (0): +-0 while the wavefronts took
-// their jobs by a fixed stride (profiles/r03_ab_experiments.txt run 24), + 1.3 % since the work queue (run 34)
-#ifndef POLAR_F2_GSEL_MASK
-#define POLAR_F2_GSEL_MASK 1
-#endif
-#ifndef POLAR_F2_WAVES_F64
-#define POLAR_F2_WAVES_F64 3
-#endif
-#ifndef POLAR_F2_WAVES_F32
-#define POLAR_F2_WAVES_F32 4
-#endif
-    static constexpr int MIN_WAVES_PER_SIMD = sizeof(R) == 8 ? POLAR_F2_WAVES_F64 : POLAR_F2_WAVES_F32;
+    static constexpr int MIN_WAVES_PER_SIMD = sizeof(R) == 8 ? 3 : 4;
     static constexpr int NFA = HI - 3;  // pointer fields: LLR levels 4..8, then partial-sum levels 5..9
     // per-codeword scratch (elements of R)
     static constexpr size_t sc_l8 = 0;
     static constexpr size_t sc_l7 = sc_l8 + 8 * 256;
-    static constexpr size_t sc_l6 = sc_l7 + 8 * 128;
+    static constexpr size_t sc_l6 = sc_l7 + 8 * 128;   // level 6 rows: not used (level 6 is in registers)
     static constexpr size_t sc_tl = sc_l6 + 8 * 64;
     static constexpr size_t scratch_cw = sc_tl + 512;
     static constexpr size_t scratch_elems = 2 * scratch_cw;  // per wave
@@ -56,7 +38,7 @@ struct Fast2Cfg {
     static constexpr size_t off_frz = off_lut + ((Lut<R>::bytes + 15) / 16) * 16;
     static constexpr size_t off_crc = off_frz + 4 * NW;
     static constexpr size_t off_kth = off_crc + 4 * N;      // kth[mask][k] = index of the k-th set bit of mask (u8)
-    static constexpr size_t off_stair = off_kth + 256 * 8;  // Stair<R>: thr[8], dlt[64] (chk_idx; experiments)
+    static constexpr size_t off_stair = off_kth + 256 * 8;  // room for a Stair<R> (chk_idx): not used
     static constexpr size_t shared_bytes = off_stair + ((Stair<R>::bytes + 15) / 16) * 16;
     // per-wave LDS
     static constexpr size_t off_bl = 0;                        // saved partial sums [2][8][NW]
@@ -80,14 +62,11 @@ struct Fast2Dec {
 
     R A[C::NA];      // levels 2..6
     R a1;            // level 1 (pos 0, 1)
-#ifdef POLAR_STAMPS_DECIDE
-    unsigned long long dt_rank = 0, n_rank = 0, dt_info = 0, n_info = 0;   // diagnostic: time / count of ranked steps, of all phase-2 steps
-#endif
-    R bp_s, bp_d, bp_ts, bp_td;
-    // Upper bound (+ 0.65) of the eight path metrics of the lane's codeword, the same in all its lanes, and whether it
-    // is current (wave-uniform).  See decide_t: the cheap sufficient form of the trivial-prune test.
+    R bp_s, bp_d, bp_ts, bp_td;   // by-products of the last level-0 check node: x + y, x - y, T(|x + y|), T(|x - y|)
+    // Written, never read: they served a bound-based trivial-prune test that lost its A/B run.  Dropping the members or
+    // their stores changes k_scl_fast2's register allocation and schedule (same operations).
     R mb65;
-    bool mb_ok;   // by-products of the last level-0 check node: x + y, x - y, T(|x + y|), T(|x - y|)
+    bool mb_ok;
     R PM;            // valid at pos 0
     uint32_t ptr, crc, bl0, fl;
     int logact;
@@ -96,9 +75,6 @@ struct Fast2Dec {
     uint32_t pos0_mask;        // ~0 in the lane that holds its path's metric (pos 0), else 0
     int cand_addr;
     Lut<R> lut;
-#ifdef POLAR_F2_IDX
-    Stair<R> st;
-#endif
     R *cand, *stg;
     uint32_t *blw, *curw, *keys;   // this lane's codeword slice of the per-wave arrays
     const uint32_t *crct;
@@ -157,25 +133,10 @@ struct Fast2Dec {
     // wide steps: the one-round-trip table form, as in the serial chains.  Round 2 had the compact two-round-trip form
     // here in f64; with the by-product octets (octet()) the one-round-trip form measures +2.2 % (same-box A/B, round 3),
     // without them +-0; in f32 it was already +2.4 %.
-    __device__ __forceinline__ R chk(R a, R b) const
-    {
-#ifdef POLAR_F2_IDX
-        return chk_idx<R>(a, b, st);
-#endif
-#ifdef POLAR_F2_WIDE_CHK2   // the compact two-round-trip form in the wide f64 steps (round 2's choice; see below)
-        if constexpr (sizeof(R) == 8) return chk_lut<R>(a, b, lut);
-#endif
-        return chk_lut1<R>(a, b, lut);
-    }
+    __device__ __forceinline__ R chk(R a, R b) const { return chk_lut1<R>(a, b, lut); }
     // the narrow levels inside an octet are serial chains: the one-round-trip table form (four more issue slots,
-    // one LDS latency less) measured +1.8 % there; POLAR_F2_CHK2 selects the compact form everywhere
-#if defined(POLAR_F2_IDX) && POLAR_F2_IDX == 2
-    __device__ __forceinline__ R chks(R a, R b) const { return chk_idx<R>(a, b, st); }
-#elif defined(POLAR_F2_CHK2)
-    __device__ __forceinline__ R chks(R a, R b) const { return chk_lut<R>(a, b, lut); }
-#else
+    // one LDS latency less) measured +1.8 % there against the compact form
     __device__ __forceinline__ R chks(R a, R b) const { return chk_lut1<R>(a, b, lut); }
-#endif
     __device__ __forceinline__ R chv(int e) const
     {
         double v = (double)ld_buf(rs_in, csrc + (unsigned)e, IN(0), 0);
@@ -191,6 +152,9 @@ struct Fast2Dec {
     }
     __device__ __forceinline__ SPtr l8(int slot) const { return SPtr{this, fresh(cscr + (unsigned)(C::sc_l8 + slot * 256))}; }
     __device__ __forceinline__ SPtr l7(int slot) const { return SPtr{this, fresh(cscr + (unsigned)(C::sc_l7 + slot * 128))}; }
+    // A slot's level-6 scratch row.  Nothing is stored there (level 6 is in registers), but from_top, from_l8 and from_l7
+    // still form it: fresh()'s empty asm pins its offset to a VGPR, and dropping it changes k_scl_fast2's register
+    // allocation and schedule (same operations).
     __device__ __forceinline__ SPtr l6s(int slot) const { return SPtr{this, fresh(cscr + (unsigned)(C::sc_l6 + slot * 64))}; }
     __device__ __forceinline__ SPtr tls() const { return SPtr{this, fresh(cscr + (unsigned)C::sc_tl)}; }
 
@@ -199,15 +163,8 @@ struct Fast2Dec {
     __device__ __forceinline__ void f_reg()
     {
         constexpr int RO = (1 << T) / 4;
-        if constexpr (T == 5 && C::L6S) {
-            vm_drain();
-            const SPtr q = l6s(p) + pos;
 #pragma unroll
-            for (int r = 0; r < RO; ++r) A[RO + r] = chk(ld_sc(q + 4 * r), ld_sc(q + 4 * r + 32));
-        } else {
-#pragma unroll
-            for (int r = 0; r < RO; ++r) A[RO + r] = chk(A[2 * RO + r], A[3 * RO + r]);
-        }
+        for (int r = 0; r < RO; ++r) A[RO + r] = chk(A[2 * RO + r], A[3 * RO + r]);
         if constexpr (T >= 4) set_pa(T, p);
     }
     // ---- register levels: g from the owner's level T+1 (bpermute), T in {4, 5} ----
@@ -219,17 +176,10 @@ struct Fast2Dec {
         uint32_t w;
         if constexpr (T == 5) w = blw[pb(5) * NW + 1] >> pos;   // level 5: word 1, bit e = pos + 4r
         else w = bl0 >> (16 + pos);                              // level 4: bits 16 + e
-        if constexpr (T == 5 && C::L6S) {
-            vm_drain();
-            const SPtr q = l6s(pa(6)) + pos;
 #pragma unroll
-            for (int r = 0; r < RO; ++r) A[RO + r] = g_bit<R>(ld_sc(q + 4 * r), ld_sc(q + 4 * r + 32), w, 4 * r);
-        } else {
-#pragma unroll
-            for (int r = 0; r < RO; ++r) {
-                const R x = __shfl(A[2 * RO + r], sl), y = __shfl(A[3 * RO + r], sl);
-                A[RO + r] = g_bit<R>(x, y, w, 4 * r);
-            }
+        for (int r = 0; r < RO; ++r) {
+            const R x = __shfl(A[2 * RO + r], sl), y = __shfl(A[3 * RO + r], sl);
+            A[RO + r] = g_bit<R>(x, y, w, 4 * r);
         }
         set_pa(T, p);
     }
@@ -248,15 +198,11 @@ struct Fast2Dec {
     // The level-6 value of pass rr (element pos + 4 rr).  Registers: the 16 level-6 registers act as a shift
     // register -- after the 16 passes of a step the value of pass rr sits in A[16 + rr] -- so the pass loops can
     // stay rolled without a dynamically indexed register and without a round trip through memory.
-    __device__ __forceinline__ void push_l6(R v, SPtr o6, int e0)
+    __device__ __forceinline__ void push_l6(R v)
     {
-        if constexpr (C::L6S) {
-            o6[e0] = v;
-        } else {
 #pragma unroll
-            for (int r = 16; r < 31; ++r) A[r] = A[r + 1];
-            A[31] = v;
-        }
+        for (int r = 16; r < 31; ++r) A[r] = A[r + 1];
+        A[31] = v;
     }
     __device__ __forceinline__ void load_l6() { set_pa(6, p); }
     // d >= 8 (octets 0, 32, 64, 96): level 8 from the top level (f, or g when gstep), f down to level 6.
@@ -277,7 +223,9 @@ struct Fast2Dec {
         vm_drain();
         const uint32_t *bt = blw + pb(TOP) * NW + 16;  // beta_9: words 16..31
         const uint32_t *bh = blw + pb(HI) * NW + 8;    // beta_8: words 8..15
-        const SPtr o8 = l8(p), o7 = l7(p), o6 = l6s(p);
+        const SPtr o8 = l8(p), o7 = l7(p);
+        const SPtr o6 = l6s(p);
+        (void)o6;
         const int w32 = (int)fresh((unsigned)(p * 4 + pos));   // lane index inside the codeword (recomputed here: the staged
                                                                // elements' offsets are not worth a register each across the frame loop)
         const int nld = right ? 8 : 4;                 // staged elements per lane and chunk
@@ -294,10 +242,7 @@ struct Fast2Dec {
 #pragma unroll
                 for (int m = 0; m < 8; ++m) pre[m] = (m < nld) ? top_src(right, w32 + 32 * m, q + 1) : R(0);
             }
-#ifndef POLAR_F2_TOP_UNROLL
-#define POLAR_F2_TOP_UNROLL 1
-#endif
-#pragma unroll POLAR_F2_TOP_UNROLL
+#pragma unroll 1
             for (int i = 0; i < 4; ++i) {
                 const int rr = 4 * q + i;
                 const int e0 = pos + 4 * rr;
@@ -324,7 +269,7 @@ struct Fast2Dec {
                 const R v70 = chk(v8[0], v8[2]), v71 = chk(v8[1], v8[3]);
                 o7[e0] = v70;
                 o7[e0 + 64] = v71;
-                push_l6(chk(v70, v71), o6, e0);
+                push_l6(chk(v70, v71));
             }
         }
         set_pa(8, p);
@@ -338,11 +283,10 @@ struct Fast2Dec {
         vm_drain();
         const SPtr s8 = l8(pa(8));
         const uint32_t *b7 = blw + pb(7) * NW + 4;  // beta_7: words 4..7
-        const SPtr o7 = l7(p), o6 = l6s(p);
-#ifndef POLAR_F2_CP_F64
-#define POLAR_F2_CP_F64 2
-#endif
-        constexpr int CP = sizeof(R) == 8 ? POLAR_F2_CP_F64 : 4;   // passes per chunk (4 loads each); f64: 8 in flight is the measured optimum
+        const SPtr o7 = l7(p);
+        const SPtr o6 = l6s(p);
+        (void)o6;
+        constexpr int CP = sizeof(R) == 8 ? 2 : 4;   // passes per chunk (4 loads each); f64: 8 in flight is the measured optimum
         for (int q = 0; q < 16 / CP; ++q) {
             R *in = A;       // levels 2..5: dead here, recomputed by the f chain below
 #pragma unroll
@@ -361,7 +305,7 @@ struct Fast2Dec {
                 const R v71 = g_bit<R>(in[4 * i + 1], in[4 * i + 3], b7[2 + wq] >> pos, sh);
                 o7[e0] = v70;
                 o7[e0 + 64] = v71;
-                push_l6(chk(v70, v71), o6, e0);
+                push_l6(chk(v70, v71));
             }
         }
         set_pa(7, p);
@@ -373,13 +317,12 @@ struct Fast2Dec {
         const SPtr s7 = l7(pa(7)) + pos;
         const uint32_t *b6 = blw + pb(6) * NW + 2;  // beta_6: words 2, 3
         const uint32_t w0 = b6[0] >> pos, w1 = b6[1] >> pos;
-        const SPtr o6 = l6s(p) + pos;
+        const SPtr o6 = l6s(p);
+        (void)o6;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const R x = ld_sc(s7 + 4 * r), y = ld_sc(s7 + 4 * r + 64);
-            const R v = g_bit<R>(x, y, r < 8 ? w0 : w1, 4 * (r & 7));
-            if constexpr (C::L6S) o6[4 * r] = v;
-            else A[16 + r] = v;
+            A[16 + r] = g_bit<R>(x, y, r < 8 ? w0 : w1, 4 * (r & 7));
         }
         set_pa(6, p);
     }
@@ -515,12 +458,6 @@ struct Fast2Dec {
     // cb / cw = the path's metric with the favoured / the other branch, cb <= cw, valid at pos 0.
     __device__ __forceinline__ bool trivial_prune(R cb, R cw) const
     {
-        uint32_t mx;
-        return trivial_prune(cb, cw, mx);
-    }
-    // mx_out: the largest favoured key of the lane's codeword (valid in every lane)
-    __device__ __forceinline__ bool trivial_prune(R cb, R cw, uint32_t &mx_out) const
-    {
         // the largest favoured key of the lane's codeword (the other lanes of a path take no part: 0), then ONE compare per
         // path: "max favoured < min other" <=> every path's other key is above that maximum
         uint32_t mx = metric_key(cb) & pos0_mask;
@@ -533,12 +470,8 @@ struct Fast2Dec {
             auto a = __builtin_amdgcn_permlane32_swap(mx, mx, false, false);
             mx = max(a[0], a[1]);
         }
-        mx_out = mx;
         return __ballot(mx >= (metric_key(cw) | ~pos0_mask)) == 0ull;
     }
-    // smallest value whose key is above `key`: an upper bound of every metric with a key <= `key`
-    static __device__ __forceinline__ double above_key(uint32_t key, double) { return __hiloint2double((int)(key + 1u), 0); }
-    static __device__ __forceinline__ float above_key(uint32_t key, float) { return __int_as_float((int)(key + 1u)); }
     static __device__ __forceinline__ uint32_t sign_bit(double x) { return (uint32_t)__double2hiint(x) >> 31; }
     static __device__ __forceinline__ uint32_t sign_bit(float x) { return (uint32_t)__float_as_int(x) >> 31; }
 
@@ -551,13 +484,8 @@ struct Fast2Dec {
     __device__ __forceinline__ void decide_t(int o, bool frozen, R lam, R tt)
     {
         const int j = 8 * o + K;
-        POLAR_MARK("d2_begin");
         uint32_t crcw = 0;
-#ifdef POLAR_F2_CRC_BRANCH
-        if (CRC_ON && !frozen) crcw = crct[j];
-#else
         if (CRC_ON) crcw = crct[j];   // the table holds 0 for frozen leaves (make_crc_table): no branch around the read
-#endif
         uint32_t bit = 0;
         if (frozen) {
             PM += tt + negmax(lam);  // PHI(.,0)
@@ -570,106 +498,54 @@ struct Fast2Dec {
                 PM += bit ? ph1 : ph0;
                 ++logact;
             } else {
-                POLAR_MARK("d2_phase2");
-#ifdef POLAR_STAMPS_DECIDE
-                const unsigned long long t_i0 = __builtin_amdgcn_s_memtime();
-#endif
                 // PHI of the branch lambda favours is T(|lambda|), of the other one T(|lambda|) + |lambda|
                 // (SCL_1024.c:481-502; T + 0 is T, so these ARE c0 / c1 in the order the sign of lambda says).
                 const uint32_t lneg = sign_bit(lam);   // lambda = +-0: cb == cw, never trivial, c0 == c1 below
-#ifdef POLAR_F2_BOUND
-                // The same test on bounds that need no reduction over the paths.  mb65 >= M + 0.65 with M >= every
-                // metric of the codeword, so every favoured candidate PM + T(|lambda|) <= mb65 (T <= 0.65, rounding is
-                // monotone); every other candidate PM + (T + |lambda|) >= PM + |lambda| (T >= 0).  If the key of mb65 is
-                // below the key of PM + |lambda| on every path, max favoured < min other: the prune is trivial.  After
-                // it every metric has grown by at most 0.65, so mb65 + 0.65 bounds the next leaf.  When the bound is
-                // stale (after a frozen leaf or a ranked step) or too loose, the exact test below decides and renews it.
-                if (mb_ok && __ballot(metric_key(mb65) >= (metric_key(PM + absr(lam)) | ~pos0_mask)) == 0ull) {
-                    bit = (uint32_t)dpp_i<0x00>((int)lneg);
-                    PM = PM + tt;
-                    mb65 = mb65 + R(0.65);
-                } else {
-#endif
                 const R cb = PM + tt, cw = PM + (tt + absr(lam));
                 // Most information leaves (85 % at 1-3 dB) prune trivially: every path keeps its favoured branch.
                 // That is certain when the largest of the eight favoured keys is below the smallest of the eight
                 // others (the 8 favoured candidates are then the 8 smallest of the 16, all strictly below the median
                 // of SCL_1024.c:619-633), and three max/min steps over the path lanes show it -- without the key
                 // exchange through LDS, the rank network and the fork bookkeeping.  Both codewords must qualify.
-                uint32_t mxk;
-                if (trivial_prune(cb, cw, mxk)) {
+                if (trivial_prune(cb, cw)) {
                     bit = (uint32_t)dpp_i<0x00>((int)lneg);   // quad_perm [0,0,0,0]: pos 0 holds lambda
                     PM = cb;
-#ifdef POLAR_F2_BOUND
-                    mb65 = above_key(mxk, R(0)) + R(0.65);   // every new metric (= cb) has a key <= mxk
-                    mb_ok = true;
-#endif
                 } else {
-#ifdef POLAR_F2_BOUND
-                mb_ok = false;
-#endif
-#ifdef POLAR_STAMPS_DECIDE
-                const unsigned long long t_r0 = __builtin_amdgcn_s_memtime();
-#endif
-                const R c0 = lneg ? cw : cb, c1 = lneg ? cb : cw;
-                const uint32_t mask = survivors(c0, c1);
-                POLAR_MARK("d2_rank_end");
-                const uint32_t m0 = mask & 0xFFu, m1 = mask >> 8;
-                const uint32_t m_both = m0 & m1, m_dead = ~(m0 | m1) & 0xFFu;
-                if (__popc(mask) < L) fl |= 0x1u;  // median tie in this lane's codeword
-                const bool s0 = (m0 >> p) & 1, s1 = (m1 >> p) & 1;
-                if (__ballot(m_dead != 0u) == 0ull) {
-                    bit = (!s0 && s1) ? 1u : 0u;  // no codeword forks: every slot keeps exactly one branch
-                    PM = bit ? c1 : c0;
-                } else {
-                    POLAR_MARK("d2_fork");
-                    // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661), per codeword
-                    const bool dead = !s0 && !s1;
-                    const int myrank = __popc(m_dead & ((1u << p) - 1u));
-                    const bool refilled = dead && (myrank < __popc(m_both));
-                    const int sg = refilled ? (int)kth[m_both * 8 + myrank] : p;
-                    const int sl = sg * 8 + gl;
-                    const R c1s = __shfl(c1, sl);
-                    ptr = __shfl(ptr, sl);
-                    crc = __shfl(crc, sl);
-                    bl0 = __shfl(bl0, sl);
-#ifdef POLAR_F2_NO_BYPROD
-                    if constexpr ((K & 4) == 0) { A[2] = __shfl(A[2], sl); A[3] = __shfl(A[3], sl); }  // level 3, read by g2
-                    if constexpr ((K & 2) == 0) A[1] = __shfl(A[1], sl);                                // level 2, read by g1
-                    if constexpr ((K & 1) == 0) a1 = __shfl(a1, sl);                                    // level 1, read by g0
-#else
-                    // what the lower-node steps still to come in this octet read: the sum / difference pairs of the
-                    // check nodes above them (octet())
-                    if constexpr ((K & 4) == 0) { A[2] = __shfl(A[2], sl); A[3] = __shfl(A[3], sl); }  // s2, d2: g at level 2 (leaf 4)
-                    if constexpr ((K & 2) == 0) { A[1] = __shfl(A[1], sl); a1 = __shfl(a1, sl); }       // s1, d1: g at level 1
-                    if constexpr ((K & 1) == 0) { bp_d = __shfl(bp_d, sl); bp_td = __shfl(bp_td, sl); } // a forked copy continues with bit 1: -d0, T(|d0|)
-#endif
-                    if (refilled) { bit = 1; PM = c1s; }
-                    else if (s0) { bit = 0; PM = c0; }
-                    else if (s1) { bit = 1; PM = c1; }
-                    else { bit = 0; PM = c0; }  // tie rule: un-refilled dead slot continues as its 0-branch
+                    const R c0 = lneg ? cw : cb, c1 = lneg ? cb : cw;
+                    const uint32_t mask = survivors(c0, c1);
+                    const uint32_t m0 = mask & 0xFFu, m1 = mask >> 8;
+                    const uint32_t m_both = m0 & m1, m_dead = ~(m0 | m1) & 0xFFu;
+                    if (__popc(mask) < L) fl |= 0x1u;  // median tie in this lane's codeword
+                    const bool s0 = (m0 >> p) & 1, s1 = (m1 >> p) & 1;
+                    if (__ballot(m_dead != 0u) == 0ull) {
+                        bit = (!s0 && s1) ? 1u : 0u;  // no codeword forks: every slot keeps exactly one branch
+                        PM = bit ? c1 : c0;
+                    } else {
+                        // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661), per codeword
+                        const bool dead = !s0 && !s1;
+                        const int myrank = __popc(m_dead & ((1u << p) - 1u));
+                        const bool refilled = dead && (myrank < __popc(m_both));
+                        const int sg = refilled ? (int)kth[m_both * 8 + myrank] : p;
+                        const int sl = sg * 8 + gl;
+                        const R c1s = __shfl(c1, sl);
+                        ptr = __shfl(ptr, sl);
+                        crc = __shfl(crc, sl);
+                        bl0 = __shfl(bl0, sl);
+                        // what the lower-node steps still to come in this octet read: the sum / difference pairs of the
+                        // check nodes above them (octet())
+                        if constexpr ((K & 4) == 0) { A[2] = __shfl(A[2], sl); A[3] = __shfl(A[3], sl); }  // s2, d2: g at level 2 (leaf 4)
+                        if constexpr ((K & 2) == 0) { A[1] = __shfl(A[1], sl); a1 = __shfl(a1, sl); }       // s1, d1: g at level 1
+                        if constexpr ((K & 1) == 0) { bp_d = __shfl(bp_d, sl); bp_td = __shfl(bp_td, sl); } // a forked copy continues with bit 1: -d0, T(|d0|)
+                        if (refilled) { bit = 1; PM = c1s; }
+                        else if (s0) { bit = 0; PM = c0; }
+                        else if (s1) { bit = 1; PM = c1; }
+                        else { bit = 0; PM = c0; }  // tie rule: un-refilled dead slot continues as its 0-branch
+                    }
                 }
-#ifdef POLAR_STAMPS_DECIDE
-                __asm__ volatile("" :: "v"(bit), "v"(PM));
-                dt_rank += __builtin_amdgcn_s_memtime() - t_r0;
-                ++n_rank;
-#endif
-                }
-#ifdef POLAR_F2_BOUND
-                }
-#endif
-#ifdef POLAR_STAMPS_DECIDE
-                __asm__ volatile("" :: "v"(bit), "v"(PM));
-                dt_info += __builtin_amdgcn_s_memtime() - t_i0;
-                ++n_info;
-#endif
             }
-            POLAR_MARK("d2_fork_end");
             if (CRC_ON) crc ^= bit ? crcw : 0u;
         }
-        POLAR_MARK("d2_setbit");
         set_bit_k<K>(o, bit);
-        POLAR_MARK("d2_end");
     }
 
     // ---- the leading run of P all-frozen octets (leaves 0 .. 8P-1; 1 <= P <= 15), instead of octets 0 .. P-1 ----
@@ -727,14 +603,8 @@ struct Fast2Dec {
             lds_fence();
             if (t >= 4) {   // node of level t that holds leaf j0: elements pos + 4r
                 const R *node = stg + ((j0 >> t) << t) + pos;
-                if (t == 6 && C::L6S) {
-                    const SPtr o6 = l6s(p) + pos;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) o6[4 * r] = node[4 * r];
-                } else {
-#pragma unroll
-                    for (int r = 0; r < h / 4; ++r) A[h / 4 + r] = node[4 * r];
-                }
+                for (int r = 0; r < h / 4; ++r) A[h / 4 + r] = node[4 * r];
             }
         }
         // PHI(lambda_j, 0) of all 128 leaves, then the metric in leaf order
@@ -806,17 +676,14 @@ struct Fast2Dec {
         r.v = xor_sign(minabs(x, y), x, y) + (r.ts - r.td);
         return r;
     }
-    // s or -d by the partner bit at position sh of w
+    // s or -d by the partner bit at position sh of w.  The selects of the by-product g steps go by sign mask + v_bfi_b32
+    // rather than v_cmp + v_cndmask: +-0 while the wavefronts took their jobs by a fixed stride
+    // (profiles/r03_ab_experiments.txt run 24), + 1.3 % since the work queue (run 34).
     static __device__ __forceinline__ R g_sel(R sum, R dif, uint32_t w, int sh)
     {
-#if !POLAR_F2_GSEL_MASK
-        const bool b = (w >> sh) & 1u;
-        return b ? -dif : sum;
-#else
         // bit -> all-ones mask (one v_bfe_i32), then v_bfi per word: no compare, no v_cndmask
         const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)w, sh, 1);
         return Lut<R>::sel_mask(m, -dif, sum);
-#endif
     }
     template <int K>   // leaves K (even) and K + 1 from the level-1 pair in a1 (pos 0: x, pos 1: y)
     __device__ __forceinline__ void leaf_pair(int o, uint32_t fm, R x1)
@@ -827,17 +694,11 @@ struct Fast2Dec {
         decide<K>(o, (fm >> K) & 1, q.v);
         // leaf K + 1: g0 with the bit just decided (bit 1 of bl0, set_bit_k<even>); a slot refilled by a fork took
         // bp_d / bp_td of its source and continues with bit 1, every other slot still has its own q.s / q.ts
-#if !POLAR_F2_GSEL_MASK
-        const bool b1 = (bl0 >> 1) & 1u;
-        decide_t<K + 1>(o, (fm >> (K + 1)) & 1, b1 ? -bp_d : q.s, b1 ? bp_td : q.ts);
-#else
         const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)bl0, 1, 1);
         decide_t<K + 1>(o, (fm >> (K + 1)) & 1, Lut<R>::sel_mask(m1, -bp_d, q.s), Lut<R>::sel_mask(m1, bp_td, q.ts));
-#endif
     }
     __device__ __forceinline__ void octet(int o, uint32_t fm)
     {
-#ifndef POLAR_F2_NO_BYPROD
         // level 2: f of (A[2], A[3]); its sum / difference stay in A[2], A[3] for the g step at leaf 4
         {
             const R s2 = A[2] + A[3], d2 = A[2] - A[3];
@@ -863,61 +724,23 @@ struct Fast2Dec {
             leaf_pair<4>(o, fm, v1);
         }
         leaf_pair<6>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
-        return;
-#endif
-        // leaf 0: f2 f1 f0
-        A[1] = chks(A[2], A[3]);
-        a1 = chks(A[1], quadp<0x4E>(A[1]));
-        decide<0>(o, fm & 1, chks(a1, quadp<0xB1>(a1)));
-        // leaf 1: g0
-        decide<1>(o, (fm >> 1) & 1, g_bit<R>(a1, quadp<0xB1>(a1), bl0, 1));
-        // leaf 2: g1 f0
-        a1 = g_bit<R>(A[1], quadp<0x4E>(A[1]), bl0, 2 + pos);
-        decide<2>(o, (fm >> 2) & 1, chks(a1, quadp<0xB1>(a1)));
-        // leaf 3: g0
-        decide<3>(o, (fm >> 3) & 1, g_bit<R>(a1, quadp<0xB1>(a1), bl0, 1));
-        // leaf 4: g2 f1 f0
-        A[1] = g_bit<R>(A[2], A[3], bl0, 4 + pos);
-        a1 = chks(A[1], quadp<0x4E>(A[1]));
-        decide<4>(o, (fm >> 4) & 1, chks(a1, quadp<0xB1>(a1)));
-        // leaf 5: g0
-        decide<5>(o, (fm >> 5) & 1, g_bit<R>(a1, quadp<0xB1>(a1), bl0, 1));
-        // leaf 6: g1 f0
-        a1 = g_bit<R>(A[1], quadp<0x4E>(A[1]), bl0, 2 + pos);
-        decide<6>(o, (fm >> 6) & 1, chks(a1, quadp<0xB1>(a1)));
-        // leaf 7: g0
-        decide<7>(o, (fm >> 7) & 1, g_bit<R>(a1, quadp<0xB1>(a1), bl0, 1));
     }
 };
 
 template <typename R, typename IN, bool CRC_ON>
 __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_fast2(SclParams P)
 {
-#ifdef POLAR_STAMPS
-    unsigned long long tsec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-#ifdef POLAR_STAMPS_XCC
-    unsigned long long njobs = 0;
-#endif
-#endif
     using D = Fast2Dec<R, IN, CRC_ON>;
     using C = Fast2Cfg<R>;
     constexpr int N = C::N, NW = C::NW, L = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-#ifdef POLAR_F2_WAVE_VGPR
-    const int wave = threadIdx.x >> 6;
-#else
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the per-wave LDS base is scalar
-#endif
     unsigned char *base = smem + C::shared_bytes + (size_t)wave * C::per_wave;
     uint32_t *frz = reinterpret_cast<uint32_t *>(smem + C::off_frz);
     uint32_t *crct = reinterpret_cast<uint32_t *>(smem + C::off_crc);
     unsigned char *kth = smem + C::off_kth;
 
     Lut<R>::build(smem + C::off_lut, threadIdx.x, blockDim.x);
-#ifdef POLAR_F2_IDX
-    Stair<R>::build(smem + C::off_stair, threadIdx.x, blockDim.x);
-#endif
     for (int i = threadIdx.x; i < NW; i += blockDim.x) frz[i] = P.frozen[i];
     if (CRC_ON)
         for (int i = threadIdx.x; i < N; i += blockDim.x) crct[i] = P.crc_tab[i];
@@ -940,9 +763,6 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
     s.pos0_mask = s.pos == 0 ? 0xFFFFFFFFu : 0u;
     s.gl = s.lane & 7;
     s.lut.bind(smem + C::off_lut);
-#ifdef POLAR_F2_IDX
-    s.st.bind(smem + C::off_stair);
-#endif
     s.crct = crct;
     s.kth = kth;
     s.blw = reinterpret_cast<uint32_t *>(base + C::off_bl) + s.c * 8 * NW;
@@ -969,9 +789,6 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
     // leading all-frozen octets (at most 15: the run must end inside the first 128-leaf subtree)
     int lead = 0;
     while (lead < 15 && ((frz[lead >> 2] >> (8 * (lead & 3))) & 0xFFu) == 0xFFu) ++lead;
-#ifdef POLAR_F2_NO_PREFIX
-    lead = 0;
-#endif
     lead = __builtin_amdgcn_readfirstlane(lead);
 
     // jobs (pairs of frames): the first one by the wavefront's index, the others from the launch's work queue
@@ -1005,37 +822,18 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
         s.mb_ok = false;
         uint32_t fword = 0;
 
-        STAMP(2);
         int o_first = 0;
         if (lead > 0) {
             s.frozen_prefix(lead);
-            STAMP(4);
             o_first = lead;
             fword = frz[o_first >> 2];
         }
         for (int o = o_first; o < N / 8; ++o) {
             if ((o & 3) == 0) fword = frz[o >> 2];
-#ifdef POLAR_STAMPS_HEADS   // finer split of the octet heads: 0 from_top, 1 from_l8, 7 from_l7, 3 register g steps, 2 f chains
-            {
-                const int d = (o == 0) ? 10 : 3 + __builtin_ctz((unsigned)o);
-                if (d >= 8) { s.from_top(o >= N / 16, d == 8); STAMP(0); }
-                else if (d == 7) { s.from_l8(); STAMP(1); }
-                else if (d == 6) { s.from_l7(); STAMP(7); }
-                else if (d == 5) { s.template g_reg<5>(); STAMP(3); }
-                else if (d == 4) { s.template g_reg<4>(); STAMP(3); }
-                else { s.g3(); STAMP(3); }
-                if (d > 5) s.template f_reg<5>();
-                if (d > 4) s.template f_reg<4>();
-                if (d > 3) s.template f_reg<3>();
-                STAMP(2);
-            }
-#else
             s.octet_head(o);
-            if (o == 0 || (o & 7) == 0) STAMP(7); else STAMP(3);
-#endif
             const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
-            if ((fm & 0x7Fu) == 0x7Fu) { s.octet_frozen_prefix(o, fm == 0xFFu); STAMP(4); }
-            else { s.octet(o, fm); STAMP(5); }
+            if ((fm & 0x7Fu) == 0x7Fu) s.octet_frozen_prefix(o, fm == 0xFFu);
+            else s.octet(o, fm);
         }
 
         // ---- choose the path, per codeword (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) ----
@@ -1079,34 +877,8 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
             if (P.flags) P.flags[frame] = fl;
         }
         lds_fence();
-        STAMP(6);
         pair = next_job_wave(P.queue, pair, waves_total, (P.B + 1) >> 1);
-#ifdef POLAR_STAMPS_XCC
-        ++njobs;
-#endif
     }
-#ifdef POLAR_STAMPS
-#ifdef POLAR_STAMPS_XCC   // diagnostic: jobs per XCD (bucket = XCC_ID) or per shader engine (POLAR_STAMPS_XCC == 2), x 1000
-    {
-        unsigned xcc, hw;
-        __asm__ volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        __asm__ volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        unsigned bucket = (POLAR_STAMPS_XCC == 2) ? ((hw >> 13) & 7u) : (xcc & 7u);
-        if (POLAR_STAMPS_XCC == 3) {   // histogram of jobs per wavefront around the mean: <= mean-3, -2, -1, 0, +1, +2, +3, >= +4 (x 1000 x jobs)
-            const int mean = (P.B / 2) / waves_total;
-            bucket = (unsigned)min(max((int)njobs - mean + 3, 0), 7);
-        }
-        if (POLAR_STAMPS_XCC == 4) bucket = (hw >> 8) & 7u;    // CU_ID (low three bits)
-        if (POLAR_STAMPS_XCC == 5) bucket = (hw >> 4) & 3u;    // SIMD_ID
-        for (int i = 0; i < 8; ++i) tsec[i] = (i == (int)bucket) ? 1000ull * njobs : 0ull;
-    }
-#endif
-#ifdef POLAR_STAMPS_DECIDE   // buckets 0 / 1: time and count (x 1000) of the ranked steps, 7 / 6: of all phase-2 information leaves
-    tsec[0] = s.dt_rank; tsec[1] = s.n_rank * 1000; tsec[7] += s.dt_info; tsec[6] = s.n_info * 1000;
-#endif
-    if (P.dbg && lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&P.dbg[i], tsec[i]);
-#endif
 }
 
 }  // namespace polar

@@ -26,13 +26,7 @@ struct Fast4Cfg {
     static constexpr int NLOG = 10, N = 1024, NW = 32, TOP = 9, HI = 8, L = 8, CW = 4;
     static constexpr int NA = 64;   // levels 2..6, level t at offset 2^t/2
     static constexpr int WAVES = 4;
-#ifndef POLAR_F4_WAVES_F64
-#define POLAR_F4_WAVES_F64 2
-#endif
-#ifndef POLAR_F4_WAVES_F32
-#define POLAR_F4_WAVES_F32 3
-#endif
-    static constexpr int MIN_WAVES_PER_SIMD = sizeof(R) == 8 ? POLAR_F4_WAVES_F64 : POLAR_F4_WAVES_F32;
+    static constexpr int MIN_WAVES_PER_SIMD = sizeof(R) == 8 ? 2 : 3;
     static constexpr int NFA = HI - 3;  // pointer fields: LLR levels 4..8, then partial-sum levels 5..9
     // per-wave scratch (elements of R).  Levels 8 and 7 are stored LANE-INTERLEAVED: element e = pos + 2 rr + 64 k of the
     // row of lane l = slot*8 + c*2 + pos sits at ((k*32 + rr)*64 + l), so that one load or store instruction of the
@@ -87,13 +81,10 @@ struct Fast4Dec {
     __device__ __forceinline__ void set_pa(int t, int v) { ptr = (ptr & ~(7u << (3 * (t - 4)))) | ((uint32_t)v << (3 * (t - 4))); }
     __device__ __forceinline__ int pb(int t) const { return (ptr >> (3 * (NFA + t - 5))) & 7; }
     __device__ __forceinline__ void set_pb(int t, int v) { ptr = (ptr & ~(7u << (3 * (NFA + t - 5)))) | ((uint32_t)v << (3 * (NFA + t - 5))); }
-#ifndef POLAR_F4_WIDE_LUT1
-#define POLAR_F4_WIDE_LUT1 0
-#endif
-    // wide steps: the compact two-round-trip form (the one-round-trip form, POLAR_F4_WIDE_LUT1=1, measured 13.0 -> 19.5 ms: spills)
+    // wide steps: the compact two-round-trip form in f64 (the one-round-trip form there measured 13.0 -> 19.5 ms: spills)
     __device__ __forceinline__ R chk(R a, R b) const
     {
-        if constexpr (sizeof(R) == 4 || (POLAR_F4_WIDE_LUT1 != 0)) return chk_lut1<R>(a, b, lut);
+        if constexpr (sizeof(R) == 4) return chk_lut1<R>(a, b, lut);
         else return chk_lut<R>(a, b, lut);
     }
     __device__ __forceinline__ R chks(R a, R b) const { return chk_lut1<R>(a, b, lut); }
@@ -252,10 +243,7 @@ struct Fast4Dec {
         const R *s8 = l8(pa(8));
         const uint32_t *b7 = blw + pb(7) * NW + 4;  // beta_7: words 4..7
         R *o7 = l7(p);
-#ifndef POLAR_F4_L8_BATCH
-#define POLAR_F4_L8_BATCH 4
-#endif
-        constexpr int NB = POLAR_F4_L8_BATCH;   // passes per batch: 4 NB loads in flight per lane
+        constexpr int NB = 4;   // passes per batch: 4 NB loads in flight per lane
         for (int q = 0; q < 4; ++q) {
             R t6[8];
 #pragma unroll
@@ -289,10 +277,7 @@ struct Fast4Dec {
         vm_drain();
         const R *s7 = l7(pa(7));
         const uint32_t *b6 = blw + pb(6) * NW + 2;  // beta_6: words 2, 3
-#ifndef POLAR_F4_L7_BATCH
-#define POLAR_F4_L7_BATCH 8
-#endif
-        constexpr int NB = POLAR_F4_L7_BATCH;   // passes per batch: 2 NB loads in flight per lane
+        constexpr int NB = 8;   // passes per batch: 2 NB loads in flight per lane
         for (int q = 0; q < 4; ++q) {
             R t6[8];
 #pragma unroll
@@ -672,10 +657,6 @@ struct Fast4Dec {
 template <typename R, typename IN, bool CRC_ON>
 __global__ __launch_bounds__(256, (Fast4Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_fast4(SclParams P)
 {
-#ifdef POLAR_STAMPS
-    unsigned long long tsec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-#endif
     using D = Fast4Dec<R, IN, CRC_ON>;
     using C = Fast4Cfg<R>;
     constexpr int N = C::N, NW = C::NW, L = 8, CW = C::CW;
@@ -733,9 +714,6 @@ __global__ __launch_bounds__(256, (Fast4Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
     // leading all-frozen octets (at most 15: the run must end inside the first 128-leaf subtree)
     int lead = 0;
     while (lead < 15 && ((frz[lead >> 2] >> (8 * (lead & 3))) & 0xFFu) == 0xFFu) ++lead;
-#ifdef POLAR_F4_NO_PREFIX
-    lead = 0;
-#endif
     lead = __builtin_amdgcn_readfirstlane(lead);
 
     for (int quad = wave_global; CW * quad < P.B; quad = next_job_wave(P.queue, quad, waves_total, (P.B + CW - 1) / CW)) {
@@ -765,40 +743,18 @@ __global__ __launch_bounds__(256, (Fast4Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
         s.logact = 0;
         uint32_t fword = 0;
 
-        STAMP(2);
         int o_first = 0;
         if (lead > 0) {
             s.frozen_prefix(lead);
-            STAMP(6);
             o_first = lead;
             fword = frz[o_first >> 2];
         }
         for (int o = o_first; o < N / 8; ++o) {
             if ((o & 3) == 0) fword = frz[o >> 2];
-#ifdef POLAR_STAMPS
-            {
-                const int d = (o == 0) ? 10 : 3 + __builtin_ctz((unsigned)o);
-                if (d >= 8) { s.from_top(o >= N / 16, d == 8); STAMP(0); }
-                else if (d == 7) { s.from_l8(); STAMP(1); }
-                else if (d == 6) { s.from_l7(); STAMP(7); }
-                else if (d == 5) { s.template g_reg<5>(); STAMP(3); }
-                else if (d == 4) { s.template g_reg<4>(); STAMP(3); }
-                else { s.g3(); STAMP(3); }
-                if (d > 5) s.template f_reg<5>();
-                if (d > 4) s.template f_reg<4>();
-                if (d > 3) s.template f_reg<3>();
-                STAMP(4);
-            }
-#else
             s.octet_head(o);
-#endif
             const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
-#ifndef POLAR_F4_NO_PREFIX
             if ((fm & 0x7Fu) == 0x7Fu) s.octet_frozen_prefix(o, fm == 0xFFu);
-            else
-#endif
-                s.octet(o, fm);
-            STAMP(5);
+            else s.octet(o, fm);
         }
 
         // ---- choose the path, per codeword (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) ----
@@ -851,12 +807,7 @@ __global__ __launch_bounds__(256, (Fast4Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
             if (P.flags) P.flags[frame] = fl;
         }
         lds_fence();
-        STAMP(6);
     }
-#ifdef POLAR_STAMPS
-    if (P.dbg && lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&P.dbg[i], tsec[i]);
-#endif
 }
 
 }  // namespace polar

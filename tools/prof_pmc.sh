@@ -1,11 +1,12 @@
 #!/bin/bash
-# [POLAR_PROF_PROG=tools/bench_configs.py] tools/prof_pmc.sh OUTDIR [args] -- rocprofv3 passes for the headline kernel (run on the GPU box via gpurun).
+# [POLAR_PROF_PROG=tools/bench_configs.py] tools/prof_pmc.sh OUTDIR [args] -- rocprofv3 passes for the headline kernel (run on the GPU machine).
 # One kernel-trace/stats pass and separate --pmc passes (never combined with other trace domains).
 # The program itself follows `--` (python3 bench.py ...), no env/bash -c hop.
 OUT=${1:-gpurun_out/prof}
 shift
 ARGS=${@:-"--steps 3 --warmup 1 --no-cpu-baseline --no-fer-sweep --no-other-configs --no-end-to-end"}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)   # the repository root
+[ -n "$R" ] || { echo "cannot locate the repository root" >&2; exit 1; }
 PROG=${POLAR_PROF_PROG:-bench.py}   # e.g. tools/bench_configs.py with ARGS "--only BP"
 mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp

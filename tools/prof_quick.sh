@@ -2,7 +2,8 @@
 # tools/prof_quick.sh OUTDIR LIBNAME [config] -- a handful of rocprofv3 --pmc passes over ONE library variant's kernel
 # (tools/variant.py worker: 1 warm + a few timed launches), program directly after `--`.
 OUT=$1; LIB=$2; CFG=${3:-cascl}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)   # the repository root
+[ -n "$R" ] || { echo "cannot locate the repository root" >&2; exit 1; }
 mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
 i=0

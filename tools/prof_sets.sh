@@ -2,7 +2,8 @@
 # tools/prof_sets.sh OUTDIR LIBNAME CONFIG "SET1" "SET2" ... -- one rocprofv3 --pmc pass per counter set over one library
 # variant's kernel (tools/variant.py worker), then per-dispatch means.  Program directly after `--`.
 OUT=$1; LIB=$2; CFG=$3; shift 3
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)   # the repository root
+[ -n "$R" ] || { echo "cannot locate the repository root" >&2; exit 1; }
 mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
 i=0

@@ -1,5 +1,5 @@
-"""Developer tool: run bench.py (or another script) against an alternative build of the library, e.g. the
--DPOLAR_STAMPS build:   python tools/run_with_lib.py build/libpolar_hip_stamps.so bench.py --steps 3 --no-cpu-baseline"""
+"""Developer tool: run bench.py (or another script) against an alternative build of the library, e.g. one from
+tools/variant.py:   python tools/run_with_lib.py build/variants/libpolar_hip_NAME.so bench.py --steps 3 --no-cpu-baseline"""
 import os
 import runpy
 import sys

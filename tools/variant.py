@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Developer tool: build variants of the library for same-box A/B comparisons of one kernel.
 
-    python tools/variant.py build NAME [--tu k_fast2] [-DFOO=1 ...] [--flags "-mllvm ..."]
-        compiles the named translation unit(s) with the extra flags and links them with the default objects of the
-        other units into build/variants/libpolar_hip_NAME.so (run __graft_entry__.build_library() first).
-        With --stamps the host unit is rebuilt with -DPOLAR_STAMPS too (section timers printed at exit).
-    python tools/variant.py ab NAME1 NAME2 ... [--config cascl|scl|cfg5|bp|sc] [--reps 5] [--dtype f64]
-        on the GPU box: times the configuration's kernel with each library in its own process (same inputs, fixed seed),
+    python tools/variant.py build NAME [--tu k_fast2] [--flags "-mllvm ..."] [--no-sched]
+        compiles the named translation unit(s) with other compiler options and links them with the default objects of
+        the other units into build/variants/libpolar_hip_NAME.so (run __graft_entry__.build_library() first).  The
+        sources have no preprocessor switches: a source variant is built from its own checkout (e.g. a git worktree)
+        and compared by the path of its library.
+    python tools/variant.py ab LIB1 LIB2 ... [--config cascl|scl|cfg5|bp|sc] [--reps 5] [--dtype f64]
+        on the GPU: times the configuration's kernel with each library in its own process (same inputs, fixed seed),
         checks the decisions against the first one and against the CPU oracle on 64 frames, prints one line per library.
-        "base" names the shipped polardecoding_amd/lib/libpolar_hip.so.
+        A LIB is a variant NAME, "base" (the shipped polardecoding_amd/lib/libpolar_hip.so) or the path of a .so.
 """
 import argparse
 import hashlib
@@ -23,25 +24,24 @@ VDIR = os.path.join(REPO, "build", "variants")
 
 
 def lib_of(name):
+    if name.endswith(".so") or os.sep in name:
+        return os.path.abspath(name)
     if name == "base":
         return os.path.join(REPO, "polardecoding_amd", "lib", "libpolar_hip.so")
     return os.path.join(VDIR, f"libpolar_hip_{name}.so")
 
 
-def build(args, extra):
+def build(args):
     import __graft_entry__ as g
     g.build_library(testing=False)
     os.makedirs(VDIR, exist_ok=True)
     odir = os.path.join(g.OBJDIR, "var_" + args.name)
     os.makedirs(odir, exist_ok=True)
     tus = args.tu.split(",")
-    if args.stamps and "polar_hip" not in tus:
-        tus.append("polar_hip")
-        extra = list(extra) + ["-DPOLAR_STAMPS"]
     flags = [f for f in g.HIPCC_FLAGS]
     if args.no_sched:
         flags = [f for f in flags if "sched-strategy" not in f and f != "-mllvm"]
-    flags += list(extra) + (args.flags.split() if args.flags else [])
+    flags += args.flags.split() if args.flags else []
     objs = []
     procs = []
     for tu in g.KERNEL_TUS + ["polar_hip"]:
@@ -151,11 +151,8 @@ def ab(args):
                 first = d["hash"]
             d["same_as_first"] = d["hash"] == first
             rows.append(d)
-            st = [l for l in r.stderr.splitlines() if l.startswith("[stamps]")]
             print(f"{name:24s} {d['config']:8s} {d['dtype']} med {d['ms_med']:8.3f} ms  min {d['ms_min']:8.3f} ms  {d['Mfps']:8.3f} M/s  "
                   f"same={d['same_as_first']} oracle={d['oracle_ok']}  {d['kernel']}", flush=True)
-            for l in st:
-                print("    " + l)
     return rows
 
 
@@ -165,7 +162,6 @@ def main():
     ap.add_argument("names", nargs="*")
     ap.add_argument("--tu", default="k_fast2")
     ap.add_argument("--flags", default="")
-    ap.add_argument("--stamps", action="store_true")
     ap.add_argument("--no-sched", action="store_true", help="drop the -amdgpu-sched-strategy flag")
     ap.add_argument("--meta", action="store_true", help="print vgpr / spill counts of the unit's kernels")
     ap.add_argument("--grep", default="", help="with --meta: only kernels whose mangled name contains this")
@@ -177,10 +173,10 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--worker", default="")
-    args, extra = ap.parse_known_args()
+    args = ap.parse_args()
     if args.cmd == "build":
         args.name = args.names[0]
-        build(args, extra)
+        build(args)
     elif args.worker:
         worker(args)
     else:
