@@ -32,6 +32,7 @@ extern "C" {
 #define POLAR_ALGO_BP 1    /* BP         BP_1024.c:372-427                     */
 #define POLAR_ALGO_SCL 2   /* SCLdecode  SCL_1024.c:547-680                    */
 #define POLAR_ALGO_CASCL 3 /* CASCL      CASCL_1024_L8.c:601-761               */
+#define POLAR_ALGO_SCF 4   /* CRC-aided SC-Flip (no reference counterpart; polar_scf_set_flips below) */
 
 /* dtype: the arithmetic type the message passing runs in */
 #define POLAR_F64 0 /* IEEE binary64 like the reference: bit-identical decisions (the parity gate) */
@@ -46,7 +47,7 @@ extern "C" {
 
 /* per-frame flags word */
 #define POLAR_FLAG_TIE 0x1u      /* a median tie occurred (reference prints "Oops!", SCL_1024.c:621-622) */
-#define POLAR_FLAG_CRC_PASS 0x2u /* CASCL: the chosen path passed the CRC (CASCL_1024_L8.c:738-746)       */
+#define POLAR_FLAG_CRC_PASS 0x2u /* CASCL: the chosen path passed the CRC (CASCL_1024_L8.c:738-746); SCF: an attempt did */
 #define POLAR_FLAG_RERANK 0x4u   /* diagnostic, no reference counterpart: at some information leaf the high 32 bits of
                                     the 2L candidate metrics did not single out L survivors and the kernel ranked on
                                     the full doubles (f64 list kernels that pre-rank on 32-bit keys; same result either
@@ -104,7 +105,7 @@ void polar_crc_matrix_free(polar_crc_matrix *m);
 /* writes the K x r matrix of g(D) in the reference's encoding, byte for byte what CRC_6.dat holds for K = 64, {0,5,6} */
 int polar_crc_matrix_save(const char *path, int K, const int *taps, int n_taps);
 /* polar_create with r and g(D) taken from such a file (cfg->crc_r / crc_taps / n_taps are ignored; cfg->algo must be
- * POLAR_ALGO_CASCL; cfg->K <= the file's row count).  cfg->crc_systematic = 1 is the encoder the matrix belongs to. */
+ * POLAR_ALGO_CASCL or POLAR_ALGO_SCF; cfg->K <= the file's row count).  cfg->crc_systematic = 1 is the encoder the matrix belongs to. */
 int polar_create_crc_file(const polar_cfg *cfg, const char *path, polar_ctx **out);
 
 /* --- reference-shaped single-frame call -------------------------------------------------------------
@@ -231,6 +232,40 @@ int polar_cascl_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, d
 /* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N]; pm, flags, list (nullable) [B]. */
 int polar_cascl_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, double *pm, unsigned *flags,
                              unsigned *list);
+
+/* --- CRC-aided SC-Flip (Afisiadis, Balatsoukas-Stimming and Burg, 2014) ---------------------------------------------------
+ * A POLAR_ALGO_SCF context takes the cfg of CA-SCL: crc_r >= 1 with its taps (or polar_create_crc_file), crc_systematic
+ * honoured by the generator and the error counters; cfg.L is ignored and reported as 1.  32 <= N <= 2048 (N = 4096:
+ * POLAR_ENOKERNEL).  With A = K + r unfrozen positions I[0..A) (info_order, as for CA-SCL), flip budget T and the dtype's
+ * arithmetic type R, a frame's output is:
+ *   1. attempt 0: the decisions of POLAR_ALGO_SC over I[0..A), the CRC positions decoded as information bits.  lambda_j is
+ *      the leaf LLR that decides u_hat_j (u_hat_j = 1 iff lambda_j < 0).
+ *   2. an attempt passes if XOR over {j : u_hat_j = 1} of crc_tab[j] is 0, crc_tab[I[i]] = D^i mod g(D) (the test of the
+ *      list kernels and of the adaptive rule, systematic or not).
+ *   3. if attempt 0 passes it is the output, attempts = 0.
+ *   4. otherwise the flip list p_1..p_T holds the T positions of I[0..A) with the smallest |lambda_j| of attempt 0, in
+ *      ascending |lambda_j| (fabs in R: +0 == -0), ties to the smaller j.
+ *   5. attempt t (1 <= t <= T) is SC with the decision at leaf p_t inverted (u_hat = 1 - [lambda < 0] there); every later
+ *      leaf uses the inverted bit in its partial sums; nothing else is forced.
+ *   6. the output is the first attempt t that passes (attempts = t, POLAR_FLAG_CRC_PASS set); if none passes, attempt 0
+ *      with attempts = T and POLAR_FLAG_CRC_PASS clear.
+ *   7. the metric (d_pm / pm_out) is 0.0; the flags word is SC's with POLAR_FLAG_CRC_PASS added on a pass.
+ * A frame that passes at attempt 0 is never touched again, so the frames SCF decodes wrongly are a subset of those SC does.
+ * The decoder is honoured by polar_decode, polar_decode_batch(_y) (no frozen_mask override), polar_decode_device,
+ * polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device and polar_kernel_name.  polar_group_* and
+ * polar_fer_multi_gpu build their contexts from a polar_cfg and run SCF with the default T = 8.
+ * The host reads the count of failing frames (one 4-byte copy and a stream sync per decode): a decode while the ctx stream
+ * is capturing a graph returns POLAR_EINVAL.  polar_cascl_set_stages refuses SCF contexts. */
+/* T: 0 <= T <= min(32, K + r); default 8 (min(8, K + r)).  T = 0 is SC plus the CRC flag.  POLAR_EINVAL (ctx unchanged):
+ * not an SCF ctx, or T out of range. */
+int polar_scf_set_flips(polar_ctx *ctx, int T);
+/* polar_decode_device for an SCF ctx, plus per frame d_attempts (nullable) [B]: the attempt that decided it (0 = plain SC;
+ * T when no attempt passed).  d_flags and d_attempts are nullable. */
+int polar_scf_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
+                            uint32_t *d_uhat_bits, uint32_t *d_flags, uint32_t *d_attempts);
+/* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N]; flags, attempts (nullable) [B]. */
+int polar_scf_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *flags,
+                           unsigned *attempts);
 
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at

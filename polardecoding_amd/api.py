@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL = 0, 1, 2, 3
+ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF = 0, 1, 2, 3, 4
 F64, F32 = 0, 1
 FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
 BP_STOP_NONE, BP_STOP_G = 0, 1   # polar_bp_set_stop: iterMax round trips / stop at the first with u_hat F == x_hat
@@ -91,6 +91,9 @@ def load_library(testing=False):
     L.polar_cascl_set_stages.argtypes = [vp, ip, C.c_int]
     L.polar_cascl_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp, vp]
     L.polar_cascl_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, dp, up, up]
+    L.polar_scf_set_flips.argtypes = [vp, C.c_int]
+    L.polar_scf_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
+    L.polar_scf_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
     L.polar_generate_device.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp, C.c_int,
                                         C.c_int, vp]
     L.polar_fer_batch.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, C.POINTER(C.c_ulonglong),
@@ -184,6 +187,7 @@ class Decoder:
         self._cfg, self._cfg_keep = cfg, (taps, io)   # kept for polar_fer_multi_gpu (the arrays the struct points to must stay alive)
         self.bp_stop = BP_STOP_NONE
         self.cascl_stages = ()
+        self.scf_flips = None   # None: the library's default (min(8, K + r))
         self._create()
         A, Lr = C.c_int(), C.c_int()
         self._lib.polar_ctx_info(self._h, None, None, C.byref(A), C.byref(Lr), None, None)
@@ -210,6 +214,8 @@ class Decoder:
             self.set_bp_stop(self.bp_stop)
         if self.cascl_stages:
             self.set_cascl_stages(self.cascl_stages)
+        if self.scf_flips is not None:
+            self.set_scf_flips(self.scf_flips)
 
     @property
     def info_order(self):
@@ -251,6 +257,12 @@ class Decoder:
         self._check(self._lib.polar_cascl_set_stages(self._h, _ptr(st, C.c_int) if st.size else None, int(st.size)),
                     "polar_cascl_set_stages")
         self.cascl_stages = tuple(int(x) for x in st) if st.size > 1 else ()
+
+    def set_scf_flips(self, T):
+        """SC-Flip flip budget (polar_scf_set_flips): up to T single-flip attempts per CRC-failing frame, 0 <= T <=
+        min(32, K + r); T = 0 is SC plus the CRC flag."""
+        self._check(self._lib.polar_scf_set_flips(self._h, int(T)), "polar_scf_set_flips")
+        self.scf_flips = int(T)
 
     @property
     def kernel_name(self):
@@ -380,6 +392,37 @@ class Decoder:
                                                        _ptr(pm, C.c_double), _ptr(fl, C.c_uint), _ptr(ls, C.c_uint)),
                     "polar_cascl_decode_batch")
         return uh, pm, fl, ls
+
+    def decode_scf_device(self, d_in, sigma=0.0, out_bits=None, flags=None, attempts=None):
+        """polar_scf_decode_device: like decode_device, plus per frame the attempt that decided it (`attempts`, int32 [B]:
+        0 = plain SC, T when none passed); flags and attempts are optional tensors.  Returns out_bits."""
+        import torch
+        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
+        B = d_in.numel() // self.N
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        for t in (flags, attempts):
+            if t is not None and (t.numel() < B or t.element_size() != 4 or not t.is_contiguous()):
+                raise ValueError("flags / attempts must be contiguous 32-bit tensors of at least B elements")
+        self._check(self._lib.polar_scf_decode_device(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B, C.c_void_p(out_bits.data_ptr()),
+            C.c_void_p(flags.data_ptr()) if flags is not None else None,
+            C.c_void_p(attempts.data_ptr()) if attempts is not None else None), "polar_scf_decode_device")
+        return out_bits
+
+    def decode_scf_batch(self, llr):
+        """polar_scf_decode_batch: llr [B][N] -> (u_hat [B][N] int32, flags [B] uint32, attempts [B] uint32)."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        B = llr.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        fl = np.zeros(B, dtype=np.uint32)
+        at = np.zeros(B, dtype=np.uint32)
+        self._check(self._lib.polar_scf_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
+                                                     _ptr(fl, C.c_uint), _ptr(at, C.c_uint)), "polar_scf_decode_batch")
+        return uh, fl, at
 
     def decode_bp_batch(self, llr):
         """polar_bp_decode_batch: llr [B][N] -> (u_hat [B][N] int32, iters [B] uint32, flags [B] uint32)."""
@@ -549,6 +592,19 @@ def CASCL(N, K, L=8, crc_taps=CRC24C_TAPS, crc_file=None, stages=None, **kw):
         dec = Decoder(N, K, ALGO_CASCL, L=L, crc_taps=crc_taps, **kw)
     if stages is not None:
         dec.set_cascl_stages(stages)
+    return dec
+
+
+def SCFlip(N, K, T=8, crc_taps=CRC24C_TAPS, crc_file=None, **kw):
+    """CRC-aided SC-Flip (include/polar_hip.h, POLAR_ALGO_SCF): SC over the K + r unfrozen positions; a frame that fails
+    the CRC is decoded again with one of its T least reliable decisions inverted, up to T times, until one passes.
+    ``crc_taps`` / ``crc_file`` / ``systematic`` as for CASCL."""
+    if crc_file is not None:
+        dec = Decoder(N, K, ALGO_SCF, L=1, crc_taps=None, crc_file=crc_file, **kw)
+    else:
+        dec = Decoder(N, K, ALGO_SCF, L=1, crc_taps=crc_taps, **kw)
+    if T != 8:
+        dec.set_scf_flips(T)
     return dec
 
 

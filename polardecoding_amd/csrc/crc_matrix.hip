@@ -168,7 +168,7 @@ int polar_create_crc_file(const polar_cfg *cfg, const char *path, polar_ctx **ou
 {
     if (!cfg || !out) return POLAR_EINVAL;
     *out = nullptr;
-    if (cfg->algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    if (cfg->algo != POLAR_ALGO_CASCL && cfg->algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
     polar_crc_matrix m;
     int rc = polar_crc_matrix_load(path, &m);
     if (rc) return rc;

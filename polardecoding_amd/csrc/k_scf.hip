@@ -1,0 +1,65 @@
+// k_scf.hip -- k_scf_lanes (CRC-aided SC-Flip, scf_lanes.h), k_scf_resolve and their launch code
+#include "polar_host.h"
+#include "scf_lanes.h"
+
+namespace {
+
+template <typename R, typename IN, int MODE>
+int launch_scf_lanes(polar_ctx *c, const polar::ScfParams &P)
+{
+    using Cfg = polar::ScfCfg<R>;
+    auto kern = polar::k_scf_lanes<R, IN, MODE>;
+    int waves = Cfg::WAVES;
+    while (waves > 1 && Cfg::lds_bytes(P.N, P.T, MODE, waves) > (size_t)160 * 1024) waves /= 2;
+    const size_t lds = Cfg::lds_bytes(P.N, P.T, MODE, waves);
+    if (lds > (size_t)160 * 1024) return POLAR_ENOKERNEL;
+    const int threads = 64 * waves;
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    int occ = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
+    if (occ < 1) occ = 1;
+    const long long batches = ((long long)P.B + 63) / 64;
+    int grid = (int)std::min<long long>((batches + waves - 1) / waves, (long long)occ * c->num_cu);
+    if (grid < 1) grid = 1;
+    polar::ScfParams Q = P;
+    int rc = ensure(c, c->scratch, polar::ScLanesCfg<R>::scratch_bytes(P.N) * (size_t)grid * waves);
+    if (rc) return rc;
+    Q.scratch = c->scratch.p;
+    Q.queue = nullptr;
+    if (batches > (long long)grid * waves && (rc = work_queue(c, c->scratch, &Q.queue))) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    return POLAR_OK;
+}
+
+template <int MODE>
+int launch_mode(polar_ctx *c, const polar::ScfParams &P, bool r32, bool in32)
+{
+    if (!r32) return in32 ? launch_scf_lanes<double, float, MODE>(c, P) : launch_scf_lanes<double, double, MODE>(c, P);
+    return in32 ? launch_scf_lanes<float, float, MODE>(c, P) : launch_scf_lanes<float, double, MODE>(c, P);
+}
+
+}  // namespace
+
+int polar_tu::scf_lanes(polar_ctx *c, const polar::ScfParams &P, int mode, bool r32, bool in32)
+{
+    if (P.B <= 0) return POLAR_OK;
+    if (mode == polar::SCF_CHECK) return launch_mode<polar::SCF_CHECK>(c, P, r32, in32);
+    if (mode == polar::SCF_RECORD) return launch_mode<polar::SCF_RECORD>(c, P, r32, in32);
+    return launch_mode<polar::SCF_FLIP>(c, P, r32, in32);
+}
+
+int polar_tu::scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, const uint32_t *d_idx, size_t n,
+                          int T, uint32_t *d_bits, uint32_t *d_flags, uint32_t *d_attempts)
+{
+    if (n == 0) return POLAR_OK;
+    int lw = 0;
+    while ((1 << lw) < c->NW) ++lw;
+    const long long items = (long long)n << lw;
+    const int grid = (int)std::max<long long>(1, std::min<long long>((items + 255) / 256, (long long)c->num_cu * 16));
+    hipLaunchKernelGGL(polar::k_scf_resolve, dim3(grid), dim3(256), 0, c->stream, d_pass, d_pbits, d_idx, (long long)n, T, lw,
+                       d_bits, d_flags, d_attempts);
+    HIP_TRY(c, hipGetLastError());
+    return POLAR_OK;
+}

@@ -17,6 +17,7 @@
 
 #include "count_kernel.h"
 #include "gen_kernel.h"
+#include "scf_params.h"
 
 namespace {
 
@@ -70,6 +71,9 @@ std::vector<uint32_t> make_crc_table(int N, int r, const std::vector<int> &taps,
     }
     return tab;
 }
+
+// contexts whose code carries a CRC: r, crc_tab, the generator's CRC multiply, the systematic K-bit error metric
+bool has_crc(int algo) { return algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF; }
 
 static bool sc_lanes_ok(const polar_ctx *c, size_t B)
 {
@@ -213,11 +217,73 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
     return POLAR_OK;
 }
 
+// CRC-aided SC-Flip (POLAR_ALGO_SCF, include/polar_hip.h).  Pass A decodes every frame with SC and checks its CRC; the
+// frames that fail are compacted in a stable order (the adaptive rule's glue), decoded once more to find their T least
+// reliable information decisions, and pass B runs all T single-flip attempts of every failing frame at once, one lane per
+// (frame, attempt), in chunks of at most 256 MiB of decisions; k_scf_resolve keeps the first attempt that passes.  One
+// 4-byte copy and a stream sync: the failing count.
+int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
+               uint32_t *d_flags, uint32_t *d_attempts)
+{
+    if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the host reads the failing count
+    const int T = c->scf_T, NW = c->NW;
+    const bool r32 = c->cfg.dtype == POLAR_F32, in32 = in_is_f32 != 0;
+    int rc;
+    if (!d_flags) {
+        if ((rc = ensure(c, c->ad_flags, B * sizeof(uint32_t)))) return rc;
+        d_flags = (uint32_t *)c->ad_flags.p;
+    }
+    polar::ScfParams P{};
+    P.in = d_in; P.sigma = sigma; P.out_bits = d_bits; P.pm = d_pm; P.flags = d_flags; P.attempts = d_attempts;
+    P.frozen = c->d_frozen; P.crc_tab = c->d_crc_tab;
+    P.N = c->cfg.N; P.n = c->n; P.B = (int)B; P.T = T;
+    if ((rc = polar_tu::scf_lanes(c, P, polar::SCF_CHECK, r32, in32))) return rc;
+    if (T == 0) return POLAR_OK;
+    if ((rc = ensure(c, c->ad_idx[0], B * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
+    uint32_t *idx = (uint32_t *)c->ad_idx[0].p;
+    if ((rc = polar_tu::ad_compact(c, d_flags, nullptr, B, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p))) return rc;
+    uint32_t h = 0;
+    HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t n = h;
+    if (n == 0) return POLAR_OK;
+    // the flip list of every failing frame: attempt 0 again, its T smallest |lambda_j|
+    if ((rc = ensure(c, c->scf_flips, n * (size_t)T * sizeof(uint16_t)))) return rc;
+    uint16_t *flips = (uint16_t *)c->scf_flips.p;
+    polar::ScfParams R = P;
+    R.out_bits = nullptr; R.pm = nullptr; R.flags = nullptr; R.attempts = nullptr;
+    R.idx = idx; R.flips = flips; R.B = (int)n;
+    if ((rc = polar_tu::scf_lanes(c, R, polar::SCF_RECORD, r32, in32))) return rc;
+    // pass B: frames [off, off + nc) of the list, T pairs each
+    const size_t pair_bytes = (size_t)NW * sizeof(uint32_t);
+    const size_t CH = std::min(n, std::max<size_t>(1, ((size_t)256 << 20) / (pair_bytes * (size_t)T)));
+    if ((rc = ensure(c, c->scf_bits, CH * (size_t)T * pair_bytes))) return rc;
+    if ((rc = ensure(c, c->scf_pass, CH * (size_t)T * sizeof(uint32_t)))) return rc;
+    for (size_t off = 0; off < n; off += CH) {
+        const size_t nc = std::min(CH, n - off);
+        polar::ScfParams F = R;
+        F.idx = idx + off; F.flips = flips + off * (size_t)T; F.B = (int)(nc * (size_t)T);
+        F.out_bits = (uint32_t *)c->scf_bits.p; F.flags = (uint32_t *)c->scf_pass.p;
+        if ((rc = polar_tu::scf_lanes(c, F, polar::SCF_FLIP, r32, in32))) return rc;
+        if ((rc = polar_tu::scf_resolve(c, (uint32_t *)c->scf_pass.p, (uint32_t *)c->scf_bits.p, idx + off, nc, T, d_bits,
+                                        d_flags, d_attempts)))
+            return rc;
+    }
+    return POLAR_OK;
+}
+
 // every decode of the C ABI: the fixed decoder, or for a CA-SCL ctx with a stage rule the adaptive one.
-// d_iters: BP round trips per frame; CA-SCL: the list size that decided each frame.
+// d_iters: BP round trips per frame; CA-SCL: the list size that decided each frame; SC-Flip: the attempt that decided it.
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
 {
+    if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
     if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
         if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
         if (B == 0) return POLAR_OK;
@@ -245,6 +311,9 @@ void refresh_kernel_name(polar_ctx *c)
         snprintf(nm, sizeof nm, "k_sc_lanes<%s> (batches of 64+; k_scl_generic below)", ty);
     if (fast_ok(c, g.dtype == POLAR_F32))
         snprintf(nm, sizeof nm, "k_scl_fast%s<%s,N=%d,L=8>", (g.N == 1024 && c->use_fast4) ? "4" : (g.N == 1024 && c->use_fast2) ? "2" : "", ty, g.N);
+    if (g.algo == POLAR_ALGO_SCF)
+        snprintf(nm, sizeof nm, "k_scf_lanes<%s> (SC-Flip, T=%d; pass A, k_ad_fail_count/scan/write, record, pass B, k_scf_resolve)",
+                 ty, c->scf_T);
     c->kernel_name = nm;
     if (!c->cascl_stages.empty()) {
         sync_stage_ctx(c);
@@ -297,7 +366,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     const int N = c->cfg.N, NW = c->NW;
     const uint32_t *d_frozen = c->d_frozen;
     if (frozen_mask) {
-        if (c->cfg.algo == POLAR_ALGO_CASCL) return POLAR_EINVAL;
+        if (has_crc(c->cfg.algo)) return POLAR_EINVAL;
         std::vector<uint32_t> w = pack_mask(frozen_mask, N, false);
         if (!c->d_frozen_override) HIP_TRY(c, hipMalloc(&c->d_frozen_override, NW * sizeof(uint32_t)));
         HIP_TRY(c, hipMemcpyAsync(c->d_frozen_override, w.data(), NW * sizeof(uint32_t), hipMemcpyHostToDevice,
@@ -475,13 +544,14 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     const int N = cfg->N;
     if (N < 32 || N > 4096 || (N & (N - 1))) return POLAR_EINVAL;
     if (cfg->K < 1 || cfg->crc_r < 0 || cfg->crc_r > 32 || cfg->K + cfg->crc_r > N) return POLAR_EINVAL;
-    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCF) return POLAR_EINVAL;
     if (cfg->dtype != POLAR_F64 && cfg->dtype != POLAR_F32) return POLAR_EINVAL;
     int L = cfg->L;
-    if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP) L = 1;
+    if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF) L = 1;
     if (L < 1 || L > 32 || (L & (L - 1))) return POLAR_EINVAL;
-    if (cfg->algo == POLAR_ALGO_CASCL && (cfg->crc_r < 1 || !cfg->crc_taps || cfg->n_taps < 2)) return POLAR_EINVAL;
+    if (has_crc(cfg->algo) && (cfg->crc_r < 1 || !cfg->crc_taps || cfg->n_taps < 2)) return POLAR_EINVAL;
     if (cfg->algo == POLAR_ALGO_BP && cfg->bp_iters < 1) return POLAR_EINVAL;
+    if (cfg->algo == POLAR_ALGO_SCF && N > 2048) return POLAR_ENOKERNEL;   // one codeword per lane: N <= 2048
 
     polar_ctx *c = new (std::nothrow) polar_ctx();
     if (!c) return POLAR_ENOMEM;
@@ -492,7 +562,7 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     c->logL = 0;
     while ((1 << c->logL) < L) ++c->logL;
     c->NW = N / 32;
-    const int r = (cfg->algo == POLAR_ALGO_CASCL) ? cfg->crc_r : 0;
+    const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
     c->cfg.crc_r = r;
     c->A = cfg->K + r;
     if (r > 0) {
@@ -520,6 +590,7 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
         c->frozen[j] = 0;
     }
     c->h_crc_tab = make_crc_table(N, r, c->taps, c->info_order);
+    c->scf_T = std::min(8, c->A);
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev) {
@@ -601,7 +672,7 @@ void polar_destroy(polar_ctx *c)
     }
     for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
     for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
-                   &c->ad_pm, &c->ad_sflags})
+                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits})
         if (b->p) (void)hipFree(b->p);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
@@ -772,6 +843,28 @@ int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
     c->cascl_stages = n > 1 ? std::vector<int>(stages, stages + n) : std::vector<int>();
     refresh_kernel_name(c);
     return POLAR_OK;
+}
+
+int polar_scf_set_flips(polar_ctx *c, int T)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF || T < 0 || T > polar::SCF_MAX_T || T > c->A) return POLAR_EINVAL;
+    c->scf_T = T;
+    refresh_kernel_name(c);
+    return POLAR_OK;
+}
+
+int polar_scf_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                            uint32_t *d_flags, uint32_t *d_attempts)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, nullptr, d_flags, c->d_frozen, d_attempts);
+}
+
+int polar_scf_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, unsigned *flags, unsigned *attempts)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
+    return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, nullptr, flags, attempts);
 }
 
 int polar_cascl_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
@@ -971,7 +1064,8 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
     // pass of its decode overlap the other half's decode.  Frame i of the batch is the same frame either way
     // (the generator is counter-based), and the two counters are atomics.
     // (not with an adaptive CA-SCL rule: its stage buffers belong to one stream and it syncs between stages)
-    const size_t half = (B >= 32768 && c->cascl_stages.empty()) ? (B / 2 + 63) / 64 * 64 : B;
+    // (nor for SC-Flip, for the same reasons)
+    const size_t half = (B >= 32768 && c->cascl_stages.empty() && c->cfg.algo != POLAR_ALGO_SCF) ? (B / 2 + 63) / 64 * 64 : B;
     if (half < B && !c->stream_b) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming));

@@ -14,6 +14,10 @@
 
 #include "polar_params.h"
 
+namespace polar {
+struct ScfParams;   // scf_params.h
+}
+
 struct PolarBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -47,6 +51,9 @@ struct polar_ctx {
     Buf ad_flags;                         // per-frame flags when the caller passes none
     Buf ad_idx[2], ad_blk, ad_cnt;        // failing-frame lists (ping-pong), compaction block counts, device count
     Buf ad_in, ad_bits, ad_pm, ad_sflags; // a later stage's gathered input and outputs
+    // SC-Flip (POLAR_ALGO_SCF): flip budget T (polar_scf_set_flips), the failing frames' flip positions, pass B's pairs
+    int scf_T = 8;
+    Buf scf_flips, scf_pass, scf_bits;
     Buf in2[2], bits2[2];                 // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
@@ -142,6 +149,10 @@ int ad_compact(polar_ctx *c, const uint32_t *d_flags, const uint32_t *d_idx_in, 
 int ad_gather(polar_ctx *c, const void *d_src, void *d_dst, const uint32_t *d_idx, size_t n, size_t row_bytes);
 int ad_scatter(polar_ctx *c, const uint32_t *s_bits, const double *s_pm, const uint32_t *s_flags, const uint32_t *d_idx,
                size_t n, uint32_t *d_bits, double *d_pm, uint32_t *d_flags, uint32_t *d_list, int L);
+// k_scf.hip: SC-Flip (scf_lanes.h); mode = polar::SCF_CHECK | SCF_RECORD | SCF_FLIP
+int scf_lanes(polar_ctx *c, const polar::ScfParams &P, int mode, bool r32, bool in32);
+int scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, const uint32_t *d_idx, size_t n, int T,
+                uint32_t *d_bits, uint32_t *d_flags, uint32_t *d_attempts);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

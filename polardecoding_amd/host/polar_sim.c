@@ -174,10 +174,11 @@ static const int CRC6[] = {0, 5, 6};
 
 static void usage(void)
 {
-    fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
+    fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
                     "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
-                    "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n");
+                    "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
+                    "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n");
     exit(2);
 }
 
@@ -186,6 +187,7 @@ int main(int argc, char **argv)
     int N = 1024, K = 512, L = 8, algo = POLAR_ALGO_CASCL, ble = 100, batch = 4096, dtype = POLAR_F64, bp_iters = 100;
     int fast = 0, sys = 0, bpr = 0, gpus = 1, bp_stop = POLAR_BP_STOP_NONE;
     int stages[6], nstages = 0;   /* --stages: polar_cascl_set_stages */
+    int flips = -1;               /* --flips: polar_scf_set_flips (-1: the library's default) */
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
     double lo = 1.0, hi = 3.0, step = 0.5;
@@ -198,7 +200,8 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--algo") && v) {
             if (!strcmp(v, "bpr")) { bpr = 1; v = "bp"; bp_iters = 90; }   /* BPr_128.c: iterMax 90 (:16) */
             algo = !strcmp(v, "sc") ? POLAR_ALGO_SC : !strcmp(v, "bp") ? POLAR_ALGO_BP
-                 : !strcmp(v, "scl") ? POLAR_ALGO_SCL : !strcmp(v, "cascl") ? POLAR_ALGO_CASCL : -1;
+                 : !strcmp(v, "scl") ? POLAR_ALGO_SCL : !strcmp(v, "cascl") ? POLAR_ALGO_CASCL
+                 : !strcmp(v, "scf") ? POLAR_ALGO_SCF : -1;
             if (algo < 0) usage();
             i++;
         } else if (!strcmp(a, "--N") && v) { N = atoi(v); i++; }
@@ -232,6 +235,12 @@ int main(int argc, char **argv)
             }
             i++;
         }
+        else if (!strcmp(a, "--flips") && v) {
+            char *end;
+            flips = (int)strtol(v, &end, 10);
+            if (end == v || *end) usage();
+            i++;
+        }
         else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : POLAR_F64; i++; }
         else if (!strcmp(a, "--snr-list") && v) {
             const char *q = v;
@@ -255,7 +264,8 @@ int main(int argc, char **argv)
     c.N = N; c.K = K;
     polar_crc_matrix gcm;
     memset(&gcm, 0, sizeof gcm);
-    if (algo == POLAR_ALGO_CASCL && crcfile) {
+    const int with_crc = algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF;
+    if (with_crc && crcfile) {
         /* g(D) and r come from the generator-matrix file (the reference's CRC_6.dat, or Gc of CASCL_1024_sys.c:48-561 as
            a file); the library has checked that every row is D^(r+i) mod g */
         if (crc) { fprintf(stderr, "--crc and --crc-file exclude each other\n"); return 1; }
@@ -266,7 +276,7 @@ int main(int argc, char **argv)
         memcpy(c.taps, gcm.taps, sizeof(int) * (size_t)c.ntaps);
         c.r = gcm.r;
         c.gc = gcm.rows;
-    } else if (algo == POLAR_ALGO_CASCL) {
+    } else if (with_crc) {
         if (!crc) crc = (N == 128) ? "6" : "24c";
         const int *t = !strcmp(crc, "6") ? CRC6 : CRC24C;
         c.ntaps = !strcmp(crc, "6") ? 3 : 13;
@@ -324,6 +334,12 @@ int main(int argc, char **argv)
         /* a polar_group builds its contexts from cfg and runs the fixed decoder */
         if (fast && gpus > 1) { fprintf(stderr, "--stages: not with --gpus > 1\n"); return 1; }
         if ((rc = polar_cascl_set_stages(ctx, stages, nstages)) != 0) { fprintf(stderr, "--stages: %s\n", polar_strerror(rc)); return 1; }
+    }
+    if (flips >= 0) {
+        /* a polar_group builds its contexts from cfg and runs the default T */
+        if (algo != POLAR_ALGO_SCF) { fprintf(stderr, "--flips: only with --algo scf\n"); return 1; }
+        if (fast && gpus > 1) { fprintf(stderr, "--flips: not with --gpus > 1\n"); return 1; }
+        if ((rc = polar_scf_set_flips(ctx, flips)) != 0) { fprintf(stderr, "--flips: %s\n", polar_strerror(rc)); return 1; }
     }
     /* the library built the frozen set from the 5G sequence like the reference (I[i] = Q[N-(K+r)+i]);
        the encoder needs the same I[] */
@@ -432,7 +448,7 @@ int main(int argc, char **argv)
             }
             printf("BLER = %lfe-2\tBER = %lfe-2\tK * BER = %lf\n", (double)errblock * 100 / run,
                    (double)errbit * 100 / K / run, (double)errbit / run);
-        } else if (algo == POLAR_ALGO_SC || algo == POLAR_ALGO_BP) {
+        } else if (algo == POLAR_ALGO_SC || algo == POLAR_ALGO_BP || (algo == POLAR_ALGO_SCF && !c.sys)) {
             printf("bSNR = %.2lf\terror block = %d\trun = %ld\tBLER = %lf\n", db, errblock, run, (double)errblock / run);
             printf("Error bit = %ld\tBER = %lf\n", errbit, (double)errbit / K / run);
         } else if (c.sys) { /* CASCL_1024_sys.c:832-835 */
