@@ -267,6 +267,63 @@ int polar_scf_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, dou
 int polar_scf_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *flags,
                            unsigned *attempts);
 
+/* --- 5G NR rate matching (TS 38.212 5.4.1; no reference counterpart) -------------------------------------------------
+ * A rate-matched context sends E channel values per codeword instead of N.  Notation of 38.212: A = K + r bits enter the
+ * encoder (r = 0 for SC / BP / SCL), N is the context's block length, 32 <= N <= 1024, A <= E <= 8192, d = u F^{(x)n} is the
+ * codeword.
+ *   1. sub-block interleaver (5.4.1.1): P = {0,1,2,4,3,5,6,7,8,16,9,17,10,18,11,19,12,20,13,21,14,22,15,23,24,25,26,28,27,29,
+ *      30,31}, J(n) = P[floor(32n/N)] (N/32) + (n mod N/32), y_n = d_{J(n)}.
+ *   2. bit selection (5.4.1.2): repetition when E >= N, e_k = y_{k mod N}; else puncturing when 16 A <= 7 E,
+ *      e_k = y_{k+N-E}; else shortening, e_k = y_k.
+ *   3. channel interleaver (5.4.1.3, ibil = 1, the uplink case): T = the least integer with T(T+1)/2 >= E; e is written row
+ *      by row into the upper triangle v_{i,j}, i = 0..T-1, j = 0..T-1-i, NULL after E, and read column by column,
+ *      j = 0..T-1, i = 0..T-1-j, skipping the NULLs.  ibil = 0: the row sent is e.
+ *   4. frozen set (5.3.1.2 with n_PC = 0): Q_F,tmp is empty for E >= N.  Puncturing adds J(n) for n < N-E and then
+ *      {0 .. ceil((3N-2E)/4)-1} if 4E >= 3N, else {0 .. ceil((9N-4E)/16)-1}.  Shortening adds J(n) for E <= n < N.
+ *      I[0..A) = the A most reliable positions of the context's reliability order (the 5G sequence restricted to < N) that
+ *      are not in Q_F,tmp, in ascending reliability: the library's own convention (CRC word w[i] -> u[I[i]]).  The 38.212
+ *      placement of payload and CRC bits inside the information set, the input interleaver (I_IL), PC bits, distributed
+ *      CRC and code-block segmentation are NOT part of this.
+ *   5. N selection (5.3.1), a helper: n1 = ceil(log2 E) - 1 if E <= (9/8) 2^(ceil(log2 E)-1) and 16 A < 9 E, else
+ *      ceil(log2 E); n2 = ceil(log2 (8A)); n = max(min(n1, n2, n_max), 5), n_max = 9 or 10.
+ *   6. recovery (receiver): a row of E received values becomes the N-wide row the decoders read.  The channel interleaver is
+ *      undone (ibil = 1), then the value at decoder position J(n) is: repetition, the sum over k = n (mod N), k < E, in
+ *      ascending k; puncturing, +0.0 for n < N-E and e_{n-(N-E)} otherwise; shortening, e_n for n < E and
+ *      POLAR_RM_SHORT_LLR otherwise.  With sigma > 0 every term is 2*y/sigma/sigma (that order).  Terms are accumulated in
+ *      double and rounded once to the input's type (f32 input gives an f32 row).  POLAR_RM_SHORT_LLR = 2^20 is finite on
+ *      purpose (two infinities meet in g = cL - cU and give NaN), exact in f32, and 2^20 summed over 2^12 leaves stays far
+ *      below FLT_MAX; the table-driven check node clamps by exponent, so large finite values are safe there.
+ *   7. a decode on a rate-matched context IS the decoder of the same cfg with info_order = rule 4, applied to the rule 6 row
+ *      with sigma = 0.  Outputs stay in the u domain, [B][N]: bits, pm, flags, iterations, attempts, error counters.
+ * On a rate-matched context every decode entry point takes rows of E values instead of N (polar_decode,
+ * polar_decode_batch(_y), polar_decode_device, polar_bp_ / polar_cascl_ / polar_scf_decode_device and _batch,
+ * polar_stop_rule_batch_y, polar_time_decode_device); the recovery runs once per call into context-owned scratch (chunks of
+ * at most 256 MiB of recovered rows).  A frozen_mask override and polar_bp_readout_* return POLAR_EINVAL.
+ * polar_generate_device writes [B][E]: the payload stream of a plain context with the same info_order and seed (d_u_bits
+ * equal), encoded, rules 1-3, then BPSK + AWGN with sigma = 10^(-snr_db/20); element t of the sent row takes normal (t & 1) of
+ * Philox(seed, frame, t >> 1, stream 2) by Box-Muller.  polar_fer_batch chains generate -> recover -> decode -> count.
+ * polar_create_crc_file, polar_group_* and polar_fer_multi_gpu take no E.  The recovery scratch grows with B on first use:
+ * warm a context at its largest B before capturing its stream into a graph. */
+#define POLAR_RM_NONE 0      /* ctx not made by polar_create_rm */
+#define POLAR_RM_REPEAT 1
+#define POLAR_RM_PUNCTURE 2
+#define POLAR_RM_SHORTEN 3
+#define POLAR_RM_SHORT_LLR 1048576.0
+/* rule 5: N for (A, E), n_max 9 or 10; POLAR_EINVAL for A < 1, E < A, E > 8192 or another n_max.  Host only. */
+int polar_rm_select_n(int A, int E, int n_max);
+/* rule 4: out[0..A) = I for (N, A, E); POLAR_EINVAL for N not a power of two in 32..1024, A < 1, E < A, E > 8192 or
+ * A > N - |Q_F,tmp|.  Host only, touches no device. */
+int polar_rm_info_order(int N, int A, int E, int *out);
+/* polar_create with info_order = rule 4 for E and a channel interleaver if ibil = 1.  Refuses (POLAR_EINVAL, before any
+ * device is touched) a non-NULL cfg->info_order, N outside 32..1024, E < A, E > 8192, ibil not 0 / 1 and
+ * A > N - |Q_F,tmp|; every algo and dtype is accepted.  polar_info_order returns the rate-matched order. */
+int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out);
+/* E, POLAR_RM_* mode and ibil of a ctx (each nullable); a plain ctx reports E = N, POLAR_RM_NONE, 0. */
+int polar_rm_info(const polar_ctx *ctx, int *E, int *mode, int *ibil);
+/* rule 6 on the ctx stream: d_in [B][E] double (in_is_f32 = 0) or float, LLRs or y when sigma > 0 -> d_out [B][N] of the
+ * same type.  POLAR_EINVAL on a ctx not made by polar_create_rm. */
+int polar_rm_recover_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, void *d_out);
+
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at
  * Eb/N0 = snr_db (sigma = 10^(-snr_db/20), rate 1/2 as in the reference, :237) -> d_out[B][N] (double, or float

@@ -17,6 +17,8 @@ import numpy as np
 ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF = 0, 1, 2, 3, 4
 F64, F32 = 0, 1
 FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
+RM_NONE, RM_REPEAT, RM_PUNCTURE, RM_SHORTEN = 0, 1, 2, 3   # polar_rm_info modes (5G rate matching)
+RM_SHORT_LLR = 1048576.0   # POLAR_RM_SHORT_LLR: the recovered value at a shortened position
 BP_STOP_NONE, BP_STOP_G = 0, 1   # polar_bp_set_stop: iterMax round trips / stop at the first with u_hat F == x_hat
 _BP_STOP_RULES = {None: BP_STOP_NONE, "none": BP_STOP_NONE, "g": BP_STOP_G, BP_STOP_NONE: BP_STOP_NONE, BP_STOP_G: BP_STOP_G}
 CRC6_TAPS = (0, 5, 6)  # g(D) = D^6 + D^5 + 1 (CASCL_128.c:3)
@@ -115,6 +117,11 @@ def load_library(testing=False):
                                            C.POINTER(C.c_float)]
     L.polar_ctx_info.argtypes = [vp, ip, ip, ip, ip, ip, ip]
     L.polar_info_order.argtypes = [vp, ip, C.c_int]
+    L.polar_rm_select_n.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.polar_rm_info_order.argtypes = [C.c_int, C.c_int, C.c_int, ip]
+    L.polar_create_rm.argtypes = [C.POINTER(_Cfg), C.c_int, C.c_int, C.POINTER(vp)]
+    L.polar_rm_info.argtypes = [vp, ip, ip, ip]
+    L.polar_rm_recover_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -162,12 +169,35 @@ def _ptr(a, ty):
     return a.ctypes.data_as(C.POINTER(ty))
 
 
+def rm_select_n(A, E, n_max=10):
+    """polar_rm_select_n: the block length 38.212 5.3.1 picks for A = K + r encoder bits sent as E values."""
+    lib = load_library()
+    rc = lib.polar_rm_select_n(int(A), int(E), int(n_max))
+    if rc < 0:
+        raise PolarError(f"polar_rm_select_n({A}, {E}, {n_max}): {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return rc
+
+
+def rm_info_order(N, A, E):
+    """polar_rm_info_order: I[0..A) of the rate-matched frozen set (include/polar_hip.h rule 4), ascending reliability."""
+    lib = load_library()
+    out = np.zeros(max(int(A), 1), dtype=np.int32)
+    rc = lib.polar_rm_info_order(int(N), int(A), int(E), _ptr(out, C.c_int))
+    if rc != 0:
+        raise PolarError(f"polar_rm_info_order({N}, {A}, {E}): {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return out[:int(A)]
+
+
 class Decoder:
     """One polar_ctx: a (N, K, CRC, L, algo, dtype) configuration bound to one GPU."""
 
     def __init__(self, N, K, algo, L=1, crc_taps=None, bp_iters=100, dtype=F64, device=0, info_order=None,
-                 systematic=False, crc_file=None, _library=None):
+                 systematic=False, crc_file=None, E=None, ibil=False, _library=None):
+        """E: 5G rate matching (polar_create_rm): every decode takes rows of E channel values and generate_device writes
+        them; ibil: with the channel interleaver (uplink)."""
         self._h = C.c_void_p()
+        if E is not None and crc_file is not None:
+            raise ValueError("E (rate matching) and crc_file exclude each other: polar_create_crc_file takes no E")
         self._lib = _library if _library is not None else load_library()
         self.N, self.K, self.algo, self.dtype, self.device = N, K, algo, dtype, device
         taps = np.asarray(list(crc_taps) if crc_taps else [0], dtype=np.int32)
@@ -188,14 +218,21 @@ class Decoder:
         self.bp_stop = BP_STOP_NONE
         self.cascl_stages = ()
         self.scf_flips = None   # None: the library's default (min(8, K + r))
+        self._rm = (int(E), 1 if ibil else 0) if E is not None else None
         self._create()
         A, Lr = C.c_int(), C.c_int()
         self._lib.polar_ctx_info(self._h, None, None, C.byref(A), C.byref(Lr), None, None)
         self.A, self.L = A.value, Lr.value
         self.NW = N // 32
+        e, mode, il = C.c_int(), C.c_int(), C.c_int()
+        self._lib.polar_rm_info(self._h, C.byref(e), C.byref(mode), C.byref(il))
+        self.E, self.rm_mode, self.ibil = e.value, mode.value, bool(il.value)   # plain: E = N, RM_NONE
+        self._w = self.E   # values per input row of every decode entry point
 
     def _create(self):
-        if self._crc_file is not None:
+        if self._rm is not None:
+            rc = self._lib.polar_create_rm(C.byref(self._cfg), self._rm[0], self._rm[1], C.byref(self._h))
+        elif self._crc_file is not None:
             rc = self._lib.polar_create_crc_file(C.byref(self._cfg), self._crc_file, C.byref(self._h))
         else:
             rc = self._lib.polar_create(C.byref(self._cfg), C.byref(self._h))
@@ -268,12 +305,24 @@ class Decoder:
     def kernel_name(self):
         return self._lib.polar_kernel_name(self._h).decode()
 
+    def _rows(self, x):
+        """host rows of this decoder's width (N, or E on a rate-matched decoder) as float64 [B][width]"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim == 0 or x.shape[-1] != self._w:
+            raise ValueError(f"rows must have {self._w} values (shape [B][{self._w}])")
+        return x.reshape(-1, self._w)
+
+    def _dev_rows(self, d):
+        if not (d.is_cuda and d.is_contiguous()) or d.dim() == 0 or d.shape[-1] != self._w:
+            raise ValueError(f"device rows must be a contiguous CUDA tensor of shape [B][{self._w}]")
+        return d.numel() // self._w
+
     # ---- host buffers -------------------------------------------------------------------------------
     def __call__(self, y, sigma):
         """Reference call shape: channel observations y[N] and sigma (the global ``std``) -> u_hat[N]."""
         y = np.ascontiguousarray(y, dtype=np.float64)
-        if y.shape != (self.N,):
-            raise ValueError(f"y must have shape ({self.N},)")
+        if y.shape != (self._w,):
+            raise ValueError(f"y must have shape ({self._w},)")
         uh = np.empty(self.N, dtype=np.int32)
         self._check(self._lib.polar_decode(self._h, _ptr(y, C.c_double), float(sigma), _ptr(uh, C.c_int)),
                     "polar_decode")
@@ -282,7 +331,7 @@ class Decoder:
     def decode_batch(self, llr, frozen_mask=None, want_pm=True, out=None):
         """out: optional int32 [B][N] array to receive u_hat (a caller that keeps its buffers, as the reference does, pays
         no page faults for a fresh half-gigabyte array per call)."""
-        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        llr = self._rows(llr)
         B = llr.shape[0]
         if out is not None:
             if out.dtype != np.int32 or out.shape != (B, self.N) or not out.flags["C_CONTIGUOUS"]:
@@ -302,7 +351,7 @@ class Decoder:
         return uh, pm, fl
 
     def decode_batch_y(self, y, sigma):
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, self.N)
+        y = self._rows(y)
         B = y.shape[0]
         uh = np.empty((B, self.N), dtype=np.int32)
         pm = np.zeros(B, dtype=np.float64)
@@ -323,8 +372,7 @@ class Decoder:
         """d_in: torch CUDA tensor [B][N] float64 or float32 (LLRs, or y if sigma > 0).
         Returns out_bits: int32 tensor [B][N/32] (bit j&31 of word j>>5 = u_hat[j])."""
         import torch
-        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
-        B = d_in.numel() // self.N
+        B = self._dev_rows(d_in)
         if out_bits is None:
             out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
         f32 = 1 if d_in.dtype == torch.float32 else 0
@@ -340,8 +388,7 @@ class Decoder:
         """polar_bp_decode_device: like decode_device, plus per frame the round trips run (`iters`, int32 [B]) and
         FLAG_BP_CONVERGED (`flags`, int32 [B]); both optional tensors.  Returns out_bits."""
         import torch
-        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
-        B = d_in.numel() // self.N
+        B = self._dev_rows(d_in)
         if out_bits is None:
             out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
         f32 = 1 if d_in.dtype == torch.float32 else 0
@@ -360,8 +407,7 @@ class Decoder:
         """polar_cascl_decode_device: like decode_device, plus per frame the list size of the stage that decided it
         (`list_size`, int32 [B], 1 = SC); pm (float64 [B]), flags and list_size are optional tensors.  Returns out_bits."""
         import torch
-        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
-        B = d_in.numel() // self.N
+        B = self._dev_rows(d_in)
         if out_bits is None:
             out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
         f32 = 1 if d_in.dtype == torch.float32 else 0
@@ -382,7 +428,7 @@ class Decoder:
     def decode_cascl_batch(self, llr):
         """polar_cascl_decode_batch: llr [B][N] -> (u_hat [B][N] int32, pm [B] float64, flags [B] uint32,
         list size [B] uint32)."""
-        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        llr = self._rows(llr)
         B = llr.shape[0]
         uh = np.empty((B, self.N), dtype=np.int32)
         pm = np.zeros(B, dtype=np.float64)
@@ -397,8 +443,7 @@ class Decoder:
         """polar_scf_decode_device: like decode_device, plus per frame the attempt that decided it (`attempts`, int32 [B]:
         0 = plain SC, T when none passed); flags and attempts are optional tensors.  Returns out_bits."""
         import torch
-        assert d_in.is_cuda and d_in.is_contiguous() and d_in.shape[-1] == self.N
-        B = d_in.numel() // self.N
+        B = self._dev_rows(d_in)
         if out_bits is None:
             out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
         f32 = 1 if d_in.dtype == torch.float32 else 0
@@ -415,7 +460,7 @@ class Decoder:
 
     def decode_scf_batch(self, llr):
         """polar_scf_decode_batch: llr [B][N] -> (u_hat [B][N] int32, flags [B] uint32, attempts [B] uint32)."""
-        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        llr = self._rows(llr)
         B = llr.shape[0]
         uh = np.empty((B, self.N), dtype=np.int32)
         fl = np.zeros(B, dtype=np.uint32)
@@ -426,7 +471,7 @@ class Decoder:
 
     def decode_bp_batch(self, llr):
         """polar_bp_decode_batch: llr [B][N] -> (u_hat [B][N] int32, iters [B] uint32, flags [B] uint32)."""
-        llr = np.ascontiguousarray(llr, dtype=np.float64).reshape(-1, self.N)
+        llr = self._rows(llr)
         B = llr.shape[0]
         uh = np.empty((B, self.N), dtype=np.int32)
         it = np.zeros(B, dtype=np.uint32)
@@ -436,10 +481,10 @@ class Decoder:
         return uh, it, fl
 
     def generate_device(self, seed, first_frame, snr_db, out, u_bits=None, out_is_y=False):
-        """Device-side transmit chain (throughput mode): fills `out` [B][N] (float64/float32 LLRs, or y) and
-        `u_bits` [B][N/32] int32 for frames first_frame .. first_frame + B - 1 of stream `seed`."""
+        """Device-side transmit chain (throughput mode): fills `out` [B][N] ([B][E] on a rate-matched decoder; float64/float32
+        LLRs, or y) and `u_bits` [B][N/32] int32 for frames first_frame .. first_frame + B - 1 of stream `seed`."""
         import torch
-        B = out.numel() // self.N
+        B = self._dev_rows(out) if self.rm_mode != RM_NONE else out.numel() // self.N
         self._check(self._lib.polar_generate_device(
             self._h, int(seed), int(first_frame), float(snr_db), B, C.c_void_p(out.data_ptr()),
             1 if out.dtype == torch.float32 else 0, 1 if out_is_y else 0,
@@ -479,7 +524,7 @@ class Decoder:
     def stop_rule_batch_y(self, y, sigma, u, need, min_frames=0):
         """One batch of main()'s loop on host buffers: y [B][N] observations, u [B][N] sent bits (0/1).  Returns
         (frames consumed, block errors, bit errors) under the stop rule with `need` block errors still missing."""
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, self.N)
+        y = self._rows(y)
         ub = np.packbits(np.ascontiguousarray(u, dtype=np.uint8).reshape(-1, self.N), axis=1, bitorder="little")
         ub = np.ascontiguousarray(ub).view(np.uint32)
         used, blk, bits = C.c_size_t(0), C.c_ulonglong(0), C.c_ulonglong(0)
@@ -501,12 +546,29 @@ class Decoder:
 
     def time_decode_device(self, d_in, out_bits, reps, sigma=0.0):
         import torch
-        B = d_in.numel() // self.N
+        B = d_in.numel() // self._w
         ms = C.c_float()
         self._check(self._lib.polar_time_decode_device(
             self._h, C.c_void_p(d_in.data_ptr()), 1 if d_in.dtype == torch.float32 else 0, float(sigma), B,
             C.c_void_p(out_bits.data_ptr()), int(reps), C.byref(ms)), "polar_time_decode_device")
         return ms.value
+
+    def rm_recover_device(self, d_in, sigma=0.0, out=None):
+        """polar_rm_recover_device (rate-matched decoders): d_in [B][E] float64/float32 LLRs (or y with sigma > 0) -> the
+        [B][N] rows of the same dtype that the decoder reads (include/polar_hip.h rule 6).  Asynchronous on the ctx stream."""
+        import torch
+        if self.rm_mode == RM_NONE:
+            raise PolarError("rm_recover_device: not a rate-matched decoder (pass E=...)")
+        B = self._dev_rows(d_in)
+        if d_in.dtype not in (torch.float64, torch.float32):
+            raise ValueError("input must be float64 or float32")
+        if out is None:
+            out = torch.empty((B, self.N), dtype=d_in.dtype, device=d_in.device)
+        if out.dtype != d_in.dtype or not out.is_contiguous() or out.numel() < B * self.N:
+            raise ValueError("out must be a contiguous tensor of the input's dtype with B * N elements")
+        self._check(self._lib.polar_rm_recover_device(self._h, C.c_void_p(d_in.data_ptr()), 1 if d_in.dtype == torch.float32 else 0,
+                                                      float(sigma), B, C.c_void_p(out.data_ptr())), "polar_rm_recover_device")
+        return out
 
     def synchronize(self):
         self._check(self._lib.polar_synchronize(self._h), "polar_synchronize")

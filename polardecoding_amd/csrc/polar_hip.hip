@@ -75,6 +75,61 @@ std::vector<uint32_t> make_crc_table(int N, int r, const std::vector<int> &taps,
 // contexts whose code carries a CRC: r, crc_tab, the generator's CRC multiply, the systematic K-bit error metric
 bool has_crc(int algo) { return algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF; }
 
+// ---- 5G rate matching, host side (include/polar_hip.h rules 1-5) ----
+const int kRmP[32] = {0, 1, 2, 4, 3, 5, 6, 7, 8, 16, 9, 17, 10, 18, 11, 19, 12, 20, 13, 21, 14, 22, 15, 23, 24, 25, 26, 28, 27, 29, 30, 31};
+
+int rm_J(int N, int n) { return kRmP[n / (N / 32)] * (N / 32) + n % (N / 32); }   // rule 1
+
+bool rm_args_ok(int N, int A, int E)
+{
+    return N >= 32 && N <= 1024 && !(N & (N - 1)) && A >= 1 && E >= A && E <= 8192;
+}
+
+int rm_mode_of(int N, int A, int E)   // rule 2
+{
+    if (E >= N) return POLAR_RM_REPEAT;
+    return (16 * A <= 7 * E) ? POLAR_RM_PUNCTURE : POLAR_RM_SHORTEN;
+}
+
+// rule 4: I[0..A) in ascending reliability; POLAR_EINVAL if fewer than A positions are left
+int rm_order(int N, int A, int E, std::vector<int> &I)
+{
+    if (!rm_args_ok(N, A, E)) return POLAR_EINVAL;
+    std::vector<unsigned char> pre((size_t)N, 0);   // Q_F,tmp
+    const int mode = rm_mode_of(N, A, E);
+    if (mode == POLAR_RM_PUNCTURE) {
+        for (int n = 0; n < N - E; ++n) pre[(size_t)rm_J(N, n)] = 1;
+        const int t = (4 * E >= 3 * N) ? (3 * N - 2 * E + 3) / 4 : (9 * N - 4 * E + 15) / 16;
+        for (int i = 0; i < t; ++i) pre[(size_t)i] = 1;
+    } else if (mode == POLAR_RM_SHORTEN) {
+        for (int n = E; n < N; ++n) pre[(size_t)rm_J(N, n)] = 1;
+    }
+    const std::vector<int> q = default_order(N);
+    I.clear();
+    for (int i = N - 1; i >= 0 && (int)I.size() < A; --i)
+        if (!pre[(size_t)q[(size_t)i]]) I.push_back(q[(size_t)i]);
+    if ((int)I.size() < A) return POLAR_EINVAL;
+    std::reverse(I.begin(), I.end());
+    return POLAR_OK;
+}
+
+// rule 3: pos[k] = position of e_k in the sent row (triangle written by rows, read by columns, NULLs skipped)
+std::vector<uint16_t> rm_channel_ilv(int E)
+{
+    int T = 0;
+    while (T * (T + 1) / 2 < E) ++T;
+    std::vector<int> kat((size_t)T * T, -1);   // e index at (i, j), -1 = NULL
+    int k = 0;
+    for (int i = 0; i < T; ++i)
+        for (int j = 0; j < T - i; ++j, ++k) kat[(size_t)i * T + j] = k < E ? k : -1;
+    std::vector<uint16_t> pos((size_t)E);
+    int t = 0;
+    for (int j = 0; j < T; ++j)
+        for (int i = 0; i < T - j; ++i)
+            if (kat[(size_t)i * T + j] >= 0) pos[(size_t)kat[(size_t)i * T + j]] = (uint16_t)t++;
+    return pos;
+}
+
 static bool sc_lanes_ok(const polar_ctx *c, size_t B)
 {
     return c->cfg.algo == POLAR_ALGO_SC && !c->force_generic && c->cfg.N <= 2048 && B >= 64;
@@ -278,10 +333,10 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     return POLAR_OK;
 }
 
-// every decode of the C ABI: the fixed decoder, or for a CA-SCL ctx with a stage rule the adaptive one.
+// the decoder of ctx c on N-wide rows: the fixed decoder, or for a CA-SCL ctx with a stage rule the adaptive one, or SC-Flip.
 // d_iters: BP round trips per frame; CA-SCL: the list size that decided each frame; SC-Flip: the attempt that decided it.
-int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
-                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
+int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
+                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters)
 {
     if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
     if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
@@ -292,6 +347,32 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
         d_iters = nullptr;
     }
     return decode_fixed(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters);
+}
+
+// every decode of the C ABI.  On a rate-matched ctx (polar_create_rm) the rows hold E values: k_rm_recover turns them into
+// N-wide rows of the input type in ctx scratch (chunks of at most 256 MiB), which the ctx's own decoder reads with sigma = 0
+// (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (polar_fer_batch swaps it with rm_rows_b).
+int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
+                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
+{
+    if (!c || c->rm_mode == POLAR_RM_NONE) return decode_device_plain(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters);
+    const size_t esz = in_is_f32 ? 4 : 8;
+    if (!d_in || !d_bits || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    const size_t row = (size_t)c->cfg.N * esz;
+    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
+    int rc;
+    if ((rc = ensure(c, c->rm_rows, CH * row))) return rc;
+    for (size_t off = 0; off < B; off += CH) {
+        const size_t nc = std::min(CH, B - off);
+        if ((rc = polar_tu::rm_recover(c, (const char *)d_in + off * (size_t)c->rm_E * esz, in_is_f32 != 0, sigma, nc,
+                                       c->rm_rows.p)))
+            return rc;
+        if ((rc = decode_device_plain(c, c->rm_rows.p, in_is_f32, 0.0, nc, d_bits + off * (size_t)c->NW, d_pm ? d_pm + off : nullptr,
+                                      d_flags ? d_flags + off : nullptr, d_frozen, d_iters ? d_iters + off : nullptr)))
+            return rc;
+    }
+    return POLAR_OK;
 }
 
 // the kernel instantiation decode_device_impl will launch for this ctx (mirrors its choices)
@@ -326,6 +407,7 @@ void refresh_kernel_name(polar_ctx *c)
         a += "; glue k_ad_crc_check, k_ad_fail_count/scan/write, k_ad_gather, k_ad_scatter";
         c->kernel_name = a;
     }
+    if (c->rm_mode != POLAR_RM_NONE) c->kernel_name = "k_rm_recover, then " + c->kernel_name;
 }
 
 std::vector<uint32_t> pack_mask(const unsigned char *m, int N, bool invert)
@@ -364,9 +446,10 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     const int N = c->cfg.N, NW = c->NW;
+    const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : N;   // values per input row
     const uint32_t *d_frozen = c->d_frozen;
     if (frozen_mask) {
-        if (has_crc(c->cfg.algo)) return POLAR_EINVAL;
+        if (has_crc(c->cfg.algo) || c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
         std::vector<uint32_t> w = pack_mask(frozen_mask, N, false);
         if (!c->d_frozen_override) HIP_TRY(c, hipMalloc(&c->d_frozen_override, NW * sizeof(uint32_t)));
         HIP_TRY(c, hipMemcpyAsync(c->d_frozen_override, w.data(), NW * sizeof(uint32_t), hipMemcpyHostToDevice,
@@ -385,7 +468,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     // asynchronous DMA.
     // chunk: 16384 frames, but at most 128 MiB of input (N = 1024: 16384 frames; N = 4096: 4096), so that the two pinned
     // staging buffers and the two device buffers stay at 256 MiB each whatever the block length
-    const size_t CH = std::max<size_t>(256, std::min<size_t>(16384, ((size_t)128 << 20) / ((size_t)N * sizeof(double))));
+    const size_t CH = std::max<size_t>(256, std::min<size_t>(16384, ((size_t)128 << 20) / ((size_t)W * sizeof(double))));
     // Chunk boundaries.  Big batches ramp up and down (CH/8, CH/4, CH/2, CH ... CH, CH/2, CH/4, CH/8): nothing overlaps the
     // staging of the first chunk nor the copy-out and unpacking of the last one, so those two are small.
     std::vector<size_t> off{0};
@@ -410,7 +493,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     const size_t nch = off.size() - 1;
     const size_t chf = std::min(B, CH);
     for (int i = 0; i < 2; ++i) {
-        if ((rc = ensure(c, c->in2[i], chf * N * sizeof(double)))) return rc;
+        if ((rc = ensure(c, c->in2[i], chf * W * sizeof(double)))) return rc;
         if ((rc = ensure(c, c->bits2[i], chf * NW * sizeof(uint32_t)))) return rc;
     }
     if (c->h_bits_cap < chf * NW * sizeof(uint32_t)) {
@@ -431,23 +514,23 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         }
     }
     const bool staged = nch >= 3;
-    if (staged && c->h_in_cap < chf * N * sizeof(double)) {
+    if (staged && c->h_in_cap < chf * W * sizeof(double)) {
         c->h_in_cap = 0;
         for (int i = 0; i < 2; ++i) {
             if (c->h_in[i]) HIP_TRY(c, hipHostFree(c->h_in[i]));
             c->h_in[i] = nullptr;
-            HIP_TRY(c, hipHostMalloc((void **)&c->h_in[i], chf * N * sizeof(double), hipHostMallocDefault));
+            HIP_TRY(c, hipHostMalloc((void **)&c->h_in[i], chf * W * sizeof(double), hipHostMallocDefault));
         }
-        c->h_in_cap = chf * N * sizeof(double);
+        c->h_in_cap = chf * W * sizeof(double);
     }
     auto stage_chunk = [&](size_t k) {    // caller's rows of chunk k -> pinned h_in[k & 1], four threads
         const size_t f0 = off[k], nf = off[k + 1] - off[k];
-        const double *src = in + f0 * (size_t)N;
+        const double *src = in + f0 * (size_t)W;
         double *dst = c->h_in[k & 1];
         const unsigned nthr = HOST_THREADS;
         auto part = [=](unsigned t) {
             const size_t a = nf * t / nthr, b = nf * (t + 1) / nthr;
-            std::memcpy(dst + a * (size_t)N, src + a * (size_t)N, (b - a) * (size_t)N * sizeof(double));
+            std::memcpy(dst + a * (size_t)W, src + a * (size_t)W, (b - a) * (size_t)W * sizeof(double));
         };
         std::vector<std::thread> pool;
         for (unsigned t = 1; t < nthr; ++t) pool.emplace_back(part, t);
@@ -479,14 +562,14 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         const size_t f0 = off[k], nf = off[k + 1] - off[k];
         // the decode of chunk k-2 must be done with in2[s] before it is overwritten
         if (k >= 2 && hipStreamWaitEvent(c->copy_stream, c->ev_free[s], 0) != hipSuccess) return fail_join(POLAR_EDEVICE);
-        const double *h_src = in + f0 * (size_t)N;
+        const double *h_src = in + f0 * (size_t)W;
         if (staged) {
             // h_in[s] was the source of chunk k-2's DMA: that copy must have left it (ev_in[s] is recorded behind it)
             if (k >= 2 && hipEventSynchronize(c->ev_in[s]) != hipSuccess) return fail_join(POLAR_EDEVICE);
             stage_chunk(k);
             h_src = c->h_in[s];
         }
-        if (hipMemcpyAsync(c->in2[s].p, h_src, nf * N * sizeof(double), hipMemcpyHostToDevice,
+        if (hipMemcpyAsync(c->in2[s].p, h_src, nf * W * sizeof(double), hipMemcpyHostToDevice,
                            c->copy_stream) != hipSuccess) return fail_join(POLAR_EDEVICE);
         if (hipEventRecord(c->ev_in[s], c->copy_stream) != hipSuccess) return fail_join(POLAR_EDEVICE);
         if (hipStreamWaitEvent(c->stream, c->ev_in[s], 0) != hipSuccess) return fail_join(POLAR_EDEVICE);
@@ -672,7 +755,7 @@ void polar_destroy(polar_ctx *c)
     }
     for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
     for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
-                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits})
+                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->rm_rows, &c->rm_rows_b})
         if (b->p) (void)hipFree(b->p);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
@@ -683,6 +766,8 @@ void polar_destroy(polar_ctx *c)
     if (c->d_frozen_override) (void)hipFree(c->d_frozen_override);
     if (c->d_info_order) (void)hipFree(c->d_info_order);
     if (c->d_gc_rows) (void)hipFree(c->d_gc_rows);
+    if (c->d_rm_ilv) (void)hipFree(c->d_rm_ilv);
+    if (c->d_rm_ilv_inv) (void)hipFree(c->d_rm_ilv_inv);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -732,6 +817,86 @@ int polar_info_order(const polar_ctx *c, int *out, int n)
 }
 
 const char *polar_kernel_name(const polar_ctx *c) { return c ? c->kernel_name.c_str() : ""; }
+
+// ---- 5G rate matching (include/polar_hip.h) ----------------------------------------------------------------------------
+int polar_rm_select_n(int A, int E, int n_max)
+{
+    if (A < 1 || E < A || E > 8192 || (n_max != 9 && n_max != 10)) return POLAR_EINVAL;
+    int cl = 0;   // ceil(log2 E)
+    while ((1 << cl) < E) ++cl;
+    const int n1 = (cl >= 1 && 8ll * E <= 9ll * (1ll << (cl - 1)) && 16ll * A < 9ll * E) ? cl - 1 : cl;
+    int n2 = 0;   // ceil(log2 8A)
+    while ((1ll << n2) < 8ll * A) ++n2;
+    return 1 << std::max(std::min(std::min(n1, n2), n_max), 5);
+}
+
+int polar_rm_info_order(int N, int A, int E, int *out)
+{
+    if (!out) return POLAR_EINVAL;
+    std::vector<int> I;
+    const int rc = rm_order(N, A, E, I);
+    if (rc) return rc;
+    std::copy(I.begin(), I.end(), out);
+    return POLAR_OK;
+}
+
+int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out)
+{
+    if (!cfg || !out) return POLAR_EINVAL;
+    *out = nullptr;
+    if (cfg->info_order || (ibil != 0 && ibil != 1)) return POLAR_EINVAL;
+    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCF) return POLAR_EINVAL;
+    const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
+    if (cfg->K < 1 || r < 0 || r > 32) return POLAR_EINVAL;
+    const int N = cfg->N, A = cfg->K + r;
+    std::vector<int> I;
+    if (rm_order(N, A, E, I)) return POLAR_EINVAL;   // N, E and A > N - |Q_F,tmp|
+    polar_cfg g = *cfg;
+    g.info_order = I.data();
+    polar_ctx *c = nullptr;
+    int rc = polar_create(&g, &c);
+    if (rc) return rc;
+    c->rm_E = E;
+    c->rm_mode = rm_mode_of(N, A, E);
+    c->rm_ibil = ibil;
+    if (ibil) {
+        const std::vector<uint16_t> pos = rm_channel_ilv(E);
+        std::vector<uint16_t> inv((size_t)E);
+        for (int k = 0; k < E; ++k) inv[pos[(size_t)k]] = (uint16_t)k;
+        DeviceGuard guard(cfg->device);
+        const size_t bytes = (size_t)E * sizeof(uint16_t);
+        if (hipMalloc(&c->d_rm_ilv, bytes) != hipSuccess || hipMalloc(&c->d_rm_ilv_inv, bytes) != hipSuccess) {
+            polar_destroy(c);
+            return POLAR_ENOMEM;
+        }
+        if (hipMemcpy(c->d_rm_ilv, pos.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(c->d_rm_ilv_inv, inv.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            polar_destroy(c);
+            return POLAR_EDEVICE;
+        }
+    }
+    refresh_kernel_name(c);
+    *out = c;
+    return POLAR_OK;
+}
+
+int polar_rm_info(const polar_ctx *c, int *E, int *mode, int *ibil)
+{
+    if (!c) return POLAR_EINVAL;
+    if (E) *E = c->rm_mode != POLAR_RM_NONE ? c->rm_E : c->cfg.N;
+    if (mode) *mode = c->rm_mode;
+    if (ibil) *ibil = c->rm_ibil;
+    return POLAR_OK;
+}
+
+int polar_rm_recover_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, void *d_out)
+{
+    if (!c || c->rm_mode == POLAR_RM_NONE || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    const size_t esz = in_is_f32 ? 4 : 8;
+    if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) % esz) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return polar_tu::rm_recover(c, d_in, in_is_f32 != 0, sigma, B, d_out);
+}
 
 int polar_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                         double *d_pm, uint32_t *d_flags)
@@ -903,6 +1068,7 @@ int polar_bp_readout_device(polar_ctx *c, const void *d_in, int in_is_f32, doubl
     if (!c || !d_in || !d_u_bits || !checkpoints || !d_E) return POLAR_EINVAL;
     if (c->cfg.algo != POLAR_ALGO_BP || ncp < 1 || ncp > 8 || B > 0x7fffffffull) return POLAR_EINVAL;
     if (c->bp_stop != POLAR_BP_STOP_NONE) return POLAR_EINVAL;   // the checkpoints need every frame to run all round trips
+    if (c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     polar::BpReadoutParams P{};
@@ -922,7 +1088,7 @@ int polar_bp_readout_batch(polar_ctx *c, const double *in, double sigma, size_t 
                            int ncp, unsigned long long *E, int *u_hat)
 {
     if (!c || !in || !u || !checkpoints || !E) return POLAR_EINVAL;
-    if (ncp < 1 || ncp > 8 || c->bp_stop != POLAR_BP_STOP_NONE) return POLAR_EINVAL;
+    if (ncp < 1 || ncp > 8 || c->bp_stop != POLAR_BP_STOP_NONE || c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     const int N = c->cfg.N, NW = c->NW, n = c->n;
@@ -991,15 +1157,16 @@ int polar_stop_rule_batch_y(polar_ctx *c, const double *y, double sigma, const u
     if (B == 0) return POLAR_OK;
     if (B > 0x7fffffffull) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
-    const int N = c->cfg.N, NW = c->NW;
+    const int NW = c->NW;
+    const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : c->cfg.N;   // values per row
     int rc;
-    if ((rc = ensure(c, c->in, B * N * sizeof(double)))) return rc;
+    if ((rc = ensure(c, c->in, B * W * sizeof(double)))) return rc;
     if ((rc = ensure(c, c->bits, B * NW * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->gen_u, B * NW * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->flags, B * sizeof(uint32_t)))) return rc;           // per-frame error counts
     if ((rc = ensure(c, c->gen_cnt, 5 * sizeof(unsigned long long)))) return rc;   // [0..2) totals, [2..5) the cut
     unsigned long long *cnt = (unsigned long long *)c->gen_cnt.p;
-    HIP_TRY(c, hipMemcpyAsync(c->in.p, y, B * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->in.p, y, B * W * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->gen_u.p, u_bits, B * NW * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(cnt, 0, 5 * sizeof(unsigned long long), c->stream));
     if ((rc = decode_device_impl(c, c->in.p, 0, sigma, B, (uint32_t *)c->bits.p, nullptr, nullptr, c->d_frozen))) return rc;
@@ -1040,6 +1207,7 @@ int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long l
     }
     P.N = g.N; P.n = c->n; P.K = g.K; P.A = c->A; P.B = (int)B;
     P.out_is_f32 = out_is_f32; P.out_is_y = out_is_y;
+    if (c->rm_mode != POLAR_RM_NONE) return polar_tu::rm_generate(c, P);   // [B][E] (include/polar_hip.h rules 1-3)
     const int waves = 4;
     const size_t lds = (size_t)waves * (g.N + 2 * 1024);
     int grid = (int)std::min<size_t>((B + waves - 1) / waves, (size_t)c->num_cu * 8);
@@ -1052,10 +1220,11 @@ int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long l
 static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double snr_db, size_t B,
                           unsigned long long *h, uint32_t *d_frame_err = nullptr)
 {
-    const int N = c->cfg.N, NW = c->NW;
+    const int NW = c->NW;
+    const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : c->cfg.N;   // values per generated row
     const bool f32 = c->cfg.dtype == POLAR_F32;
     int rc;
-    if ((rc = ensure(c, c->gen_llr, B * N * (f32 ? 4 : 8)))) return rc;
+    if ((rc = ensure(c, c->gen_llr, B * W * (f32 ? 4 : 8)))) return rc;
     if ((rc = ensure(c, c->gen_u, B * NW * 4))) return rc;
     if ((rc = ensure(c, c->bits, B * NW * 4))) return rc;
     if ((rc = ensure(c, c->gen_cnt, 16))) return rc;
@@ -1073,9 +1242,9 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
     const size_t esz = f32 ? 4 : 8;
     auto run_part = [&](size_t f0, size_t nf) -> int {
         int r;
-        if ((r = polar_generate_device(c, seed, first_frame + f0, snr_db, nf, (char *)c->gen_llr.p + f0 * N * esz, f32 ? 1 : 0, 0,
+        if ((r = polar_generate_device(c, seed, first_frame + f0, snr_db, nf, (char *)c->gen_llr.p + f0 * W * esz, f32 ? 1 : 0, 0,
                                        (uint32_t *)c->gen_u.p + f0 * NW))) return r;
-        if ((r = decode_device_impl(c, (char *)c->gen_llr.p + f0 * N * esz, f32 ? 1 : 0, 0.0, nf, (uint32_t *)c->bits.p + f0 * NW,
+        if ((r = decode_device_impl(c, (char *)c->gen_llr.p + f0 * W * esz, f32 ? 1 : 0, 0.0, nf, (uint32_t *)c->bits.p + f0 * NW,
                                     nullptr, nullptr, c->d_frozen))) return r;
         return polar_count_errors_device(c, (uint32_t *)c->bits.p + f0 * NW, (uint32_t *)c->gen_u.p + f0 * NW, nf,
                                          (unsigned long long *)c->gen_cnt.p, d_frame_err ? d_frame_err + f0 : nullptr);
@@ -1086,10 +1255,12 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
         HIP_TRY(c, hipStreamWaitEvent(c->stream_b, c->ev_b, 0));
         std::swap(c->stream, c->stream_b);
         std::swap(c->scratch, c->scratch_b);
+        std::swap(c->rm_rows, c->rm_rows_b);
         rc = run_part(half, B - half);
         hipError_t e = hipEventRecord(c->ev_b, c->stream);
         std::swap(c->stream, c->stream_b);
         std::swap(c->scratch, c->scratch_b);
+        std::swap(c->rm_rows, c->rm_rows_b);
         if (rc) return rc;
         HIP_TRY(c, e);
     }

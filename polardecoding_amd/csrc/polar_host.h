@@ -16,6 +16,7 @@
 
 namespace polar {
 struct ScfParams;   // scf_params.h
+struct GenParams;   // gen_common.h
 }
 
 struct PolarBuf {
@@ -54,7 +55,12 @@ struct polar_ctx {
     // SC-Flip (POLAR_ALGO_SCF): flip budget T (polar_scf_set_flips), the failing frames' flip positions, pass B's pairs
     int scf_T = 8;
     Buf scf_flips, scf_pass, scf_bits;
-    Buf in2[2], bits2[2];                 // chunked host pipeline: ping-pong device buffers
+    // 5G rate matching (polar_create_rm): E, POLAR_RM_* mode (POLAR_RM_NONE: a plain ctx), channel interleaver, its tables
+    // (sent-row position of e_k, and the inverse) and the recovered rows, one buffer per stream of polar_fer_batch
+    int rm_E = 0, rm_mode = POLAR_RM_NONE, rm_ibil = 0;
+    uint16_t *d_rm_ilv = nullptr, *d_rm_ilv_inv = nullptr;
+    Buf rm_rows, rm_rows_b;
+    Buf in2[2], bits2[2];                // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
     double *h_in[2] = {nullptr, nullptr};       // pinned staging of the caller's (pageable) input chunks, big batches only
@@ -153,6 +159,9 @@ int ad_scatter(polar_ctx *c, const uint32_t *s_bits, const double *s_pm, const u
 int scf_lanes(polar_ctx *c, const polar::ScfParams &P, int mode, bool r32, bool in32);
 int scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, const uint32_t *d_idx, size_t n, int T,
                 uint32_t *d_bits, uint32_t *d_flags, uint32_t *d_attempts);
+// k_rm.hip: 5G rate matching (rm_kernel.h): recovery [B][E] -> [B][N] of the input type, generator [B][E]
+int rm_recover(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t B, void *d_out);
+int rm_generate(polar_ctx *c, const polar::GenParams &G);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

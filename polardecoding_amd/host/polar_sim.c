@@ -178,7 +178,8 @@ static void usage(void)
                     "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
-                    "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n");
+                    "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n"
+                    "                 [--E e [--ibil]]   (--fast only: 5G rate matching, e channel values per codeword; --ibil: channel interleaver)\n");
     exit(2);
 }
 
@@ -188,6 +189,7 @@ int main(int argc, char **argv)
     int fast = 0, sys = 0, bpr = 0, gpus = 1, bp_stop = POLAR_BP_STOP_NONE;
     int stages[6], nstages = 0;   /* --stages: polar_cascl_set_stages */
     int flips = -1;               /* --flips: polar_scf_set_flips (-1: the library's default) */
+    int rm_E = 0, rm_ibil = 0;    /* --E / --ibil: polar_create_rm (0: no rate matching) */
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
     double lo = 1.0, hi = 3.0, step = 0.5;
@@ -217,6 +219,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--min-run") && v) { min_run = atol(v); i++; }
         else if (!strcmp(a, "--fn") && v) { fnfile = v; i++; }
         else if (!strcmp(a, "--fast")) { fast = 1; }
+        else if (!strcmp(a, "--E") && v) { rm_E = atoi(v); i++; }
+        else if (!strcmp(a, "--ibil")) { rm_ibil = 1; }
         else if (!strcmp(a, "--gpus") && v) { gpus = atoi(v); i++; }   /* --fast only: frames sharded over the GPUs of the node */
         else if (!strcmp(a, "--sys")) { sys = 1; }
         else if (!strcmp(a, "--bp-stop") && v) {   /* polar_bp_set_stop */
@@ -322,9 +326,20 @@ int main(int argc, char **argv)
     cfg.N = N; cfg.K = K; cfg.crc_r = c.r; cfg.crc_taps = c.r ? c.taps : NULL; cfg.n_taps = c.ntaps;
     cfg.L = L; cfg.algo = algo; cfg.bp_iters = bp_iters; cfg.info_order = qorder ? qorder + (N - c.A) : NULL; cfg.dtype = dtype; cfg.device = 0;
     cfg.crc_systematic = c.sys;
+    if (rm_ibil && !rm_E) { fprintf(stderr, "--ibil needs --E\n"); return 1; }
+    if (rm_E) {
+        /* the device-side generator and decoder handle the E-value rows; the host Ranq1 path below has no rate matching */
+        if (!fast) { fprintf(stderr, "--E: only with --fast (the host Ranq1 frame loop has no rate matching)\n"); return 1; }
+        if (c.gc || qorder || gpus > 1) { fprintf(stderr, "--E: not with --crc-file, --q or --gpus > 1\n"); return 1; }
+    }
     polar_ctx *ctx = NULL;
     int rc = (c.gc) ? polar_create_crc_file(&cfg, crcfile, &ctx) : polar_create(&cfg, &ctx);
     if (rc) { fprintf(stderr, "polar_create: %s\n", polar_strerror(rc)); return 1; }
+    if (rm_E) {   /* the plain context above has checked cfg; the rate-matched one replaces it */
+        polar_destroy(ctx);
+        ctx = NULL;
+        if ((rc = polar_create_rm(&cfg, rm_E, rm_ibil, &ctx)) != 0) { fprintf(stderr, "polar_create_rm: %s\n", polar_strerror(rc)); return 1; }
+    }
     if (bp_stop != POLAR_BP_STOP_NONE) {
         /* the read-outs need fixed iterations; a polar_group builds its contexts from cfg and has no stop rule */
         if (bpr || (fast && gpus > 1)) { fprintf(stderr, "--bp-stop: not with --algo bpr or --gpus > 1\n"); return 1; }
