@@ -324,6 +324,44 @@ int polar_rm_info(const polar_ctx *ctx, int *E, int *mode, int *ibil);
  * same type.  POLAR_EINVAL on a ctx not made by polar_create_rm. */
 int polar_rm_recover_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, void *d_out);
 
+/* --- Monte-Carlo code construction: genie-aided SC on the device (Arikan 2009, section IX) ---------------------------
+ * A frozen set designed for an operating point, for any N: send the all-zero codeword, run SC with a genie that feeds the
+ * true bits into the partial sums, and count per leaf how often its LLR has the wrong sign.  For a block length N = 2^n,
+ * 32 <= N <= 4096, arithmetic type R (the ctx dtype) and one input row l[0..N) of channel LLRs:
+ *  1. lambda_j, j = 0..N-1, is the leaf LLR of POLAR_ALGO_SC at leaf j when EVERY leaf is frozen: all decisions are 0, every
+ *     g step is cL + cU, every f step is the library's check node, in SC's operation order.  No subtree is skipped.  The
+ *     ctx's own frozen set plays no part.
+ *  2. A frame adds to two counters per leaf: err[j] += (lambda_j < 0), tie[j] += (lambda_j == 0) (comparisons in R; -0.0 is a
+ *     tie; a NaN counts as neither).  Counters are uint64_t [2][N] (err row, then tie row) in device memory, and a call ADDS
+ *     to what the buffer holds, so calls and GPUs can be summed.  Integer sums: the result does not depend on launch shape,
+ *     chunking or order.
+ *  3. Design rows: frame f, element e is 2*y/sigma/sigma (that order) with y = 1 + sigma * z (bit 0 is sent as +1),
+ *     z = normal (e & 1) of Philox(seed, first_frame + f, e >> 1, stream 2) by the generator's Box-Muller
+ *     (sqrt(-2 log u0), sincospi(2 u1)); rounded to float for an F32 ctx.
+ *  4. Order: score[j] = 2*err[j] + tie[j].  out[0..N) lists the positions in ASCENDING reliability = descending score; equal
+ *     scores keep the order of a caller-given base order (ascending reliability; NULL = the library's own order for N: the
+ *     5G sequence, or polarization weight above 1024).  With all counters zero the result is the base order, and
+ *     out + N - A is directly a polar_cfg.info_order for A unfrozen positions.
+ * The entry points work on any ctx (they use its N, dtype, device, stream, scratch and work queue; an SC ctx is the natural
+ * choice) and return POLAR_EINVAL on a ctx made by polar_create_rm (its rows are E wide), for NULL buffers, B > 0x7fffffff
+ * and, in the two design-row calls, sigma <= 0; the ctx stays usable.  All three are asynchronous on the ctx stream and can
+ * be captured into a graph after a warm-up call at the same B.
+ * Out of scope: Gaussian-approximation / density-evolution construction, soft statistics (sums of 1/(1+e^lambda): float
+ * sums depend on order), rate-matched construction, polar_group_* wrappers (counters add, so a caller can shard frames over
+ * GPUs by first_frame and sum). */
+/* rules 1-2 on caller rows d_in [B][N] (double, or float when in_is_f32; LLRs, or y when sigma > 0) */
+int polar_genie_count_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint64_t *d_counts);
+/* rule 3: d_out [B][N] double, or float when out_is_f32 */
+int polar_genie_rows_device(polar_ctx *ctx, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
+                            void *d_out, int out_is_f32);
+/* rule 3 rows of the ctx dtype into ctx-owned scratch in chunks of at most 256 MiB, rules 1-2 on each chunk: exactly the
+ * counters of polar_genie_rows_device followed by polar_genie_count_device on the same frames */
+int polar_construct_batch(polar_ctx *ctx, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
+                          uint64_t *d_counts);
+/* rule 4 on host counters [2][N].  Host only, touches no device.  POLAR_EINVAL for N not a power of two in 32..4096, NULL
+ * counts / out, or a base order that is not a permutation of 0..N-1. */
+int polar_construct_order(int N, const uint64_t *counts, const int *base_order, int *out);
+
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at
  * Eb/N0 = snr_db (sigma = 10^(-snr_db/20), rate 1/2 as in the reference, :237) -> d_out[B][N] (double, or float

@@ -122,6 +122,10 @@ def load_library(testing=False):
     L.polar_create_rm.argtypes = [C.POINTER(_Cfg), C.c_int, C.c_int, C.POINTER(vp)]
     L.polar_rm_info.argtypes = [vp, ip, ip, ip]
     L.polar_rm_recover_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp]
+    L.polar_genie_count_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp]
+    L.polar_genie_rows_device.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp, C.c_int]
+    L.polar_construct_batch.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp]
+    L.polar_construct_order.argtypes = [C.c_int, C.POINTER(C.c_uint64), ip, ip]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -186,6 +190,47 @@ def rm_info_order(N, A, E):
     if rc != 0:
         raise PolarError(f"polar_rm_info_order({N}, {A}, {E}): {lib.polar_strerror(rc).decode()} (rc={rc})")
     return out[:int(A)]
+
+
+def construct_order(N, counts, base_order=None):
+    """polar_construct_order (include/polar_hip.h, Monte-Carlo construction rule 4): counts [2][N] (err row, tie row) -> the
+    N positions in ascending reliability (descending 2*err + tie, equal scores in `base_order`; None: the library's own order
+    for N).  ``order[N - A:]`` is an ``info_order`` for A unfrozen positions.  Host only."""
+    lib = load_library()
+    cnt = np.ascontiguousarray(counts, dtype=np.uint64)
+    if cnt.shape != (2, int(N)):
+        raise ValueError(f"counts must have shape (2, {N})")
+    base = None
+    if base_order is not None:
+        base = np.ascontiguousarray(base_order, dtype=np.int32)
+        if base.shape != (int(N),):
+            raise ValueError(f"base_order must have shape ({N},)")
+    out = np.zeros(int(N), dtype=np.int32)
+    rc = lib.polar_construct_order(int(N), _ptr(cnt, C.c_uint64), _ptr(base, C.c_int) if base is not None else None,
+                                   _ptr(out, C.c_int))
+    if rc != 0:
+        raise PolarError(f"polar_construct_order({N}): {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return out
+
+
+def construct_mc(N, sigma, frames, seed=0, dtype=F64, device=0, base_order=None, batch=1 << 16):
+    """Monte-Carlo construction for design noise `sigma`: genie-aided SC of `frames` all-zero codewords on the device
+    (Decoder.construct_batch, `batch` frames per call) -> (order, counts).  order: the N positions in ascending reliability
+    (``order[N - A:]`` feeds ``SCLdecode(N, K, info_order=...)`` and the others); counts: uint64 [2][N] (err row, tie row)."""
+    import torch
+    dec = Decoder(N, N // 2, ALGO_SC, dtype=dtype, device=device)
+    try:
+        d_counts = torch.zeros((2, N), dtype=torch.int64, device=f"cuda:{device}")
+        done = 0
+        while done < frames:
+            nb = min(int(batch), int(frames) - done)
+            dec.construct_batch(seed, done, sigma, nb, d_counts)
+            done += nb
+        dec.synchronize()
+        counts = d_counts.cpu().numpy().view(np.uint64)
+    finally:
+        dec.close()
+    return construct_order(N, counts, base_order), counts
 
 
 class Decoder:
@@ -569,6 +614,48 @@ class Decoder:
         self._check(self._lib.polar_rm_recover_device(self._h, C.c_void_p(d_in.data_ptr()), 1 if d_in.dtype == torch.float32 else 0,
                                                       float(sigma), B, C.c_void_p(out.data_ptr())), "polar_rm_recover_device")
         return out
+
+    # ---- Monte-Carlo construction (include/polar_hip.h: genie-aided SC, rules 1-3) -----------------------------------
+    @staticmethod
+    def _counts(counts, N):
+        import torch
+        if not (counts.is_cuda and counts.is_contiguous() and counts.dtype == torch.int64 and counts.numel() == 2 * N):
+            raise ValueError("counts must be a contiguous int64 CUDA tensor of shape [2][N] (err row, tie row)")
+        return C.c_void_p(counts.data_ptr())
+
+    def genie_count_device(self, d_in, counts, sigma=0.0):
+        """polar_genie_count_device: d_in [B][N] float64/float32 LLRs (or y with sigma > 0); adds per leaf the frames whose
+        genie-aided SC leaf LLR is negative (counts[0]) or zero (counts[1]).  counts: int64 CUDA tensor [2][N] holding the
+        library's uint64 counters.  Asynchronous on the ctx stream."""
+        import torch
+        if d_in.dtype not in (torch.float64, torch.float32):
+            raise ValueError("input must be float64 or float32")
+        if not (d_in.is_cuda and d_in.is_contiguous()) or d_in.dim() == 0 or d_in.shape[-1] != self.N:
+            raise ValueError(f"device rows must be a contiguous CUDA tensor of shape [B][{self.N}]")
+        B = d_in.numel() // self.N
+        self._check(self._lib.polar_genie_count_device(self._h, C.c_void_p(d_in.data_ptr()), 1 if d_in.dtype == torch.float32 else 0,
+                                                       float(sigma), B, self._counts(counts, self.N)), "polar_genie_count_device")
+        return counts
+
+    def genie_rows_device(self, seed, first_frame, sigma, out):
+        """polar_genie_rows_device: fills out [B][N] (float64 or float32 CUDA tensor) with the design rows of frames
+        first_frame .. first_frame + B - 1: the all-zero codeword over BPSK + AWGN of standard deviation sigma, as LLRs."""
+        import torch
+        if out.dtype not in (torch.float64, torch.float32):
+            raise ValueError("out must be float64 or float32")
+        if not (out.is_cuda and out.is_contiguous()) or out.dim() == 0 or out.shape[-1] != self.N:
+            raise ValueError(f"out must be a contiguous CUDA tensor of shape [B][{self.N}]")
+        self._check(self._lib.polar_genie_rows_device(self._h, int(seed), int(first_frame), float(sigma), out.numel() // self.N,
+                                                      C.c_void_p(out.data_ptr()), 1 if out.dtype == torch.float32 else 0),
+                    "polar_genie_rows_device")
+        return out
+
+    def construct_batch(self, seed, first_frame, sigma, B, counts):
+        """polar_construct_batch: design rows of B frames (ctx dtype, ctx scratch) -> genie-aided SC -> counts (as
+        genie_count_device).  Exactly genie_rows_device followed by genie_count_device on the same frames."""
+        self._check(self._lib.polar_construct_batch(self._h, int(seed), int(first_frame), float(sigma), int(B),
+                                                    self._counts(counts, self.N)), "polar_construct_batch")
+        return counts
 
     def synchronize(self):
         self._check(self._lib.polar_synchronize(self._h), "polar_synchronize")

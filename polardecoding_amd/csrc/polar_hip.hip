@@ -755,7 +755,7 @@ void polar_destroy(polar_ctx *c)
     }
     for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
     for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
-                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->rm_rows, &c->rm_rows_b})
+                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->rm_rows, &c->rm_rows_b, &c->genie_rows})
         if (b->p) (void)hipFree(b->p);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
@@ -1179,6 +1179,61 @@ int polar_stop_rule_batch_y(polar_ctx *c, const double *y, double sigma, const u
     *consumed = (size_t)h[0];
     *block_errors = h[1];
     *bit_errors = h[2];
+    return POLAR_OK;
+}
+
+// ---- Monte-Carlo construction (include/polar_hip.h) ---------------------------------------------------------------------
+int polar_genie_count_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint64_t *d_counts)
+{
+    if (!c || c->rm_mode != POLAR_RM_NONE || !d_in || !d_counts || B > 0x7fffffffull) return POLAR_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_in) % (in_is_f32 ? 4 : 8)) || (reinterpret_cast<uintptr_t>(d_counts) % 8)) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return polar_tu::genie_count(c, d_in, in_is_f32 != 0, sigma, B, reinterpret_cast<unsigned long long *>(d_counts));
+}
+
+int polar_genie_rows_device(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
+                            void *d_out, int out_is_f32)
+{
+    if (!c || c->rm_mode != POLAR_RM_NONE || !d_out || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_out) % (out_is_f32 ? 4 : 8)) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return polar_tu::genie_rows(c, seed, first_frame, sigma, B, d_out, out_is_f32 != 0);
+}
+
+// design rows of the ctx dtype into ctx scratch, chunks of at most 256 MiB (the rule of the rate-matching path), counted chunk by chunk
+int polar_construct_batch(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
+                          uint64_t *d_counts)
+{
+    if (!c || c->rm_mode != POLAR_RM_NONE || !d_counts || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_counts) % 8) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    const bool f32 = c->cfg.dtype == POLAR_F32;
+    const size_t row = (size_t)c->cfg.N * (f32 ? 4 : 8);
+    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
+    int rc;
+    if ((rc = ensure(c, c->genie_rows, CH * row))) return rc;
+    for (size_t off = 0; off < B; off += CH) {
+        const size_t nc = std::min(CH, B - off);
+        if ((rc = polar_tu::genie_rows(c, seed, first_frame + off, sigma, nc, c->genie_rows.p, f32))) return rc;
+        if ((rc = polar_tu::genie_count(c, c->genie_rows.p, f32, 0.0, nc, reinterpret_cast<unsigned long long *>(d_counts)))) return rc;
+    }
+    return POLAR_OK;
+}
+
+int polar_construct_order(int N, const uint64_t *counts, const int *base_order, int *out)
+{
+    if (N < 32 || N > 4096 || (N & (N - 1)) || !counts || !out) return POLAR_EINVAL;
+    std::vector<int> base = base_order ? std::vector<int>(base_order, base_order + N) : default_order(N);
+    std::vector<unsigned char> seen((size_t)N, 0);
+    for (int j : base) {
+        if (j < 0 || j >= N || seen[(size_t)j]) return POLAR_EINVAL;
+        seen[(size_t)j] = 1;
+    }
+    // score = 2 * err + tie, wider than the counters; descending score, equal scores in base order
+    auto score = [&](int j) { return 2 * (unsigned __int128)counts[j] + counts[(size_t)N + j]; };
+    std::stable_sort(base.begin(), base.end(), [&](int a, int b) { return score(a) > score(b); });
+    std::copy(base.begin(), base.end(), out);
     return POLAR_OK;
 }
 

@@ -60,6 +60,7 @@ struct polar_ctx {
     int rm_E = 0, rm_mode = POLAR_RM_NONE, rm_ibil = 0;
     uint16_t *d_rm_ilv = nullptr, *d_rm_ilv_inv = nullptr;
     Buf rm_rows, rm_rows_b;
+    Buf genie_rows;                       // polar_construct_batch: one chunk of design rows
     Buf in2[2], bits2[2];                // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
@@ -162,6 +163,10 @@ int scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, c
 // k_rm.hip: 5G rate matching (rm_kernel.h): recovery [B][E] -> [B][N] of the input type, generator [B][E]
 int rm_recover(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t B, void *d_out);
 int rm_generate(polar_ctx *c, const polar::GenParams &G);
+// k_genie.hip: Monte-Carlo construction (genie_lanes.h): leaf-sign counters of genie-aided SC (the ctx's N and dtype), design rows
+int genie_count(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t B, unsigned long long *d_counts);
+int genie_rows(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B, void *d_out,
+               bool out32);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

@@ -21,6 +21,8 @@
  * that brings the block errors to >= BLE.  Same code, same decoder, different (statistically equivalent)
  * noise: use it for FER curves at 10^6..10^7 frames/s, not for reproducing published run counts.
  */
+#define _GNU_SOURCE   /* RTLD_DEFAULT */
+#include <dlfcn.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -172,6 +174,39 @@ static void make_batch(gen_state *g, const code_t *c, double sigma, int batch, u
 static const int CRC24C[] = {0, 1, 2, 4, 8, 12, 13, 15, 17, 20, 21, 23, 24};
 static const int CRC6[] = {0, 5, 6};
 
+/* Monte-Carlo construction (include/polar_hip.h): counters on the device of an SC context, order on the host.  This program
+   links the library only; the four HIP runtime calls the counters need come from the runtime the library already loaded. */
+static int construct_order(int N, int dtype, long long frames, double sigma, uint64_t seed, int *order)
+{
+    int (*dmalloc)(void **, size_t) = (int (*)(void **, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
+    int (*dmemset)(void *, int, size_t) = (int (*)(void *, int, size_t))dlsym(RTLD_DEFAULT, "hipMemset");
+    int (*dmemcpy)(void *, const void *, size_t, int) = (int (*)(void *, const void *, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy");
+    int (*dfree)(void *) = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipFree");
+    if (!dmalloc || !dmemset || !dmemcpy || !dfree) { fprintf(stderr, "--construct: no HIP runtime in this process\n"); return 1; }
+    polar_cfg cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.N = N; cfg.K = N / 2; cfg.L = 1; cfg.algo = POLAR_ALGO_SC; cfg.dtype = dtype; cfg.device = 0;
+    polar_ctx *ctx = NULL;
+    int rc = polar_create(&cfg, &ctx);
+    if (rc) { fprintf(stderr, "--construct: polar_create: %s\n", polar_strerror(rc)); return 1; }
+    const size_t bytes = sizeof(uint64_t) * 2 * (size_t)N;
+    void *d_counts = NULL;
+    uint64_t *counts = (uint64_t *)malloc(bytes);
+    if (!counts || dmalloc(&d_counts, bytes) || dmemset(d_counts, 0, bytes)) { fprintf(stderr, "--construct: no memory for the counters\n"); return 1; }
+    for (long long done = 0; done < frames && !rc; done += 65536)
+        rc = polar_construct_batch(ctx, seed, (unsigned long long)done, sigma, (size_t)(frames - done < 65536 ? frames - done : 65536),
+                                   (uint64_t *)d_counts);
+    if (!rc) rc = polar_synchronize(ctx);
+    if (rc) { fprintf(stderr, "--construct: %s (%s)\n", polar_strerror(rc), polar_last_error(ctx)); return 1; }
+    if (dmemcpy(counts, d_counts, bytes, 2 /* hipMemcpyDeviceToHost */)) { fprintf(stderr, "--construct: copy of the counters failed\n"); return 1; }
+    (void)dfree(d_counts);
+    polar_destroy(ctx);
+    rc = polar_construct_order(N, counts, NULL, order);
+    free(counts);
+    if (rc) { fprintf(stderr, "--construct: polar_construct_order: %s\n", polar_strerror(rc)); return 1; }
+    return 0;
+}
+
 static void usage(void)
 {
     fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
@@ -179,6 +214,8 @@ static void usage(void)
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
                     "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n"
+                    "                 [--construct frames --design-snr db [--q-out file]]   (Monte-Carlo construction of the order on the device first;\n"
+                    "                                  --q-out: write it in the format --q reads)\n"
                     "                 [--E e [--ibil]]   (--fast only: 5G rate matching, e channel values per codeword; --ibil: channel interleaver)\n");
     exit(2);
 }
@@ -195,7 +232,10 @@ int main(int argc, char **argv)
     double lo = 1.0, hi = 3.0, step = 0.5;
     double pts[64];
     int npts = 0;   /* --snr-list a,b,c: explicit Eb/N0 points (the published L = 32 log goes 1.0, 1.5, 2.0, 2.2) */
-    const char *crc = NULL, *qfile = NULL, *fnfile = NULL, *crcfile = NULL;
+    const char *crc = NULL, *qfile = NULL, *fnfile = NULL, *crcfile = NULL, *qout = NULL;
+    long long construct = 0;      /* --construct FRAMES: Monte-Carlo construction of the order before the sweep */
+    double design_db = 0;         /* --design-snr DB: its design point (sigma = 10^(-DB/20)) */
+    int have_design = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -216,6 +256,9 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--batch") && v) { batch = atoi(v); i++; }
         else if (!strcmp(a, "--bp-iters") && v) { bp_iters = atoi(v); i++; }
         else if (!strcmp(a, "--q") && v) { qfile = v; i++; }
+        else if (!strcmp(a, "--q-out") && v) { qout = v; i++; }
+        else if (!strcmp(a, "--construct") && v) { construct = atoll(v); i++; if (construct < 1) usage(); }
+        else if (!strcmp(a, "--design-snr") && v) { design_db = atof(v); have_design = 1; i++; }
         else if (!strcmp(a, "--min-run") && v) { min_run = atol(v); i++; }
         else if (!strcmp(a, "--fn") && v) { fnfile = v; i++; }
         else if (!strcmp(a, "--fast")) { fast = 1; }
@@ -319,6 +362,21 @@ int main(int argc, char **argv)
                 return 1;
             }
         fclose(fq);
+    }
+    /* --construct FRAMES --design-snr DB: genie-aided SC of FRAMES all-zero codewords at sigma = 10^(-DB/20) (this program's
+       Eb/N0 convention at rate 1/2) on the device, polar_construct_order on the counters; the sweep then uses that order */
+    if (construct > 0) {
+        if (!have_design) { fprintf(stderr, "--construct needs --design-snr\n"); return 1; }
+        if (qfile) { fprintf(stderr, "--construct and --q exclude each other\n"); return 1; }
+        qorder = (int *)malloc(sizeof(int) * (size_t)N);
+        if (!qorder || construct_order(N, dtype, construct, pow(10, design_db / ((double)-20)), seed, qorder)) return 1;
+    } else if (have_design) { fprintf(stderr, "--design-snr needs --construct\n"); return 1; }
+    if (qout) {
+        if (!qorder) { fprintf(stderr, "--q-out needs --construct or --q\n"); return 1; }
+        FILE *fo = fopen(qout, "w");
+        if (!fo) { fprintf(stderr, "cannot write %s\n", qout); return 1; }
+        for (int i = 0; i < N; i++) fprintf(fo, "%d%c", qorder[i], (i % 16 == 15 || i == N - 1) ? '\n' : ' ');
+        fclose(fo);
     }
 
     polar_cfg cfg;
