@@ -341,6 +341,16 @@ struct Fast2Dec {
         if (d > 4) f_reg<4>();
         if (d > 3) f_reg<3>();
     }
+    // the same for an octet inside a group of eight (o & 7 != 0, d <= 5): only the register levels 2..5 change
+    __device__ __forceinline__ void octet_head_reg(int o)
+    {
+        const int d = 3 + __builtin_ctz((unsigned)o);
+        if (d == 5) g_reg<5>();
+        else if (d == 4) g_reg<4>();
+        else g3();
+        if (d > 4) f_reg<4>();
+        if (d > 3) f_reg<3>();
+    }
 
     // ---- partial sums (identical per path to k_scl_fast) ----
     template <int K>
@@ -356,26 +366,30 @@ struct Fast2Dec {
             const uint32_t c2 = (((bl0 >> 2) & 3u) ^ c1) | (c1 << 2);
             bl0 = (bl0 & ~0xF0u) | (c2 << 4);
         } else {
-            set_bit_tail(8 * o + 7, bit);
+            const uint32_t c1 = (((bl0 >> 1) & 1u) ^ bit) | (bit << 1);
+            const uint32_t c2 = (((bl0 >> 2) & 3u) ^ c1) | (c1 << 2);
+            set_bit7(o, (((bl0 >> 4) & 15u) ^ c2) | (c2 << 4));
         }
     }
-    __device__ __forceinline__ void set_bit_tail(int j, uint32_t bit)
+    // Leaf 7 of octet o closes the octet: j = 8o + 7, so the combine steps at levels 0..2 are the same at every octet
+    // (the caller does them with constant masks and passes c3, the octet's eight level-3 partial sums); how far the
+    // carry runs beyond that depends on o alone, which is wave-uniform.
+    __device__ __forceinline__ void set_bit7(int o, uint32_t c3)
     {
-        uint32_t cur = bit;
-        const int z = __builtin_ctz(~(unsigned)j);
-        const int zl = z < 5 ? z : 5;
-        for (int t = 0; t < zl; ++t) {
-            const int h = 1 << t;
-            const uint32_t mask = (1u << h) - 1u;
-            const uint32_t l = (bl0 >> h) & mask;
-            cur = (l ^ (cur & mask)) | ((cur & mask) << h);
-        }
-        if (z < 5) {
-            const int h = 1 << z;
-            const uint32_t mask = (1u << h) - 1u;
-            bl0 = (bl0 & ~(mask << h)) | ((cur & mask) << h);
+        if ((o & 1) == 0) {
+            bl0 = (bl0 & ~0xFF00u) | (c3 << 8);
             return;
         }
+        const uint32_t c4 = (((bl0 >> 8) & 0xFFu) ^ c3) | (c3 << 8);
+        if ((o & 2) == 0) {
+            bl0 = (bl0 & 0xFFFFu) | (c4 << 16);
+            return;
+        }
+        set_bit_lds(8 * o + 7, ((bl0 >> 16) ^ c4) | (c4 << 16));
+    }
+    // levels >= 5 (words in LDS); cur = the 32 level-5 partial sums that end at leaf j, j = 31 mod 32
+    __device__ __forceinline__ void set_bit_lds(int j, uint32_t cur)
+    {
         lds_fence();
         if (pos == 0) curw[p * NW] = cur;
         lds_fence();
@@ -653,7 +667,7 @@ struct Fast2Dec {
         bl0 &= ~0xFEu;
         if (last_frozen) {
             PM += quadp<0xFF>(pg);
-            set_bit_tail(8 * o + 7, 0u);
+            set_bit7(o, 0u);   // bits 1..7 of bl0 are 0 (above) and so is this one: c3 = 0
         } else {
             decide<7>(o, false, quadp<0xFF>(lg));
         }
@@ -828,12 +842,21 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
             o_first = lead;
             fword = frz[o_first >> 2];
         }
-        for (int o = o_first; o < N / 8; ++o) {
-            if ((o & 3) == 0) fword = frz[o >> 2];
-            s.octet_head(o);
-            const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
-            if ((fm & 0x7Fu) == 0x7Fu) s.octet_frozen_prefix(o, fm == 0xFFu);
-            else s.octet(o, fm);
+        // Groups of eight octets: level 6 (and the scratch levels) change only at the head of a group, so the inner
+        // loop does not carry the 16 level-6 registers as loop-variant values.  (With one loop over all octets the
+        // compiler kept them in one register set at the loop header and another behind the head, and copied all of
+        // them twice per octet.)
+        for (int o = o_first; o < N / 8;) {
+            s.octet_head(o);   // the first octet after the frozen run, then octets 8, 16, ...
+            for (;;) {
+                if ((o & 3) == 0) fword = frz[o >> 2];
+                const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
+                if ((fm & 0x7Fu) == 0x7Fu) s.octet_frozen_prefix(o, fm == 0xFFu);
+                else s.octet(o, fm);
+                ++o;
+                if ((o & 7) == 0) break;
+                s.octet_head_reg(o);
+            }
         }
 
         // ---- choose the path, per codeword (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) ----
