@@ -33,6 +33,7 @@ extern "C" {
 #define POLAR_ALGO_SCL 2   /* SCLdecode  SCL_1024.c:547-680                    */
 #define POLAR_ALGO_CASCL 3 /* CASCL      CASCL_1024_L8.c:601-761               */
 #define POLAR_ALGO_SCF 4   /* CRC-aided SC-Flip (no reference counterpart; polar_scf_set_flips below) */
+#define POLAR_ALGO_SCAN 5  /* soft-output SCAN (no reference counterpart; polar_scan_set_iters below) */
 
 /* dtype: the arithmetic type the message passing runs in */
 #define POLAR_F64 0 /* IEEE binary64 like the reference: bit-identical decisions (the parity gate) */
@@ -266,6 +267,55 @@ int polar_scf_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, dou
 /* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N]; flags, attempts (nullable) [B]. */
 int polar_scf_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *flags,
                            unsigned *attempts);
+
+/* --- Soft-output SCAN (soft cancellation; Fayyaz and Barry, IEEE JSAC 2014) ----------------------------------------------
+ * SCAN is BP's message arithmetic driven by SC's schedule: a serial walk over the tree that carries LLRs upwards instead of
+ * hard partial sums, and returns an LLR for every u bit and every code bit.  A POLAR_ALGO_SCAN context takes the cfg of a BP
+ * context (crc_r as BP accepts it; cfg.L is ignored and reported as 1; bp_iters is ignored).  32 <= N <= 1024 (above:
+ * POLAR_ENOKERNEL).
+ * Setting: N = 2^n, a frozen mask, the dtype's arithmetic type R, one row l[0..N) of finite channel LLRs (2*y/sigma/sigma
+ * when sigma > 0, as for the other decoders), I >= 1 iterations.
+ *   CHK-inf(a, b): if b = +inf the result is a; otherwise, if a = +inf, it is b; otherwise it is the check node chk<R>(a, b)
+ *   (csrc/polar_math.h).  This is chk's own value for a finite partner up to the sign of a zero; it is spelled out so that
+ *   (+inf, +inf) gives +inf and no inf - inf is ever evaluated.  The only infinity that can arise is +inf, and no
+ *   subtraction occurs anywhere in the decoder.
+ *   A node at level t covers the leaves s .. s + 2^t - 1, h = 2^(t-1); it receives alpha[0..2^t) and returns beta[0..2^t).
+ *   The root is the node at level n with s = 0 and alpha = l.
+ *   1. leaf (t = 0): lambda_s = alpha[0]; beta[0] = +inf if leaf s is frozen, else 0.
+ *   2. stored state: each right child (t-1, s+h) keeps the beta it returned, for the next iteration.  Before iteration 1
+ *      that stored beta is +inf in every element if all of the child's leaves are frozen, and 0 otherwise (a declared
+ *      difference from the paper, which starts internal nodes at 0: the stored beta of an all-frozen right child is a
+ *      constant that needs no memory; for frozen sets that respect the partial order no decision changes).
+ *   3. left child: alpha_l[e] = CHK-inf(alpha[e], alpha[e+h] + beta_r_prev[e]), e < h; beta_l = visit(left child, alpha_l).
+ *   4. right child: alpha_r[e] = alpha[e+h] + CHK-inf(alpha[e], beta_l[e]); beta_r = visit(right child, alpha_r); this
+ *      beta_r replaces beta_r_prev.
+ *   5. upwards: beta[e] = CHK-inf(beta_l[e], beta_r[e] + alpha[e+h]); beta[e+h] = beta_r[e] + CHK-inf(beta_l[e], alpha[e]).
+ *   6. one iteration is one visit of the root; iterations 1..I run back to back; the stored right-child betas are the only
+ *      state carried over between them.
+ *   7. outputs, all from iteration I: u_hat_j = 0 if j is frozen, else [lambda_j < 0]; llr_u[j] = lambda_j at unfrozen j
+ *      and +inf at frozen j; ext_x[e] = the root's beta[e], the extrinsic LLR of code bit e (the caller forms
+ *      l[e] + ext_x[e]; +inf where the frozen set fixes the bit); the metric is 0.0 and the flags word is 0.
+ *   8. every sum and every chk is rounded once in R, no contraction.  Soft outputs are compared by value: the sign of a
+ *      zero is not pinned.
+ * Consequences a kernel may use (each preserves every value above): an all-frozen subtree returns +inf everywhere and its
+ * lambdas are not reported, so it is never entered; an all-information subtree returns exactly 0 everywhere, so it is
+ * entered in iteration I only, downwards only (alpha_l = chk(a, b), alpha_r = b); whether an element of a beta is +inf
+ * depends on the frozen mask only.
+ * The decoder is honoured by polar_decode, polar_decode_batch(_y) (a frozen_mask override works as for SC),
+ * polar_decode_device, polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device, polar_kernel_name and
+ * polar_ctx_info.  On a polar_create_rm context the recovered N-wide row is the input l; ext_x stays N wide, in decoder
+ * order.  polar_group_* and polar_fer_multi_gpu run the default I = 4.  polar_bp_*, polar_cascl_*, polar_scf_* and
+ * polar_create_crc_file return POLAR_EINVAL on (or for) a SCAN ctx.  A decode that cannot get its scratch memory returns
+ * POLAR_ENOMEM and leaves the ctx usable. */
+/* I: 1 <= I <= 64; default 4.  POLAR_EINVAL (ctx unchanged): not a SCAN ctx, or I out of range. */
+int polar_scan_set_iters(polar_ctx *ctx, int I);
+/* d_uhat_bits [B][N/32], d_llr_u and d_ext_x [B][N] of the ctx dtype (double or float); each of the three may be NULL.
+ * Asynchronous on the ctx stream, no host read-back: after a warm-up at the same B it can be captured into a graph. */
+int polar_scan_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
+                             uint32_t *d_uhat_bits, void *d_llr_u, void *d_ext_x);
+/* Host-buffer form: llr_in [B][N] LLRs (E per row on a rate-matched ctx); u_hat [B][N], llr_u and ext_x [B][N] of the ctx
+ * dtype; each of the three outputs may be NULL. */
+int polar_scan_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, void *llr_u, void *ext_x);
 
 /* --- 5G NR rate matching (TS 38.212 5.4.1; no reference counterpart) -------------------------------------------------
  * A rate-matched context sends E channel values per codeword instead of N.  Notation of 38.212: A = K + r bits enter the

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF = 0, 1, 2, 3, 4
+ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF, ALGO_SCAN = 0, 1, 2, 3, 4, 5
 F64, F32 = 0, 1
 FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
 RM_NONE, RM_REPEAT, RM_PUNCTURE, RM_SHORTEN = 0, 1, 2, 3   # polar_rm_info modes (5G rate matching)
@@ -96,6 +96,9 @@ def load_library(testing=False):
     L.polar_scf_set_flips.argtypes = [vp, C.c_int]
     L.polar_scf_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
     L.polar_scf_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
+    L.polar_scan_set_iters.argtypes = [vp, C.c_int]
+    L.polar_scan_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
+    L.polar_scan_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, vp, vp]
     L.polar_generate_device.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp, C.c_int,
                                         C.c_int, vp]
     L.polar_fer_batch.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, C.POINTER(C.c_ulonglong),
@@ -263,6 +266,7 @@ class Decoder:
         self.bp_stop = BP_STOP_NONE
         self.cascl_stages = ()
         self.scf_flips = None   # None: the library's default (min(8, K + r))
+        self.scan_iters = None  # None: the library's default (4)
         self._rm = (int(E), 1 if ibil else 0) if E is not None else None
         self._create()
         A, Lr = C.c_int(), C.c_int()
@@ -298,6 +302,8 @@ class Decoder:
             self.set_cascl_stages(self.cascl_stages)
         if self.scf_flips is not None:
             self.set_scf_flips(self.scf_flips)
+        if self.scan_iters is not None:
+            self.set_scan_iters(self.scan_iters)
 
     @property
     def info_order(self):
@@ -345,6 +351,11 @@ class Decoder:
         min(32, K + r); T = 0 is SC plus the CRC flag."""
         self._check(self._lib.polar_scf_set_flips(self._h, int(T)), "polar_scf_set_flips")
         self.scf_flips = int(T)
+
+    def set_scan_iters(self, iters):
+        """SCAN iteration count (polar_scan_set_iters): 1 <= iters <= 64, default 4."""
+        self._check(self._lib.polar_scan_set_iters(self._h, int(iters)), "polar_scan_set_iters")
+        self.scan_iters = int(iters)
 
     @property
     def kernel_name(self):
@@ -513,6 +524,44 @@ class Decoder:
         self._check(self._lib.polar_scf_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
                                                      _ptr(fl, C.c_uint), _ptr(at, C.c_uint)), "polar_scf_decode_batch")
         return uh, fl, at
+
+    def decode_scan_device(self, d_in, sigma=0.0, out_bits=None, llr_u=None, ext_x=None):
+        """polar_scan_decode_device: soft-output SCAN.  llr_u and ext_x are optional tensors [B][N] of the decoder's dtype
+        (float64 or float32) on d_in's device: the LLR of every u bit (+inf at frozen positions) and the extrinsic LLR of
+        every code bit.  out_bits=False skips the hard decisions; None allocates them.  Returns out_bits (or None)."""
+        import torch
+        B = self._dev_rows(d_in)
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        elif out_bits is False:
+            out_bits = None
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        want = torch.float32 if self.dtype == F32 else torch.float64
+        for t in (llr_u, ext_x):
+            if t is not None and (t.numel() < B * self.N or t.dtype != want or not t.is_contiguous()):
+                raise ValueError(f"llr_u / ext_x must be contiguous {want} tensors of at least B*N elements")
+        self._check(self._lib.polar_scan_decode_device(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B,
+            C.c_void_p(out_bits.data_ptr()) if out_bits is not None else None,
+            C.c_void_p(llr_u.data_ptr()) if llr_u is not None else None,
+            C.c_void_p(ext_x.data_ptr()) if ext_x is not None else None), "polar_scan_decode_device")
+        return out_bits
+
+    def decode_scan_batch(self, llr):
+        """polar_scan_decode_batch: llr [B][N] -> (u_hat [B][N] int32, llr_u [B][N], ext_x [B][N]), the soft outputs in the
+        decoder's dtype."""
+        llr = self._rows(llr)
+        B = llr.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        soft = np.float32 if self.dtype == F32 else np.float64
+        lu = np.empty((B, self.N), dtype=soft)
+        ex = np.empty((B, self.N), dtype=soft)
+        self._check(self._lib.polar_scan_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
+                                                      C.c_void_p(lu.ctypes.data), C.c_void_p(ex.ctypes.data)),
+                    "polar_scan_decode_batch")
+        return uh, lu, ex
 
     def decode_bp_batch(self, llr):
         """polar_bp_decode_batch: llr [B][N] -> (u_hat [B][N] int32, iters [B] uint32, flags [B] uint32)."""
@@ -754,6 +803,15 @@ def SCFlip(N, K, T=8, crc_taps=CRC24C_TAPS, crc_file=None, **kw):
         dec = Decoder(N, K, ALGO_SCF, L=1, crc_taps=crc_taps, **kw)
     if T != 8:
         dec.set_scf_flips(T)
+    return dec
+
+
+def SCAN(N, K, iters=4, **kw):
+    """Soft-output SCAN (include/polar_hip.h, POLAR_ALGO_SCAN): BP's message arithmetic on SC's schedule, ``iters``
+    iterations; Decoder.decode_scan_device / decode_scan_batch return an LLR for every u bit and every code bit."""
+    dec = Decoder(N, K, ALGO_SCAN, L=1, **kw)
+    if iters != 4:
+        dec.set_scan_iters(iters)
     return dec
 
 

@@ -1,0 +1,61 @@
+// k_scan.hip -- k_scan_lanes (SCAN, one codeword per lane, scan_lanes.h) and its launch code
+#include "polar_host.h"
+#include "scan_lanes.h"
+
+namespace {
+
+// The stored betas make a wavefront's slice large (N = 1024, f64: 4.25 MiB), so the resident wavefronts are limited by a
+// byte budget for the ctx scratch as well as by the occupancy: at most 4 GiB.
+constexpr size_t SCAN_SCRATCH_BUDGET = (size_t)4 << 30;
+
+// like ensure(), but a failed allocation is POLAR_ENOMEM and leaves the ctx usable
+int ensure_scratch(polar_ctx *c, Buf &b, size_t bytes)
+{
+    if (b.cap >= bytes) return POLAR_OK;
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        c->last_error = "SCAN scratch: out of device memory";
+        return POLAR_ENOMEM;
+    }
+    if (e != hipSuccess) return fail(c, e, "hipMalloc(SCAN scratch)");
+    b.cap = bytes;
+    return POLAR_OK;
+}
+
+template <typename R, typename IN>
+int launch_scan_lanes(polar_ctx *c, const polar::ScanParams &P)
+{
+    using Cfg = polar::ScanCfg<R>;
+    auto kern = polar::k_scan_lanes<R, IN>;
+    const size_t lds = Cfg::lds_bytes();
+    const int threads = 64 * Cfg::WAVES;
+    int occ = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
+    if (occ < 1) occ = 1;
+    const size_t wg_bytes = Cfg::scratch_bytes(P.N, P.n) * Cfg::WAVES;
+    const long long batches = ((long long)P.B + 63) / 64;
+    long long grid = std::min<long long>((batches + Cfg::WAVES - 1) / Cfg::WAVES, (long long)occ * c->num_cu);
+    grid = std::min<long long>(grid, (long long)(SCAN_SCRATCH_BUDGET / wg_bytes));
+    if (grid < 1) grid = 1;
+    polar::ScanParams Q = P;
+    int rc = ensure_scratch(c, c->scratch, wg_bytes * (size_t)grid);
+    if (rc) return rc;
+    Q.scratch = c->scratch.p;
+    if (batches > grid * Cfg::WAVES && (rc = work_queue(c, c->scratch, &Q.queue))) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, c->stream, Q);
+    HIP_TRY(c, hipGetLastError());
+    return POLAR_OK;
+}
+
+}  // namespace
+
+int polar_tu::scan_lanes(polar_ctx *c, const polar::ScanParams &P, bool r32, bool in32)
+{
+    if (!r32) return in32 ? launch_scan_lanes<double, float>(c, P) : launch_scan_lanes<double, double>(c, P);
+    return in32 ? launch_scan_lanes<float, float>(c, P) : launch_scan_lanes<float, double>(c, P);
+}

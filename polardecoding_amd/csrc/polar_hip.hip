@@ -18,6 +18,7 @@
 #include "count_kernel.h"
 #include "gen_kernel.h"
 #include "scf_params.h"
+#include "scan_params.h"
 
 namespace {
 
@@ -333,11 +334,30 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     return POLAR_OK;
 }
 
+// SCAN (POLAR_ALGO_SCAN, include/polar_hip.h): one launch of k_scan_lanes, no host read-back.  Every output is nullable
+// here: the soft-output entry point may ask for LLRs only.
+int scan_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
+                uint32_t *d_flags, const uint32_t *d_frozen, void *d_llr_u, void *d_ext_x)
+{
+    const size_t rsz = c->cfg.dtype == POLAR_F32 ? 4 : 8;
+    if (!d_in || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % (in_is_f32 ? 4 : 8))) return POLAR_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_llr_u) | reinterpret_cast<uintptr_t>(d_ext_x)) % rsz) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    if (d_pm) HIP_TRY(c, hipMemsetAsync(d_pm, 0, B * sizeof(double), c->stream));
+    if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, B * sizeof(uint32_t), c->stream));
+    polar::ScanParams P{};
+    P.in = d_in; P.sigma = sigma; P.out_bits = d_bits; P.llr_u = d_llr_u; P.ext_x = d_ext_x; P.frozen = d_frozen;
+    P.N = c->cfg.N; P.n = c->n; P.B = (int)B; P.iters = c->scan_I;
+    return polar_tu::scan_lanes(c, P, c->cfg.dtype == POLAR_F32, in_is_f32 != 0);
+}
+
 // the decoder of ctx c on N-wide rows: the fixed decoder, or for a CA-SCL ctx with a stage rule the adaptive one, or SC-Flip.
 // d_iters: BP round trips per frame; CA-SCL: the list size that decided each frame; SC-Flip: the attempt that decided it.
 int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
-                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters)
+                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters, void *d_llr_u = nullptr,
+                        void *d_ext_x = nullptr)
 {
+    if (c && c->cfg.algo == POLAR_ALGO_SCAN) return scan_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_llr_u, d_ext_x);
     if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
     if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
         if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
@@ -353,11 +373,15 @@ int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double si
 // N-wide rows of the input type in ctx scratch (chunks of at most 256 MiB), which the ctx's own decoder reads with sigma = 0
 // (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (polar_fer_batch swaps it with rm_rows_b).
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
-                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
+                       double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr,
+                       void *d_llr_u = nullptr, void *d_ext_x = nullptr)
 {
-    if (!c || c->rm_mode == POLAR_RM_NONE) return decode_device_plain(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters);
+    if (!c || c->rm_mode == POLAR_RM_NONE)
+        return decode_device_plain(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters, d_llr_u, d_ext_x);
     const size_t esz = in_is_f32 ? 4 : 8;
-    if (!d_in || !d_bits || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
+    const bool scan = c->cfg.algo == POLAR_ALGO_SCAN;   // its three outputs are nullable
+    const size_t soft_row = (size_t)c->cfg.N * (c->cfg.dtype == POLAR_F32 ? 4 : 8);
+    if (!d_in || (!d_bits && !scan) || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     const size_t row = (size_t)c->cfg.N * esz;
     const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
@@ -368,8 +392,10 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
         if ((rc = polar_tu::rm_recover(c, (const char *)d_in + off * (size_t)c->rm_E * esz, in_is_f32 != 0, sigma, nc,
                                        c->rm_rows.p)))
             return rc;
-        if ((rc = decode_device_plain(c, c->rm_rows.p, in_is_f32, 0.0, nc, d_bits + off * (size_t)c->NW, d_pm ? d_pm + off : nullptr,
-                                      d_flags ? d_flags + off : nullptr, d_frozen, d_iters ? d_iters + off : nullptr)))
+        if ((rc = decode_device_plain(c, c->rm_rows.p, in_is_f32, 0.0, nc, d_bits ? d_bits + off * (size_t)c->NW : nullptr,
+                                      d_pm ? d_pm + off : nullptr, d_flags ? d_flags + off : nullptr, d_frozen,
+                                      d_iters ? d_iters + off : nullptr, d_llr_u ? (char *)d_llr_u + off * soft_row : nullptr,
+                                      d_ext_x ? (char *)d_ext_x + off * soft_row : nullptr)))
             return rc;
     }
     return POLAR_OK;
@@ -395,6 +421,7 @@ void refresh_kernel_name(polar_ctx *c)
     if (g.algo == POLAR_ALGO_SCF)
         snprintf(nm, sizeof nm, "k_scf_lanes<%s> (SC-Flip, T=%d; pass A, k_ad_fail_count/scan/write, record, pass B, k_scf_resolve)",
                  ty, c->scf_T);
+    if (g.algo == POLAR_ALGO_SCAN) snprintf(nm, sizeof nm, "k_scan_lanes<%s> (SCAN, I=%d)", ty, c->scan_I);
     c->kernel_name = nm;
     if (!c->cascl_stages.empty()) {
         sync_stage_ctx(c);
@@ -627,14 +654,15 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     const int N = cfg->N;
     if (N < 32 || N > 4096 || (N & (N - 1))) return POLAR_EINVAL;
     if (cfg->K < 1 || cfg->crc_r < 0 || cfg->crc_r > 32 || cfg->K + cfg->crc_r > N) return POLAR_EINVAL;
-    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCF) return POLAR_EINVAL;
+    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCAN) return POLAR_EINVAL;
     if (cfg->dtype != POLAR_F64 && cfg->dtype != POLAR_F32) return POLAR_EINVAL;
     int L = cfg->L;
-    if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF) L = 1;
+    if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF || cfg->algo == POLAR_ALGO_SCAN) L = 1;
     if (L < 1 || L > 32 || (L & (L - 1))) return POLAR_EINVAL;
     if (has_crc(cfg->algo) && (cfg->crc_r < 1 || !cfg->crc_taps || cfg->n_taps < 2)) return POLAR_EINVAL;
     if (cfg->algo == POLAR_ALGO_BP && cfg->bp_iters < 1) return POLAR_EINVAL;
     if (cfg->algo == POLAR_ALGO_SCF && N > 2048) return POLAR_ENOKERNEL;   // one codeword per lane: N <= 2048
+    if (cfg->algo == POLAR_ALGO_SCAN && N > polar::SCAN_MAX_N) return POLAR_ENOKERNEL;
 
     polar_ctx *c = new (std::nothrow) polar_ctx();
     if (!c) return POLAR_ENOMEM;
@@ -755,7 +783,7 @@ void polar_destroy(polar_ctx *c)
     }
     for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
     for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
-                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->rm_rows, &c->rm_rows_b, &c->genie_rows})
+                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->scan_llr, &c->scan_ext, &c->rm_rows, &c->rm_rows_b, &c->genie_rows})
         if (b->p) (void)hipFree(b->p);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
@@ -845,7 +873,7 @@ int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out)
     if (!cfg || !out) return POLAR_EINVAL;
     *out = nullptr;
     if (cfg->info_order || (ibil != 0 && ibil != 1)) return POLAR_EINVAL;
-    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCF) return POLAR_EINVAL;
+    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCAN) return POLAR_EINVAL;
     const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
     if (cfg->K < 1 || r < 0 || r > 32) return POLAR_EINVAL;
     const int N = cfg->N, A = cfg->K + r;
@@ -1030,6 +1058,53 @@ int polar_scf_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_
 {
     if (!c || c->cfg.algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
     return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, nullptr, flags, attempts);
+}
+
+int polar_scan_set_iters(polar_ctx *c, int I)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCAN || I < 1 || I > polar::SCAN_MAX_ITERS) return POLAR_EINVAL;
+    c->scan_I = I;
+    refresh_kernel_name(c);
+    return POLAR_OK;
+}
+
+int polar_scan_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                             void *d_llr_u, void *d_ext_x)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCAN) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, nullptr, nullptr, c->d_frozen, nullptr, d_llr_u, d_ext_x);
+}
+
+// the soft outputs are [B][N] of the ctx dtype: the batch goes through the device buffers in one piece
+int polar_scan_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, void *llr_u, void *ext_x)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCAN || !llr_in) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    if (B > 0x7fffffffull) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    const int N = c->cfg.N, NW = c->NW;
+    const size_t W = c->rm_mode != POLAR_RM_NONE ? (size_t)c->rm_E : (size_t)N;
+    const size_t soft = B * (size_t)N * (c->cfg.dtype == POLAR_F32 ? 4 : 8);
+    int rc;
+    if ((rc = ensure(c, c->in, B * W * sizeof(double)))) return rc;
+    if (u_hat && (rc = ensure(c, c->bits, B * NW * sizeof(uint32_t)))) return rc;
+    if (llr_u && (rc = ensure(c, c->scan_llr, soft))) return rc;
+    if (ext_x && (rc = ensure(c, c->scan_ext, soft))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->in.p, llr_in, B * W * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = decode_device_impl(c, c->in.p, 0, 0.0, B, u_hat ? (uint32_t *)c->bits.p : nullptr, nullptr, nullptr, c->d_frozen,
+                                 nullptr, llr_u ? c->scan_llr.p : nullptr, ext_x ? c->scan_ext.p : nullptr)))
+        return rc;
+    std::vector<uint32_t> w;
+    if (u_hat) {
+        w.resize(B * (size_t)NW);
+        HIP_TRY(c, hipMemcpyAsync(w.data(), c->bits.p, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (llr_u) HIP_TRY(c, hipMemcpyAsync(llr_u, c->scan_llr.p, soft, hipMemcpyDeviceToHost, c->stream));
+    if (ext_x) HIP_TRY(c, hipMemcpyAsync(ext_x, c->scan_ext.p, soft, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t f = 0; u_hat && f < B; ++f) unpack_words(w.data() + f * NW, NW, u_hat + f * (size_t)N);
+    return POLAR_OK;
 }
 
 int polar_cascl_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,

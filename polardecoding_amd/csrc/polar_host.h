@@ -17,6 +17,7 @@
 namespace polar {
 struct ScfParams;   // scf_params.h
 struct GenParams;   // gen_common.h
+struct ScanParams;  // scan_lanes.h
 }
 
 struct PolarBuf {
@@ -55,6 +56,8 @@ struct polar_ctx {
     // SC-Flip (POLAR_ALGO_SCF): flip budget T (polar_scf_set_flips), the failing frames' flip positions, pass B's pairs
     int scf_T = 8;
     Buf scf_flips, scf_pass, scf_bits;
+    int scan_I = 4;                       // SCAN (POLAR_ALGO_SCAN): iterations (polar_scan_set_iters)
+    Buf scan_llr, scan_ext;               // polar_scan_decode_batch: staging of the soft outputs
     // 5G rate matching (polar_create_rm): E, POLAR_RM_* mode (POLAR_RM_NONE: a plain ctx), channel interleaver, its tables
     // (sent-row position of e_k, and the inverse) and the recovered rows, one buffer per stream of polar_fer_batch
     int rm_E = 0, rm_mode = POLAR_RM_NONE, rm_ibil = 0;
@@ -167,6 +170,8 @@ int rm_generate(polar_ctx *c, const polar::GenParams &G);
 int genie_count(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t B, unsigned long long *d_counts);
 int genie_rows(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B, void *d_out,
                bool out32);
+// k_scan.hip: SCAN (scan_lanes.h), 32 <= N <= 1024
+int scan_lanes(polar_ctx *c, const polar::ScanParams &P, bool r32, bool in32);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

@@ -209,11 +209,12 @@ static int construct_order(int N, int dtype, long long frames, double sigma, uin
 
 static void usage(void)
 {
-    fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
+    fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf|scan --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
                     "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
                     "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n"
+                    "                 [--iters I]   (scan: soft-output SCAN with I iterations, 1..64; default 4)\n"
                     "                 [--construct frames --design-snr db [--q-out file]]   (Monte-Carlo construction of the order on the device first;\n"
                     "                                  --q-out: write it in the format --q reads)\n"
                     "                 [--E e [--ibil]]   (--fast only: 5G rate matching, e channel values per codeword; --ibil: channel interleaver)\n");
@@ -226,6 +227,7 @@ int main(int argc, char **argv)
     int fast = 0, sys = 0, bpr = 0, gpus = 1, bp_stop = POLAR_BP_STOP_NONE;
     int stages[6], nstages = 0;   /* --stages: polar_cascl_set_stages */
     int flips = -1;               /* --flips: polar_scf_set_flips (-1: the library's default) */
+    int scan_iters = -1;          /* --iters: polar_scan_set_iters (-1: the library's default) */
     int rm_E = 0, rm_ibil = 0;    /* --E / --ibil: polar_create_rm (0: no rate matching) */
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
@@ -243,7 +245,7 @@ int main(int argc, char **argv)
             if (!strcmp(v, "bpr")) { bpr = 1; v = "bp"; bp_iters = 90; }   /* BPr_128.c: iterMax 90 (:16) */
             algo = !strcmp(v, "sc") ? POLAR_ALGO_SC : !strcmp(v, "bp") ? POLAR_ALGO_BP
                  : !strcmp(v, "scl") ? POLAR_ALGO_SCL : !strcmp(v, "cascl") ? POLAR_ALGO_CASCL
-                 : !strcmp(v, "scf") ? POLAR_ALGO_SCF : -1;
+                 : !strcmp(v, "scf") ? POLAR_ALGO_SCF : !strcmp(v, "scan") ? POLAR_ALGO_SCAN : -1;
             if (algo < 0) usage();
             i++;
         } else if (!strcmp(a, "--N") && v) { N = atoi(v); i++; }
@@ -286,6 +288,12 @@ int main(int argc, char **argv)
             char *end;
             flips = (int)strtol(v, &end, 10);
             if (end == v || *end) usage();
+            i++;
+        }
+        else if (!strcmp(a, "--iters") && v) {
+            char *end;
+            scan_iters = (int)strtol(v, &end, 10);
+            if (end == v || *end || scan_iters < 0) usage();
             i++;
         }
         else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : POLAR_F64; i++; }
@@ -414,6 +422,12 @@ int main(int argc, char **argv)
         if (fast && gpus > 1) { fprintf(stderr, "--flips: not with --gpus > 1\n"); return 1; }
         if ((rc = polar_scf_set_flips(ctx, flips)) != 0) { fprintf(stderr, "--flips: %s\n", polar_strerror(rc)); return 1; }
     }
+    if (scan_iters >= 0) {
+        /* a polar_group builds its contexts from cfg and runs the default I */
+        if (algo != POLAR_ALGO_SCAN) { fprintf(stderr, "--iters: only with --algo scan\n"); return 1; }
+        if (fast && gpus > 1) { fprintf(stderr, "--iters: not with --gpus > 1\n"); return 1; }
+        if ((rc = polar_scan_set_iters(ctx, scan_iters)) != 0) { fprintf(stderr, "--iters: %s\n", polar_strerror(rc)); return 1; }
+    }
     /* the library built the frozen set from the 5G sequence like the reference (I[i] = Q[N-(K+r)+i]);
        the encoder needs the same I[] */
     c.I = (int *)malloc(sizeof(int) * (size_t)c.A);
@@ -521,7 +535,7 @@ int main(int argc, char **argv)
             }
             printf("BLER = %lfe-2\tBER = %lfe-2\tK * BER = %lf\n", (double)errblock * 100 / run,
                    (double)errbit * 100 / K / run, (double)errbit / run);
-        } else if (algo == POLAR_ALGO_SC || algo == POLAR_ALGO_BP || (algo == POLAR_ALGO_SCF && !c.sys)) {
+        } else if (algo == POLAR_ALGO_SC || algo == POLAR_ALGO_BP || algo == POLAR_ALGO_SCAN || (algo == POLAR_ALGO_SCF && !c.sys)) {
             printf("bSNR = %.2lf\terror block = %d\trun = %ld\tBLER = %lf\n", db, errblock, run, (double)errblock / run);
             printf("Error bit = %ld\tBER = %lf\n", errbit, (double)errbit / K / run);
         } else if (c.sys) { /* CASCL_1024_sys.c:832-835 */

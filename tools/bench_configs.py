@@ -28,7 +28,7 @@ CONFIGS = [
     ("CASCL_128_L8", lambda: pa.CASCL(128, 64, L=8, crc_taps=pa.CRC6_TAPS, dtype=dt), 128, 1 << 18),
     ("SCL_1024_L32", lambda: pa.SCLdecode(1024, 512, L=32, dtype=dt), 1024, 1 << 14),
     ("CASCL_4096_L32", lambda: pa.CASCL(4096, 2048, L=32, dtype=dt), 4096, 1 << 15),
-]
+] + [(f"SCAN_{n}_I{i}", lambda n=n, i=i: pa.SCAN(n, n // 2, iters=i, dtype=dt), n, 1 << 17) for n in (1024, 128) for i in (1, 2, 4)]
 for name, mk, N, B in CONFIGS:
     if args.only and args.only not in name:
         continue
