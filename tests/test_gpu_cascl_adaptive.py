@@ -98,19 +98,20 @@ def _lib_composition(N, K, taps, stages, x, sigma=0.0, **kw):
     return compose(outs, passes)
 
 
-def _oracle_composition(oracle, code, taps, stages, llr):
+def _oracle_composition(oracle, code, taps, stages, llr, dtype="f64"):
     """The rule's output from the oracle: SC of the code with the CRC positions as information bits, CA-SCL with L_s;
-    flags = TIE from the oracle's ties, CRC_PASS from the syndrome of the chosen path."""
+    flags = TIE from the oracle's ties, CRC_PASS from the syndrome of the chosen path.  dtype "f32": the oracle in float
+    (the metrics are floats, returned widened)."""
     io = code.info_order
     outs, passes = [], []
     for L in stages:
         if L == 1:
             q = [j for j in range(code.N) if j not in set(io.tolist())] + io.tolist()
             sc = oracle.Code(code.N, code.A, None, Q=q)
-            uh, _, _ = oracle.decode(sc, llr, "SC")
+            uh, _, _ = oracle.decode(sc, llr, "SC", dtype=dtype)
             pm, ties = np.zeros(len(llr)), np.zeros(len(llr), dtype=np.int64)
         else:
-            uh, pm, ties = oracle.decode(code, llr, "CASCL", L=L)
+            uh, pm, ties = oracle.decode(code, llr, "CASCL", L=L, dtype=dtype)
         ok = syndrome(uh, io, taps) == 0
         fl = np.where(ties > 0, FLAG_TIE, 0) | np.where(ok, FLAG_CRC_PASS, 0)
         outs.append((L, uh, np.asarray(pm, dtype=np.float64), fl))

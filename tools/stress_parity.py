@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Differential sweep GPU (through the C ABI) vs the CPU oracle over many shapes: every kernel family, list sizes,
 code lengths, rates, CRCs, both arithmetic types, ragged batch sizes.  Developer tool (tests/ holds the fixed cases)."""
-import itertools, os, sys, time
+import argparse, itertools, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import polardecoding_amd as pa
 from oracle import oracle_py as O
 
-rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 2026)   # optional argument: another seed (other batch sizes and frames)
+ap = argparse.ArgumentParser()
+ap.add_argument("seed", nargs="?", type=int, default=2026, help="another seed: other batch sizes and frames")
+ap.add_argument("--inputs", choices=("gaussian", "grid", "hard"), default="gaussian",
+                help="grid: LLRs rounded to step 1, clipped to +-7; hard: +-1 with the channel sign (dense with ties)")
+args = ap.parse_args()
+rng = np.random.default_rng(args.seed)
 bad = 0
 t0 = time.time()
 
@@ -24,6 +29,10 @@ def check(tag, dec, code, algo, L, B, db, dtype, iters=20):
     sig = O.sigma_from_db(db)
     us, ys = sim.frames(code, sig, B)
     llr = np.stack([O.llr_from_y(y, sig) for y in ys]).astype(np.float32).astype(np.float64)
+    if args.inputs == "grid":
+        llr = np.clip(np.rint(llr), -7, 7)
+    elif args.inputs == "hard":
+        llr = np.where(np.signbit(llr), -1.0, 1.0)
     ref, rpm, _ = O.decode(code, llr, algo, L=L, bp_iters=iters, dtype=dtype)
     uh, pm, fl = dec.decode_batch(llr)
     ok = np.array_equal(uh, ref) and (dtype == "f32" or algo in ("SC", "BP") or np.array_equal(pm, rpm))
