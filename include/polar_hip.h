@@ -333,7 +333,7 @@ int polar_scan_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int 
  *      I[0..A) = the A most reliable positions of the context's reliability order (the 5G sequence restricted to < N) that
  *      are not in Q_F,tmp, in ascending reliability: the library's own convention (CRC word w[i] -> u[I[i]]).  The 38.212
  *      placement of payload and CRC bits inside the information set, the input interleaver (I_IL), PC bits, distributed
- *      CRC and code-block segmentation are NOT part of this.
+ *      CRC and code-block segmentation are NOT part of this (PC bits at E = N: polar_create_dyn / polar_dyn_pc5g below).
  *   5. N selection (5.3.1), a helper: n1 = ceil(log2 E) - 1 if E <= (9/8) 2^(ceil(log2 E)-1) and 16 A < 9 E, else
  *      ceil(log2 E); n2 = ceil(log2 (8A)); n = max(min(n1, n2, n_max), 5), n_max = 9 or 10.
  *   6. recovery (receiver): a row of E received values becomes the N-wide row the decoders read.  The channel interleaver is
@@ -411,6 +411,68 @@ int polar_construct_batch(polar_ctx *ctx, unsigned long long seed, unsigned long
 /* rule 4 on host counters [2][N].  Host only, touches no device.  POLAR_EINVAL for N not a power of two in 32..4096, NULL
  * counts / out, or a base order that is not a permutation of 0..N-1. */
 int polar_construct_order(int N, const uint64_t *counts, const int *base_order, int *out);
+
+/* --- Dynamic frozen bits: PAC codes, the parity-check bits of 5G PC-polar codes (no reference counterpart) ----------------
+ * A frozen position need not carry the constant 0: a dynamic frozen bit carries a GF(2) linear function of earlier decided
+ * bits of the same path.  That one mechanism covers polarization-adjusted convolutional (PAC) codes (Arikan 2019), the
+ * parity-check bits of TS 38.212 5.3.1.2 (n_PC > 0: the uplink cases 18 <= K <= 25), eBCH-polar subcodes and any
+ * lower-triangular precoding.  A dynamic context is the plain decoder of its polar_cfg plus a set Dyn of positions and a set
+ * S_j for every j in Dyn:
+ *   1. algo is POLAR_ALGO_SC, POLAR_ALGO_SCL or POLAR_ALGO_CASCL; L a power of two in 1..32; both dtypes; 32 <= N <= 1024.
+ *   2. Dyn is a set of positions that are frozen under the cfg.  S_j is a subset of {0 .. j-1}; a member may be an
+ *      information position, a plain frozen one (always 0) or an earlier dynamic one.
+ *   3. At leaf j, for every live path, u_hat_0 .. u_hat_{j-1} are that path's decided bits and lambda its leaf LLR.  An
+ *      information or plain frozen leaf is handled exactly as in the plain decoder.
+ *   4. j in Dyn: b = XOR over i in S_j of u_hat_i, and u_hat_j = b.  In SC nothing else happens.  In SCL and CA-SCL
+ *      PM = PM + PHI(lambda, b): the expression and the single rounding an information leaf uses for its branch with bit b
+ *      (T(|lambda|) + max(-lambda, 0) for b = 0, T(|lambda|) + max(lambda, 0) for b = 1, then one addition to PM).  No
+ *      fork, no ranking, no tie flag.  The partial sums proceed with b.
+ *   5. The CRC remainder takes no contribution from any frozen position, dynamic ones included.
+ *   6. Outputs: u_hat carries b at dynamic positions, not 0.  Path choice, metric and flags are otherwise those of the plain
+ *      decoder.
+ *   7. Identity: with every S_j empty, bits, metric and flags equal those of the plain context of the same cfg, bit for bit.
+ *   8. Everything is decoded in the u domain.  For a PAC code the payload is v = u T^-1 on the information positions: a host
+ *      step (polar_pac_unprecode), not a kernel step.  polar_count_errors_device keeps counting on the K + r unfrozen u
+ *      positions: block errors are those of the payload (the map is a bijection), bit errors are u-domain bit errors.
+ *   9. polar_generate_device on a dynamic context: payload, CRC and their placement are the plain context's for the same seed
+ *      and frame, then the dynamic bits are filled in ascending position, then encode and channel with the plain context's
+ *      noise.  d_u_bits carries the dynamic bits.
+ * Honoured by polar_decode, polar_decode_batch(_y) (a frozen_mask override returns POLAR_EINVAL), polar_decode_device,
+ * polar_generate_device, polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device, polar_kernel_name
+ * ("k_scl_dyn<...>"), polar_ctx_info, polar_info_order and the polar_genie_* calls (which work on any ctx and ignore the
+ * constraints).  polar_cascl_*, polar_bp_*, polar_scf_* and polar_scan_* return POLAR_EINVAL on a dynamic ctx.
+ * Out of scope: dynamic bits on polar_create_rm / polar_create_crc_file contexts (so 5G PC-polar is covered at E = N only),
+ * polar_group_* and polar_fer_multi_gpu (they build plain contexts from a polar_cfg), a CRC in the v domain for PAC, Fano or
+ * sequential decoding. */
+typedef struct polar_dyn {
+    int D;           /* number of dynamic positions (0 is allowed: the same kernel with no constraint)            */
+    const int *pos;  /* [D] strictly ascending, each frozen under the cfg                                        */
+    const int *ptr;  /* [D+1] CSR row starts, ptr[0] = 0                                                         */
+    const int *idx;  /* [ptr[D]] row d = S_{pos[d]}: strictly ascending, every entry < pos[d]                    */
+} polar_dyn;
+/* polar_create plus the constraints.  POLAR_EINVAL: a NULL or malformed dyn, a position that is unfrozen under the cfg, an
+ * algo other than SC / SCL / CA-SCL; POLAR_ENOKERNEL: N > 1024.  Both before any device is touched. */
+int polar_create_dyn(const polar_cfg *cfg, const polar_dyn *dyn, polar_ctx **out);
+/* D and the positions of a dynamic ctx (pos nullable, [D]); a ctx not made by polar_create_dyn reports D = -1. */
+int polar_dyn_info(const polar_ctx *ctx, int *D, int *pos);
+/* Host-only helpers that fill caller arrays in the polar_dyn layout (touch no device).  pos [D], ptr [D+1], idx [idx_cap];
+ * *nnz (nullable) = entries of idx needed.  idx may be NULL to ask for the sizes only; a non-NULL idx with idx_cap < *nnz is
+ * POLAR_EINVAL.
+ * PAC: the rate-1 convolutional precoder u = v T, T_ij = g_{j-i}, g given by its exponents g_taps (g_0 = 1 required), v zero
+ * outside the information set info_order[0..A).  Every position outside the information set becomes dynamic, D = N - A,
+ * with S_j = {i < j : h_{j-i} = 1}, h = 1 / g(D) mod D^N. */
+int polar_dyn_pac(int N, const int *info_order, int A, const int *g_taps, int n_taps, int *pos, int *ptr, int *idx,
+                  int idx_cap, int *nnz);
+/* bit rows [B][N] of 0/1 ints: u = v T and v = u T^-1 (u and v must not overlap) */
+int polar_pac_precode(int N, const int *g_taps, int n_taps, const int *v, size_t B, int *u);
+int polar_pac_unprecode(int N, const int *g_taps, int n_taps, const int *u, size_t B, int *v);
+/* 38.212 5.3.1.2: q_i[0..n_qi) = Q_I in ascending reliability, n_qi = K + n_PC (K counting the CRC).  The first
+ * n_pc - n_pc_wm PC positions are the least reliable members of Q_I; the other n_pc_wm are the members of minimum row weight
+ * 2^popcount(j) among the n_qi - n_pc most reliable, equal weights to the higher reliability.  The value rule is the
+ * standard's 5-stage cyclic register; as sets, S_j = {i < j : i in Q_I \ Q_PC, i = j (mod 5)}.  Fills pos [n_pc],
+ * ptr [n_pc+1], idx, and info_order [n_qi - n_pc]: Q_I \ Q_PC in ascending reliability, which is what cfg.info_order takes. */
+int polar_dyn_pc5g(int N, const int *q_i, int n_qi, int n_pc, int n_pc_wm, int *pos, int *ptr, int *idx, int idx_cap,
+                   int *nnz, int *info_order);
 
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at

@@ -38,6 +38,10 @@ class _Cfg(C.Structure):
                 ("crc_systematic", C.c_int)]
 
 
+class _Dyn(C.Structure):
+    _fields_ = [("D", C.c_int), ("pos", C.POINTER(C.c_int)), ("ptr", C.POINTER(C.c_int)), ("idx", C.POINTER(C.c_int))]
+
+
 class _CrcMatrix(C.Structure):
     _fields_ = [("K", C.c_int), ("r", C.c_int), ("n_taps", C.c_int), ("taps", C.c_int * 33),
                 ("rows", C.POINTER(C.c_uint32))]
@@ -129,6 +133,12 @@ def load_library(testing=False):
     L.polar_genie_rows_device.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp, C.c_int]
     L.polar_construct_batch.argtypes = [vp, C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_size_t, vp]
     L.polar_construct_order.argtypes = [C.c_int, C.POINTER(C.c_uint64), ip, ip]
+    L.polar_create_dyn.argtypes = [C.POINTER(_Cfg), C.POINTER(_Dyn), C.POINTER(vp)]
+    L.polar_dyn_info.argtypes = [vp, ip, ip]
+    L.polar_dyn_pac.argtypes = [C.c_int, ip, C.c_int, ip, C.c_int, ip, ip, ip, C.c_int, ip]
+    L.polar_pac_precode.argtypes = [C.c_int, ip, C.c_int, ip, C.c_size_t, ip]
+    L.polar_pac_unprecode.argtypes = [C.c_int, ip, C.c_int, ip, C.c_size_t, ip]
+    L.polar_dyn_pc5g.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, ip, ip]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -195,6 +205,84 @@ def rm_info_order(N, A, E):
     return out[:int(A)]
 
 
+def pac_taps(g):
+    """Exponents of a PAC generator polynomial.  An int is read as the usual octal shorthand with its most significant bit
+    as g_0 (0o133 = 1011011 -> g_0 g_1 .. g_6 = 1,0,1,1,0,1,1 -> exponents 0, 2, 3, 5, 6); a sequence is taken as exponents."""
+    if isinstance(g, (int, np.integer)):
+        bits = bin(int(g))[2:]
+        return tuple(i for i, c in enumerate(bits) if c == "1")
+    return tuple(int(t) for t in g)
+
+
+def _csr_sets(pos, ptr, idx):
+    return [idx[ptr[d]:ptr[d + 1]].copy() for d in range(len(pos))]
+
+
+def dyn_pac(N, info_order, g=0o133):
+    """polar_dyn_pac: the dynamic frozen bits of the PAC code with information set `info_order` and precoder polynomial g
+    (pac_taps) -> (pos, sets): every position outside the information set, and per position the earlier positions whose
+    decided bits it is the XOR of.  Feeds ``Decoder(..., dyn=(pos, sets))``.  Host only."""
+    lib = load_library()
+    io = np.ascontiguousarray(info_order, dtype=np.int32)
+    t = np.asarray(pac_taps(g), dtype=np.int32)
+    D = int(N) - io.size
+    pos = np.zeros(max(D, 1), dtype=np.int32)
+    ptr = np.zeros(D + 1, dtype=np.int32)
+    nnz = C.c_int(0)
+    args = (int(N), _ptr(io, C.c_int), io.size, _ptr(t, C.c_int), t.size, _ptr(pos, C.c_int), _ptr(ptr, C.c_int))
+    rc = lib.polar_dyn_pac(*args, None, 0, C.byref(nnz))
+    idx = np.zeros(max(nnz.value, 1), dtype=np.int32)
+    if rc == 0:
+        rc = lib.polar_dyn_pac(*args, _ptr(idx, C.c_int), idx.size, None)
+    if rc != 0:
+        raise PolarError(f"polar_dyn_pac: {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return pos[:D], _csr_sets(pos[:D], ptr, idx)
+
+
+def _pac_rows(fn, N, g, rows):
+    lib = load_library()
+    a = np.ascontiguousarray(rows, dtype=np.int32)
+    if a.ndim == 0 or a.shape[-1] != N:
+        raise ValueError(f"rows must have {N} bits")
+    t = np.asarray(pac_taps(g), dtype=np.int32)
+    out = np.zeros_like(a)
+    rc = getattr(lib, fn)(int(N), _ptr(t, C.c_int), t.size, _ptr(a, C.c_int), a.size // N, _ptr(out, C.c_int))
+    if rc != 0:
+        raise PolarError(f"{fn}: {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return out
+
+
+def pac_precode(v, g=0o133):
+    """polar_pac_precode: bit rows [..][N], u = v T (T_ij = g_{j-i}); v is zero outside the information set."""
+    return _pac_rows("polar_pac_precode", np.shape(v)[-1], g, v)
+
+
+def pac_unprecode(u, g=0o133):
+    """polar_pac_unprecode: bit rows [..][N], v = u T^-1: the payload of a decoded PAC row sits at the information positions."""
+    return _pac_rows("polar_pac_unprecode", np.shape(u)[-1], g, u)
+
+
+def dyn_pc5g(N, q_i, n_pc=3, n_pc_wm=0):
+    """polar_dyn_pc5g (38.212 5.3.1.2): q_i = Q_I in ascending reliability (K + n_pc entries, K counting the CRC) ->
+    (pos, sets, info_order): the PC positions, their sets, and Q_I without them in ascending reliability (what
+    ``Decoder(info_order=...)`` takes).  Host only."""
+    lib = load_library()
+    q = np.ascontiguousarray(q_i, dtype=np.int32)
+    D = int(n_pc)
+    pos = np.zeros(max(D, 1), dtype=np.int32)
+    ptr = np.zeros(D + 1, dtype=np.int32)
+    info = np.zeros(max(q.size - D, 1), dtype=np.int32)
+    nnz = C.c_int(0)
+    args = (int(N), _ptr(q, C.c_int), q.size, D, int(n_pc_wm), _ptr(pos, C.c_int), _ptr(ptr, C.c_int))
+    rc = lib.polar_dyn_pc5g(*args, None, 0, C.byref(nnz), _ptr(info, C.c_int))
+    idx = np.zeros(max(nnz.value, 1), dtype=np.int32)
+    if rc == 0:
+        rc = lib.polar_dyn_pc5g(*args, _ptr(idx, C.c_int), idx.size, None, _ptr(info, C.c_int))
+    if rc != 0:
+        raise PolarError(f"polar_dyn_pc5g: {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return pos[:D], _csr_sets(pos[:D], ptr, idx), info[:q.size - D]
+
+
 def construct_order(N, counts, base_order=None):
     """polar_construct_order (include/polar_hip.h, Monte-Carlo construction rule 4): counts [2][N] (err row, tie row) -> the
     N positions in ascending reliability (descending 2*err + tie, equal scores in `base_order`; None: the library's own order
@@ -240,12 +328,16 @@ class Decoder:
     """One polar_ctx: a (N, K, CRC, L, algo, dtype) configuration bound to one GPU."""
 
     def __init__(self, N, K, algo, L=1, crc_taps=None, bp_iters=100, dtype=F64, device=0, info_order=None,
-                 systematic=False, crc_file=None, E=None, ibil=False, _library=None):
-        """E: 5G rate matching (polar_create_rm): every decode takes rows of E channel values and generate_device writes
+                 systematic=False, crc_file=None, E=None, ibil=False, dyn=None, _library=None):
+        """dyn = (pos, sets): dynamic frozen bits (polar_create_dyn): pos ascending frozen positions, sets[d] the earlier
+        positions whose decided bits u_hat[pos[d]] is the XOR of (SC / SCL / CA-SCL only; see dyn_pac, dyn_pc5g).
+        E: 5G rate matching (polar_create_rm): every decode takes rows of E channel values and generate_device writes
         them; ibil: with the channel interleaver (uplink)."""
         self._h = C.c_void_p()
         if E is not None and crc_file is not None:
             raise ValueError("E (rate matching) and crc_file exclude each other: polar_create_crc_file takes no E")
+        if dyn is not None and (E is not None or crc_file is not None):
+            raise ValueError("dyn (dynamic frozen bits) excludes E and crc_file")
         self._lib = _library if _library is not None else load_library()
         self.N, self.K, self.algo, self.dtype, self.device = N, K, algo, dtype, device
         taps = np.asarray(list(crc_taps) if crc_taps else [0], dtype=np.int32)
@@ -268,6 +360,16 @@ class Decoder:
         self.scf_flips = None   # None: the library's default (min(8, K + r))
         self.scan_iters = None  # None: the library's default (4)
         self._rm = (int(E), 1 if ibil else 0) if E is not None else None
+        self._dyn = None
+        if dyn is not None:
+            dpos = np.ascontiguousarray(dyn[0], dtype=np.int32).ravel()
+            sets = [np.asarray(s, dtype=np.int32).ravel() for s in dyn[1]]
+            if len(sets) != dpos.size:
+                raise ValueError("dyn = (pos, sets) needs one set per position")
+            dptr = np.zeros(dpos.size + 1, dtype=np.int32)
+            dptr[1:] = np.cumsum([s.size for s in sets])
+            didx = np.ascontiguousarray(np.concatenate(sets + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+            self._dyn = (dpos, dptr, didx)
         self._create()
         A, Lr = C.c_int(), C.c_int()
         self._lib.polar_ctx_info(self._h, None, None, C.byref(A), C.byref(Lr), None, None)
@@ -279,7 +381,11 @@ class Decoder:
         self._w = self.E   # values per input row of every decode entry point
 
     def _create(self):
-        if self._rm is not None:
+        if self._dyn is not None:
+            dpos, dptr, didx = self._dyn
+            d = _Dyn(dpos.size, _ptr(dpos, C.c_int), _ptr(dptr, C.c_int), _ptr(didx, C.c_int))
+            rc = self._lib.polar_create_dyn(C.byref(self._cfg), C.byref(d), C.byref(self._h))
+        elif self._rm is not None:
             rc = self._lib.polar_create_rm(C.byref(self._cfg), self._rm[0], self._rm[1], C.byref(self._h))
         elif self._crc_file is not None:
             rc = self._lib.polar_create_crc_file(C.byref(self._cfg), self._crc_file, C.byref(self._h))
@@ -311,6 +417,17 @@ class Decoder:
         out = np.zeros(self.A, dtype=np.int32)
         self._check(self._lib.polar_info_order(self._h, _ptr(out, C.c_int), self.A), "polar_info_order")
         return out
+
+    @property
+    def dyn_positions(self):
+        """polar_dyn_info: the dynamic frozen positions (ascending), or None on a decoder made without dyn."""
+        D = C.c_int()
+        self._check(self._lib.polar_dyn_info(self._h, C.byref(D), None), "polar_dyn_info")
+        if D.value < 0:
+            return None
+        out = np.zeros(max(D.value, 1), dtype=np.int32)
+        self._check(self._lib.polar_dyn_info(self._h, None, _ptr(out, C.c_int)), "polar_dyn_info")
+        return out[:D.value]
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -813,6 +930,38 @@ def SCAN(N, K, iters=4, **kw):
     if iters != 4:
         dec.set_scan_iters(iters)
     return dec
+
+
+def pac_info_order(N, K, profile="rm"):
+    """Information set of a PAC code in ascending reliability.  "rm": the K positions of largest popcount(j) (the
+    Reed-Muller rate profile), ties to the more reliable in the library's order; "5g": the K most reliable."""
+    q = q_sequence(N)
+    if profile == "5g":
+        return np.asarray(q[N - K:], dtype=np.int32)
+    if profile != "rm":
+        raise ValueError("profile must be 'rm' or '5g'")
+    rel = {j: i for i, j in enumerate(q)}
+    best = sorted(range(N), key=lambda j: (bin(j).count("1"), rel[j]))[N - K:]
+    return np.asarray(sorted(best, key=lambda j: rel[j]), dtype=np.int32)
+
+
+def PAC(N, K, g=0o133, L=32, profile="rm", **kw):
+    """Polarization-adjusted convolutional code under list decoding (include/polar_hip.h, dynamic frozen bits): SCL (SC for
+    L = 1) over the rate profile `profile` (pac_info_order) with every other position a dynamic frozen bit of the precoder g.
+    Decisions are u-domain rows; ``pac_unprecode(u_hat, g)[..., dec.info_order]`` is the payload."""
+    io = pac_info_order(N, K, profile)
+    dec = Decoder(N, K, ALGO_SCL if L > 1 else ALGO_SC, L=L, info_order=io, dyn=dyn_pac(N, io, g), **kw)
+    dec.pac_g = pac_taps(g)
+    return dec
+
+
+def PCCASCL(N, K, n_pc=3, n_pc_wm=0, L=8, crc_taps=CRC6_TAPS, **kw):
+    """5G parity-check CRC-aided polar code at E = N (38.212 5.3.1.2): Q_I = the K + r + n_pc most reliable positions, n_pc
+    of them parity-check bits (dyn_pc5g), CA-SCL over the rest."""
+    r = int(max(crc_taps))
+    q = q_sequence(N)
+    pos, sets, io = dyn_pc5g(N, q[N - (K + r + n_pc):], n_pc, n_pc_wm)
+    return Decoder(N, K, ALGO_CASCL, L=L, crc_taps=crc_taps, info_order=io, dyn=(pos, sets), **kw)
 
 
 def decode(llr_in, frozen_mask, N, L):

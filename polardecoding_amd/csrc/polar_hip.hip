@@ -131,6 +131,57 @@ std::vector<uint16_t> rm_channel_ilv(int E)
     return pos;
 }
 
+// ---- dynamic frozen bits, host side (include/polar_hip.h "Dynamic frozen bits") ----
+// coefficients of g(D) from its exponents: g_0 = 1 required, exponents distinct and below N
+bool pac_poly(int N, const int *taps, int n_taps, std::vector<unsigned char> &g)
+{
+    if (N < 1 || !taps || n_taps < 1) return false;
+    g.assign((size_t)N, 0);
+    for (int i = 0; i < n_taps; ++i) {
+        if (taps[i] < 0 || taps[i] >= N || g[(size_t)taps[i]]) return false;
+        g[(size_t)taps[i]] = 1;
+    }
+    return g[0] == 1;
+}
+
+// h = 1 / g(D) mod D^N over GF(2): h_0 = 1, h_k = XOR over t >= 1 with g_t = 1 of h_{k-t}
+std::vector<unsigned char> pac_inverse(const std::vector<unsigned char> &g)
+{
+    const int N = (int)g.size();
+    std::vector<int> t1;
+    for (int t = 1; t < N; ++t)
+        if (g[(size_t)t]) t1.push_back(t);
+    std::vector<unsigned char> h((size_t)N, 0);
+    h[0] = 1;
+    for (int k = 1; k < N; ++k) {
+        unsigned char v = 0;
+        for (int t : t1)
+            if (t <= k) v ^= h[(size_t)(k - t)];
+        h[(size_t)k] = v;
+    }
+    return h;
+}
+
+// rows -> caller's CSR arrays; idx may be null (sizes only)
+int dyn_emit(const std::vector<int> &P, const std::vector<std::vector<int>> &rows, int *pos, int *ptr, int *idx, int idx_cap,
+             int *nnz)
+{
+    int tot = 0;
+    for (size_t d = 0; d < P.size(); ++d) {
+        pos[d] = P[d];
+        ptr[d] = tot;
+        tot += (int)rows[d].size();
+    }
+    ptr[P.size()] = tot;
+    if (nnz) *nnz = tot;
+    if (!idx) return POLAR_OK;
+    if (idx_cap < tot) return POLAR_EINVAL;
+    int k = 0;
+    for (const auto &r : rows)
+        for (int i : r) idx[k++] = i;
+    return POLAR_OK;
+}
+
 static bool sc_lanes_ok(const polar_ctx *c, size_t B)
 {
     return c->cfg.algo == POLAR_ALGO_SC && !c->force_generic && c->cfg.N <= 2048 && B >= 64;
@@ -180,6 +231,7 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     P.scratch = nullptr;
     P.queue = nullptr;
     const bool in32 = in_is_f32 != 0;
+    if (c->is_dyn) return polar_tu::scl_dyn(c, P, f32, in32);   // dynamic frozen bits: one kernel for every shape
     if (sc_lanes_ok(c, B)) return polar_tu::sc_lanes(c, P, f32, in32);
     if (fast_ok(c, in_is_f32)) {
         const bool crc = g.algo == POLAR_ALGO_CASCL;
@@ -435,6 +487,10 @@ void refresh_kernel_name(polar_ctx *c)
         c->kernel_name = a;
     }
     if (c->rm_mode != POLAR_RM_NONE) c->kernel_name = "k_rm_recover, then " + c->kernel_name;
+    if (c->is_dyn) {
+        snprintf(nm, sizeof nm, "k_scl_dyn<%s,L=%d> (D=%d dynamic frozen bits)", ty, g.L, (int)c->dyn_pos.size());
+        c->kernel_name = nm;
+    }
 }
 
 std::vector<uint32_t> pack_mask(const unsigned char *m, int N, bool invert)
@@ -476,7 +532,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : N;   // values per input row
     const uint32_t *d_frozen = c->d_frozen;
     if (frozen_mask) {
-        if (has_crc(c->cfg.algo) || c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
+        if (has_crc(c->cfg.algo) || c->rm_mode != POLAR_RM_NONE || c->is_dyn) return POLAR_EINVAL;
         std::vector<uint32_t> w = pack_mask(frozen_mask, N, false);
         if (!c->d_frozen_override) HIP_TRY(c, hipMalloc(&c->d_frozen_override, NW * sizeof(uint32_t)));
         HIP_TRY(c, hipMemcpyAsync(c->d_frozen_override, w.data(), NW * sizeof(uint32_t), hipMemcpyHostToDevice,
@@ -796,6 +852,9 @@ void polar_destroy(polar_ctx *c)
     if (c->d_gc_rows) (void)hipFree(c->d_gc_rows);
     if (c->d_rm_ilv) (void)hipFree(c->d_rm_ilv);
     if (c->d_rm_ilv_inv) (void)hipFree(c->d_rm_ilv_inv);
+    if (c->d_dyn_mask) (void)hipFree(c->d_dyn_mask);
+    if (c->d_dyn_row) (void)hipFree(c->d_dyn_row);
+    if (c->d_dyn_pos) (void)hipFree(c->d_dyn_pos);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -917,6 +976,173 @@ int polar_rm_info(const polar_ctx *c, int *E, int *mode, int *ibil)
     return POLAR_OK;
 }
 
+// ---- dynamic frozen bits (include/polar_hip.h) -------------------------------------------------------------------------
+int polar_create_dyn(const polar_cfg *cfg, const polar_dyn *dyn, polar_ctx **out)
+{
+    if (!cfg || !out) return POLAR_EINVAL;
+    *out = nullptr;
+    const int N = cfg->N;
+    if (N < 32 || N > 4096 || (N & (N - 1))) return POLAR_EINVAL;
+    if (cfg->algo != POLAR_ALGO_SC && cfg->algo != POLAR_ALGO_SCL && cfg->algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
+    if (cfg->K < 1 || r < 0 || r > 32 || cfg->K + r > N) return POLAR_EINVAL;
+    if (N > 1024) return POLAR_ENOKERNEL;
+    if (!dyn || dyn->D < 0 || dyn->D > N || !dyn->ptr || dyn->ptr[0] != 0 || (dyn->D > 0 && !dyn->pos)) return POLAR_EINVAL;
+    // the frozen set of the cfg, as polar_create builds it
+    const int A = cfg->K + r;
+    std::vector<int> I;
+    if (cfg->info_order) {
+        I.assign(cfg->info_order, cfg->info_order + A);
+    } else {
+        const std::vector<int> q = default_order(N);
+        I.assign(q.end() - A, q.end());
+    }
+    std::vector<unsigned char> frozen((size_t)N, 1);
+    for (int j : I) {
+        if (j < 0 || j >= N || !frozen[(size_t)j]) return POLAR_EINVAL;
+        frozen[(size_t)j] = 0;
+    }
+    const int D = dyn->D, NW = N / 32;
+    std::vector<uint32_t> mask((size_t)std::max(D, 1) * NW, 0u);
+    std::vector<int> row((size_t)N, -1);
+    for (int d = 0; d < D; ++d) {
+        const int j = dyn->pos[d];
+        if (j < 0 || j >= N || (d && j <= dyn->pos[d - 1]) || !frozen[(size_t)j]) return POLAR_EINVAL;
+        const int a = dyn->ptr[d], b = dyn->ptr[d + 1];
+        if (b < a || b - a > j || (b > a && !dyn->idx)) return POLAR_EINVAL;
+        for (int k = a; k < b; ++k) {
+            const int i = dyn->idx[k];
+            if (i < 0 || i >= j || (k > a && i <= dyn->idx[k - 1])) return POLAR_EINVAL;
+            mask[(size_t)d * NW + (i >> 5)] |= 1u << (i & 31);
+        }
+        row[(size_t)j] = d;
+    }
+    polar_ctx *c = nullptr;
+    int rc = polar_create(cfg, &c);
+    if (rc) return rc;
+    c->is_dyn = true;
+    c->dyn_pos.assign(dyn->pos, dyn->pos + D);
+    DeviceGuard guard(cfg->device);
+    const size_t mb = mask.size() * sizeof(uint32_t), pb = (size_t)std::max(D, 1) * sizeof(int);
+    if (hipMalloc(&c->d_dyn_mask, mb) != hipSuccess || hipMalloc(&c->d_dyn_row, (size_t)N * sizeof(int)) != hipSuccess ||
+        hipMalloc(&c->d_dyn_pos, pb) != hipSuccess) {
+        polar_destroy(c);
+        return POLAR_ENOMEM;
+    }
+    if (hipMemcpy(c->d_dyn_mask, mask.data(), mb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_dyn_row, row.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        (D > 0 && hipMemcpy(c->d_dyn_pos, dyn->pos, (size_t)D * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)) {
+        polar_destroy(c);
+        return POLAR_EDEVICE;
+    }
+    refresh_kernel_name(c);
+    *out = c;
+    return POLAR_OK;
+}
+
+int polar_dyn_info(const polar_ctx *c, int *D, int *pos)
+{
+    if (!c) return POLAR_EINVAL;
+    if (D) *D = c->is_dyn ? (int)c->dyn_pos.size() : -1;
+    if (pos) std::copy(c->dyn_pos.begin(), c->dyn_pos.end(), pos);
+    return POLAR_OK;
+}
+
+int polar_dyn_pac(int N, const int *info_order, int A, const int *g_taps, int n_taps, int *pos, int *ptr, int *idx,
+                  int idx_cap, int *nnz)
+{
+    if (N < 32 || N > 4096 || (N & (N - 1)) || !info_order || A < 1 || A > N || !pos || !ptr) return POLAR_EINVAL;
+    std::vector<unsigned char> g, info((size_t)N, 0);
+    if (!pac_poly(N, g_taps, n_taps, g)) return POLAR_EINVAL;
+    for (int i = 0; i < A; ++i) {
+        const int j = info_order[i];
+        if (j < 0 || j >= N || info[(size_t)j]) return POLAR_EINVAL;
+        info[(size_t)j] = 1;
+    }
+    const std::vector<unsigned char> h = pac_inverse(g);
+    std::vector<int> P;
+    std::vector<std::vector<int>> rows;
+    for (int j = 0; j < N; ++j) {
+        if (info[(size_t)j]) continue;
+        P.push_back(j);
+        rows.emplace_back();
+        for (int i = 0; i < j; ++i)
+            if (h[(size_t)(j - i)]) rows.back().push_back(i);
+    }
+    return dyn_emit(P, rows, pos, ptr, idx, idx_cap, nnz);
+}
+
+int polar_pac_precode(int N, const int *g_taps, int n_taps, const int *v, size_t B, int *u)
+{
+    std::vector<unsigned char> g;
+    if (!v || !u || !pac_poly(N, g_taps, n_taps, g)) return POLAR_EINVAL;
+    std::vector<int> t;
+    for (int k = 0; k < N; ++k)
+        if (g[(size_t)k]) t.push_back(k);
+    for (size_t b = 0; b < B; ++b)
+        for (int j = 0; j < N; ++j) {   // u_j = XOR over taps t <= j of v_{j-t}
+            int x = 0;
+            for (int k : t)
+                if (k <= j) x ^= v[b * (size_t)N + (size_t)(j - k)] & 1;
+            u[b * (size_t)N + (size_t)j] = x;
+        }
+    return POLAR_OK;
+}
+
+int polar_pac_unprecode(int N, const int *g_taps, int n_taps, const int *u, size_t B, int *v)
+{
+    std::vector<unsigned char> g;
+    if (!v || !u || u == v || !pac_poly(N, g_taps, n_taps, g)) return POLAR_EINVAL;
+    std::vector<int> t;
+    for (int k = 1; k < N; ++k)
+        if (g[(size_t)k]) t.push_back(k);
+    for (size_t b = 0; b < B; ++b)
+        for (int j = 0; j < N; ++j) {   // v_j = u_j XOR the taps t >= 1 of the v already recovered
+            int x = u[b * (size_t)N + (size_t)j] & 1;
+            for (int k : t)
+                if (k <= j) x ^= v[b * (size_t)N + (size_t)(j - k)];
+            v[b * (size_t)N + (size_t)j] = x;
+        }
+    return POLAR_OK;
+}
+
+int polar_dyn_pc5g(int N, const int *q_i, int n_qi, int n_pc, int n_pc_wm, int *pos, int *ptr, int *idx, int idx_cap,
+                   int *nnz, int *info_order)
+{
+    if (N < 32 || N > 4096 || (N & (N - 1)) || !q_i || !pos || !ptr || !info_order) return POLAR_EINVAL;
+    if (n_pc < 0 || n_pc_wm < 0 || n_pc_wm > n_pc || n_qi <= n_pc || n_qi > N) return POLAR_EINVAL;
+    std::vector<unsigned char> in_qi((size_t)N, 0), is_pc((size_t)N, 0);
+    for (int i = 0; i < n_qi; ++i) {
+        const int j = q_i[i];
+        if (j < 0 || j >= N || in_qi[(size_t)j]) return POLAR_EINVAL;
+        in_qi[(size_t)j] = 1;
+    }
+    for (int i = 0; i < n_pc - n_pc_wm; ++i) is_pc[(size_t)q_i[i]] = 1;   // the least reliable of Q_I
+    // n_pc_wm more among the n_qi - n_pc most reliable: minimum row weight 2^popcount(j), equal weights to the more reliable
+    for (int k = 0; k < n_pc_wm; ++k) {
+        int best = -1;
+        for (int i = n_pc; i < n_qi; ++i) {
+            const int j = q_i[i];
+            if (is_pc[(size_t)j]) continue;
+            if (best < 0 || __builtin_popcount((unsigned)j) <= __builtin_popcount((unsigned)q_i[best])) best = i;
+        }
+        is_pc[(size_t)q_i[best]] = 1;
+    }
+    std::vector<int> P;
+    std::vector<std::vector<int>> rows;
+    for (int j = 0; j < N; ++j) {
+        if (!is_pc[(size_t)j]) continue;
+        P.push_back(j);
+        rows.emplace_back();
+        for (int i = j % 5; i < j; i += 5)
+            if (in_qi[(size_t)i] && !is_pc[(size_t)i]) rows.back().push_back(i);
+    }
+    int k = 0;
+    for (int i = 0; i < n_qi; ++i)
+        if (!is_pc[(size_t)q_i[i]]) info_order[k++] = q_i[i];
+    return dyn_emit(P, rows, pos, ptr, idx, idx_cap, nnz);
+}
+
 int polar_rm_recover_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, void *d_out)
 {
     if (!c || c->rm_mode == POLAR_RM_NONE || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
@@ -1000,7 +1226,7 @@ int polar_bp_set_stop(polar_ctx *c, int rule)
 
 int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
 {
-    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || n < 0 || n > 6 || (n > 0 && !stages)) return POLAR_EINVAL;
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || c->is_dyn || n < 0 || n > 6 || (n > 0 && !stages)) return POLAR_EINVAL;
     for (int i = 0; i < n; ++i) {
         const int L = stages[i];
         if (L < 1 || L > 32 || (L & (L - 1)) || (i && L <= stages[i - 1])) return POLAR_EINVAL;
@@ -1110,7 +1336,7 @@ int polar_scan_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u
 int polar_cascl_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
                               double *d_pm, uint32_t *d_flags, uint32_t *d_list)
 {
-    if (!c || c->cfg.algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || c->is_dyn) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, d_pm, d_flags, c->d_frozen, d_list);
 }
@@ -1118,7 +1344,7 @@ int polar_cascl_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, dou
 int polar_cascl_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, double *pm, unsigned *flags,
                              unsigned *list)
 {
-    if (!c || c->cfg.algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || c->is_dyn) return POLAR_EINVAL;
     return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, pm, flags, list);
 }
 
@@ -1338,6 +1564,7 @@ int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long l
     P.N = g.N; P.n = c->n; P.K = g.K; P.A = c->A; P.B = (int)B;
     P.out_is_f32 = out_is_f32; P.out_is_y = out_is_y;
     if (c->rm_mode != POLAR_RM_NONE) return polar_tu::rm_generate(c, P);   // [B][E] (include/polar_hip.h rules 1-3)
+    if (c->is_dyn) return polar_tu::dyn_generate(c, P);                    // the dynamic bits filled in before the encode
     const int waves = 4;
     const size_t lds = (size_t)waves * (g.N + 2 * 1024);
     int grid = (int)std::min<size_t>((B + waves - 1) / waves, (size_t)c->num_cu * 8);

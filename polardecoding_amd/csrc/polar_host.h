@@ -64,6 +64,12 @@ struct polar_ctx {
     uint16_t *d_rm_ilv = nullptr, *d_rm_ilv_inv = nullptr;
     Buf rm_rows, rm_rows_b;
     Buf genie_rows;                       // polar_construct_batch: one chunk of design rows
+    // dynamic frozen bits (polar_create_dyn): positions (ascending), dense constraint rows [D][NW] and the row index of
+    // every leaf (-1: not dynamic) on the device
+    bool is_dyn = false;
+    std::vector<int> dyn_pos;
+    uint32_t *d_dyn_mask = nullptr;
+    int *d_dyn_row = nullptr, *d_dyn_pos = nullptr;
     Buf in2[2], bits2[2];                // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
@@ -172,6 +178,9 @@ int genie_rows(polar_ctx *c, unsigned long long seed, unsigned long long first_f
                bool out32);
 // k_scan.hip: SCAN (scan_lanes.h), 32 <= N <= 1024
 int scan_lanes(polar_ctx *c, const polar::ScanParams &P, bool r32, bool in32);
+// k_dyn.hip: dynamic frozen bits (scl_dyn.h): SC / SCL / CA-SCL with c->d_dyn_mask / d_dyn_row, the generator with them
+int scl_dyn(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32);
+int dyn_generate(polar_ctx *c, const polar::GenParams &G);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif
