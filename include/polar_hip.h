@@ -474,6 +474,62 @@ int polar_pac_unprecode(int N, const int *g_taps, int n_taps, const int *u, size
 int polar_dyn_pc5g(int N, const int *q_i, int n_qi, int n_pc, int n_pc_wm, int *pos, int *ptr, int *idx, int idx_cap,
                    int *nnz, int *info_order);
 
+/* --- Encoder, payload extraction, systematic polar codes (no reference counterpart as functions of their own) ----------------
+ * The transmit side for a caller's own bits, and the way back from a decoder's N-wide u_hat to the K payload bits.  All rows
+ * are bit-packed: bit (j & 31) of word j >> 5 is element j, the layout of d_uhat_bits.  KW = ceil(K / 32), A = K + r.
+ *   1. transform: out = in F^{(x)n} over GF(2), natural order (the encoder of SCL_1024.c:242-250), rows [B][N/32].  It is an
+ *      involution; d_out may equal d_in.
+ *   2. place: payload rows [B][KW] (bit k = v_k; bits at or above K of the last word are ignored) become the CRC word w of A
+ *      bits: w(D) = v(D) g(D), or with crc_systematic w[0..r) = D^r v mod g, w[r..A) = v (both exactly polar_generate_device's);
+ *      w = v without a CRC.  Then z[I[i]] = w[i], zero elsewhere.
+ *   3. extract, the inverse: w[i] = z[I[i]]; with crc_systematic v = w[r..A), otherwise v is the quotient of w(D) by g(D).
+ *      crc_ok = 1 iff w(D) mod g(D) = 0 (for crc_systematic that is w[0..r) = D^r v mod g); always 1 without a CRC.  The
+ *      payload rows are written with the bits at or above K zero.
+ *   4. polar_encode_device: u = place(payload); on a dynamic context the dynamic bits are then filled in ascending position
+ *      (rule 9 of that section); x = u F^{(x)n}.  On a rate-matched context d_x_bits is the sent row e of E bits (rules 1-3 of
+ *      that section), [B][ceil(E/32)] words with the bits at or above E zero.  Either output may be NULL, not both.
+ *   5. polar_payload_device: extract on d_uhat_bits (u domain, [B][N/32] on every context); d_crc_ok (nullable) [B].  For a
+ *      PAC code the payload is in the v domain: polar_pac_unprecode stays a host step.
+ * All device calls are asynchronous on the ctx stream, read nothing back and work on every ctx of every algo.  Their small
+ * tables are built on the first call (one synchronous copy): warm a ctx before capturing its stream into a graph.
+ *
+ * Systematic polar coding (Arikan 2011), opt-in by polar_set_systematic(ctx, 1): the codeword carries the CRC word on the
+ * information set, x[I[i]] = w[i], instead of u.  With F the complement of I:
+ *      z = place(payload);  t = z F^{(x)n};  t_F = 0;  x = t F^{(x)n};  u = x F^{(x)n}
+ * (u equals t, the transform being an involution, so the library runs two transforms).  This gives x[I[i]] = w[i] with
+ * u_F = 0 exactly when polar_systematic_check(N, I, A) = 1: the two-pass encoder maps every unit vector on I to a codeword
+ * that is that unit vector on I (A host transforms).  It holds for the library's default orders and fails for arbitrary sets.
+ * The decoders are unchanged: they decide u_hat.  While the mode is on,
+ *   - polar_encode_device produces the u and x above;
+ *   - polar_payload_device extracts from x_hat = u_hat F^{(x)n} (formed in registers, no scratch);
+ *   - polar_generate_device sends the systematic codeword of the same Philox payload with the same noise, and d_u_bits is the
+ *     u actually encoded;
+ *   - polar_count_errors_device, and through it polar_fer_batch and polar_stop_rule_batch_y, count the bit errors of x_hat
+ *     against x on I (with crc_systematic: on the K payload positions), block errors by the same comparison;
+ *   - CA-SCL, its adaptive stages and SC-Flip test the CRC of x_hat[I]: their N-entry table crc_tab (crc_tab[I[i]] =
+ *     D^i mod g) is replaced by tab_sys[j] = XOR over {i < A : (j & I[i]) == I[i]} of crc_tab[I[i]] at unfrozen j, 0 at frozen
+ *     j, and restored when the mode is turned off.  Path metrics, ties and every decision that does not depend on the CRC are
+ *     those of the plain context.
+ * polar_set_systematic(ctx, 1) returns POLAR_EINVAL and leaves the ctx unchanged when the check fails, on a dynamic ctx and on
+ * a rate-matched ctx (dynamic bits and punctured systematic positions would need a definition of their own).  The default is
+ * off, and with it off every entry point behaves bit for bit as before.  polar_group_* and polar_fer_multi_gpu build their
+ * contexts from a polar_cfg and stay non-systematic.  The switch synchronizes the ctx stream. */
+/* x = u F^{(x)n} on packed rows [B][N/32]; d_out may equal d_in */
+int polar_transform_device(polar_ctx *ctx, const uint32_t *d_in, size_t B, uint32_t *d_out);
+/* payload [B][KW] -> u [B][N/32] and / or the sent bits [B][N/32] ([B][ceil(E/32)] on a rate-matched ctx); either output
+ * nullable, not both.  POLAR_ENOMEM (ctx usable) if the scratch rows a NULL d_u_bits or a rate-matched ctx needs cannot be had. */
+int polar_encode_device(polar_ctx *ctx, const uint32_t *d_payload, size_t B, uint32_t *d_u_bits, uint32_t *d_x_bits);
+/* decisions [B][N/32] -> payload [B][KW] and the per-frame CRC verdict d_crc_ok [B] (nullable) */
+int polar_payload_device(polar_ctx *ctx, const uint32_t *d_uhat_bits, size_t B, uint32_t *d_payload, uint32_t *d_crc_ok);
+/* host-buffer forms: payload [B][K], u [B][N], x [B][N] ([B][E] on a rate-matched ctx), all 0/1 ints; u or x may be NULL */
+int polar_encode_batch(polar_ctx *ctx, const int *payload, size_t B, int *u, int *x);
+int polar_payload_batch(polar_ctx *ctx, const int *u_hat, size_t B, int *payload, unsigned *crc_ok);
+int polar_set_systematic(polar_ctx *ctx, int on);
+int polar_get_systematic(const polar_ctx *ctx);
+/* host only, touches no device: 1 if the two-pass encoder is systematic on info_order[0..A), 0 if not; POLAR_EINVAL for N not a
+ * power of two in 32..4096, A outside 1..N, or positions that are out of range or repeated */
+int polar_systematic_check(int N, const int *info_order, int A);
+
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at
  * Eb/N0 = snr_db (sigma = 10^(-snr_db/20), rate 1/2 as in the reference, :237) -> d_out[B][N] (double, or float

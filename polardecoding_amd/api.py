@@ -139,6 +139,14 @@ def load_library(testing=False):
     L.polar_pac_precode.argtypes = [C.c_int, ip, C.c_int, ip, C.c_size_t, ip]
     L.polar_pac_unprecode.argtypes = [C.c_int, ip, C.c_int, ip, C.c_size_t, ip]
     L.polar_dyn_pc5g.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, ip, ip]
+    L.polar_transform_device.argtypes = [vp, vp, C.c_size_t, vp]
+    L.polar_encode_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    L.polar_payload_device.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    L.polar_encode_batch.argtypes = [vp, ip, C.c_size_t, ip, ip]
+    L.polar_payload_batch.argtypes = [vp, ip, C.c_size_t, ip, up]
+    L.polar_set_systematic.argtypes = [vp, C.c_int]
+    L.polar_get_systematic.argtypes = [vp]
+    L.polar_systematic_check.argtypes = [C.c_int, ip, C.c_int]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -203,6 +211,16 @@ def rm_info_order(N, A, E):
     if rc != 0:
         raise PolarError(f"polar_rm_info_order({N}, {A}, {E}): {lib.polar_strerror(rc).decode()} (rc={rc})")
     return out[:int(A)]
+
+
+def systematic_check(N, info_order):
+    """polar_systematic_check: True if the two-pass systematic polar encoder is valid for the information set `info_order`
+    (every unit vector on it is encoded to a codeword that equals it on the set).  Host only."""
+    io = np.ascontiguousarray(info_order, dtype=np.int32).ravel()
+    rc = load_library().polar_systematic_check(int(N), _ptr(io, C.c_int), int(io.size))
+    if rc < 0:
+        raise PolarError(f"polar_systematic_check: rc={rc}")
+    return bool(rc)
 
 
 def pac_taps(g):
@@ -328,11 +346,12 @@ class Decoder:
     """One polar_ctx: a (N, K, CRC, L, algo, dtype) configuration bound to one GPU."""
 
     def __init__(self, N, K, algo, L=1, crc_taps=None, bp_iters=100, dtype=F64, device=0, info_order=None,
-                 systematic=False, crc_file=None, E=None, ibil=False, dyn=None, _library=None):
+                 systematic=False, crc_file=None, E=None, ibil=False, dyn=None, sys_polar=False, _library=None):
         """dyn = (pos, sets): dynamic frozen bits (polar_create_dyn): pos ascending frozen positions, sets[d] the earlier
         positions whose decided bits u_hat[pos[d]] is the XOR of (SC / SCL / CA-SCL only; see dyn_pac, dyn_pc5g).
         E: 5G rate matching (polar_create_rm): every decode takes rows of E channel values and generate_device writes
-        them; ibil: with the channel interleaver (uplink)."""
+        them; ibil: with the channel interleaver (uplink).
+        sys_polar: systematic polar code (polar_set_systematic; not to be confused with `systematic`, the systematic CRC)."""
         self._h = C.c_void_p()
         if E is not None and crc_file is not None:
             raise ValueError("E (rate matching) and crc_file exclude each other: polar_create_crc_file takes no E")
@@ -379,6 +398,9 @@ class Decoder:
         self._lib.polar_rm_info(self._h, C.byref(e), C.byref(mode), C.byref(il))
         self.E, self.rm_mode, self.ibil = e.value, mode.value, bool(il.value)   # plain: E = N, RM_NONE
         self._w = self.E   # values per input row of every decode entry point
+        self._sys_polar = False
+        if sys_polar:
+            self.set_systematic(True)
 
     def _create(self):
         if self._dyn is not None:
@@ -410,6 +432,9 @@ class Decoder:
             self.set_scf_flips(self.scf_flips)
         if self.scan_iters is not None:
             self.set_scan_iters(self.scan_iters)
+        if self._sys_polar:
+            self._sys_polar = False
+            self.set_systematic(True)
 
     @property
     def info_order(self):
@@ -473,6 +498,16 @@ class Decoder:
         """SCAN iteration count (polar_scan_set_iters): 1 <= iters <= 64, default 4."""
         self._check(self._lib.polar_scan_set_iters(self._h, int(iters)), "polar_scan_set_iters")
         self.scan_iters = int(iters)
+
+    def set_systematic(self, on):
+        """Systematic polar code (polar_set_systematic): the codeword carries the CRC word on the information set.  Refused
+        (PolarError, decoder unchanged) on dynamic and rate-matched decoders and when systematic_check fails."""
+        self._check(self._lib.polar_set_systematic(self._h, 1 if on else 0), "polar_set_systematic")
+        self._sys_polar = bool(on)
+
+    @property
+    def sys_polar(self):
+        return bool(self._lib.polar_get_systematic(self._h))
 
     @property
     def kernel_name(self):
@@ -690,6 +725,71 @@ class Decoder:
         self._check(self._lib.polar_bp_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
                                                     _ptr(it, C.c_uint), _ptr(fl, C.c_uint)), "polar_bp_decode_batch")
         return uh, it, fl
+
+    # ---- encoder side ---------------------------------------------------------------------------------
+    @staticmethod
+    def _words(t, width, what):
+        import torch
+        if not (t.is_cuda and t.is_contiguous()) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != width:
+            raise ValueError(f"{what} must be a contiguous CUDA int32 tensor of shape [B][{width}]")
+        return t.shape[0]
+
+    def transform_device(self, bits, out=None):
+        """polar_transform_device: rows [B][N/32] int32 -> their transform by F^{(x)n} (out may be `bits`)."""
+        import torch
+        B = self._words(bits, self.NW, "bits")
+        if out is None:
+            out = torch.empty_like(bits)
+        self._words(out, self.NW, "out")
+        self._check(self._lib.polar_transform_device(self._h, C.c_void_p(bits.data_ptr()), B, C.c_void_p(out.data_ptr())),
+                    "polar_transform_device")
+        return out
+
+    def encode_device(self, payload, want_u=True, want_x=True):
+        """polar_encode_device: payload [B][ceil(K/32)] int32 (bit k of the row = payload bit k) -> (u_bits [B][N/32],
+        x_bits [B][N/32], or [B][ceil(E/32)] on a rate-matched decoder); an output not asked for is None."""
+        import torch
+        B = self._words(payload, (self.K + 31) // 32, "payload")
+        u = torch.empty((B, self.NW), dtype=torch.int32, device=payload.device) if want_u else None
+        x = torch.empty((B, (self.E + 31) // 32), dtype=torch.int32, device=payload.device) if want_x else None
+        self._check(self._lib.polar_encode_device(self._h, C.c_void_p(payload.data_ptr()), B,
+                                                  C.c_void_p(u.data_ptr()) if want_u else None,
+                                                  C.c_void_p(x.data_ptr()) if want_x else None), "polar_encode_device")
+        return u, x
+
+    def payload_device(self, uhat_bits):
+        """polar_payload_device: decisions [B][N/32] -> (payload [B][ceil(K/32)] int32, crc_ok [B] int32)."""
+        import torch
+        B = self._words(uhat_bits, self.NW, "uhat_bits")
+        pay = torch.empty((B, (self.K + 31) // 32), dtype=torch.int32, device=uhat_bits.device)
+        ok = torch.empty(B, dtype=torch.int32, device=uhat_bits.device)
+        self._check(self._lib.polar_payload_device(self._h, C.c_void_p(uhat_bits.data_ptr()), B, C.c_void_p(pay.data_ptr()),
+                                                   C.c_void_p(ok.data_ptr())), "polar_payload_device")
+        return pay, ok
+
+    def encode_batch(self, payload):
+        """polar_encode_batch: payload [B][K] of 0/1 -> (u [B][N], x [B][N] or [B][E]) int32."""
+        p = np.ascontiguousarray(payload, dtype=np.int32)
+        if p.ndim != 2 or p.shape[1] != self.K:
+            raise ValueError(f"payload must have shape [B][{self.K}]")
+        B = p.shape[0]
+        u = np.empty((B, self.N), dtype=np.int32)
+        x = np.empty((B, self.E), dtype=np.int32)
+        self._check(self._lib.polar_encode_batch(self._h, _ptr(p, C.c_int), B, _ptr(u, C.c_int), _ptr(x, C.c_int)),
+                    "polar_encode_batch")
+        return u, x
+
+    def payload_batch(self, u_hat):
+        """polar_payload_batch: decisions [B][N] of 0/1 -> (payload [B][K] int32, crc_ok [B] uint32)."""
+        uh = np.ascontiguousarray(u_hat, dtype=np.int32)
+        if uh.ndim != 2 or uh.shape[1] != self.N:
+            raise ValueError(f"u_hat must have shape [B][{self.N}]")
+        B = uh.shape[0]
+        pay = np.empty((B, self.K), dtype=np.int32)
+        ok = np.empty(B, dtype=np.uint32)
+        self._check(self._lib.polar_payload_batch(self._h, _ptr(uh, C.c_int), B, _ptr(pay, C.c_int), _ptr(ok, C.c_uint)),
+                    "polar_payload_batch")
+        return pay, ok
 
     def generate_device(self, seed, first_frame, snr_db, out, u_bits=None, out_is_y=False):
         """Device-side transmit chain (throughput mode): fills `out` [B][N] ([B][E] on a rate-matched decoder; float64/float32

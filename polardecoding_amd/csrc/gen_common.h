@@ -18,6 +18,7 @@ struct GenParams {
     const uint32_t *gc_rows; // systematic CRC (CASCL_1024_sys.c:48-561): row k = D^(r+k) mod g as an r-bit mask; else null
     int N, n, K, A, B;
     int out_is_f32, out_is_y;
+    const uint32_t *sys_frozen;   // [N/32] frozen mask: systematic polar code (polar_set_systematic); null = off
 };
 
 struct Philox {

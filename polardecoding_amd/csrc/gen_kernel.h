@@ -13,6 +13,23 @@
 
 namespace polar {
 
+// x = u F^{(x)n} (SCL_1024.c:242-250) in the layout below: strides < 64 across lanes, strides >= 64 inside the lane word
+__device__ __forceinline__ uint64_t gen_encode(uint64_t x, int lane, int n, int KR)
+{
+    for (int s = 0; s < 6 && s < n; ++s) {
+        const uint64_t o = __shfl_xor((unsigned long long)x, 1 << s);
+        if (!(lane & (1 << s))) x ^= o;
+    }
+    for (int s = 6; s < n; ++s) {
+        const int sh = 1 << (s - 6);
+        uint64_t msk = 0;
+        for (int k = 0; k < KR; ++k)
+            if (!(k & sh)) msk |= 1ull << k;
+        x ^= (x >> sh) & msk;
+    }
+    return x;
+}
+
 // lane l holds codeword / u bits j = l + 64 k as bit k of a 16-bit (N = 1024) .. 64-bit (N = 4096) word
 __global__ __launch_bounds__(256) void k_generate(GenParams P)
 {
@@ -65,6 +82,13 @@ __global__ __launch_bounds__(256) void k_generate(GenParams P)
         __builtin_amdgcn_wave_barrier();
         uint64_t u = 0;
         for (int k = 0; k < KR; ++k) u |= (uint64_t)(ub[lane + 64 * k] & 1) << k;
+        if (P.sys_frozen) {
+            // systematic polar code: the placed row z becomes u = (z F) with the frozen positions cleared, so that x = u F
+            // carries z on the information set (include/polar_hip.h)
+            uint64_t fz = 0;
+            for (int k = 0; k < KR; ++k) fz |= (uint64_t)((P.sys_frozen[2 * k + (lane >> 5)] >> (lane & 31)) & 1u) << k;
+            u = gen_encode(u, lane, P.n, KR) & ~fz;
+        }
         if (P.u_bits) {
             for (int k = 0; k < KR; ++k) {
                 const uint64_t m = __ballot((u >> k) & 1ull);  // bits j = 64k .. 64k+63
@@ -74,19 +98,7 @@ __global__ __launch_bounds__(256) void k_generate(GenParams P)
                 }
             }
         }
-        // x = u F^{(x)n} (SCL_1024.c:242-250): strides < 64 across lanes, strides >= 64 inside the lane word
-        uint64_t x = u;
-        for (int s = 0; s < 6 && s < P.n; ++s) {
-            const uint64_t o = __shfl_xor((unsigned long long)x, 1 << s);
-            if (!(lane & (1 << s))) x ^= o;
-        }
-        for (int s = 6; s < P.n; ++s) {
-            const int sh = 1 << (s - 6);
-            uint64_t msk = 0;
-            for (int k = 0; k < KR; ++k)
-                if (!(k & sh)) msk |= 1ull << k;
-            x ^= (x >> sh) & msk;
-        }
+        const uint64_t x = gen_encode(u, lane, P.n, KR);
         // channel: y = (1 - 2x) + sigma n, n from Box-Muller on Philox uniforms; LLR = 2 y / sigma / sigma
         for (int k2 = 0; k2 < KR; k2 += 2) {
             const Philox g(P.seed, frame, (uint32_t)(lane + 64 * (k2 >> 1)), 1u);

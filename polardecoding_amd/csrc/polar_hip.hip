@@ -855,6 +855,10 @@ void polar_destroy(polar_ctx *c)
     if (c->d_dyn_mask) (void)hipFree(c->d_dyn_mask);
     if (c->d_dyn_row) (void)hipFree(c->d_dyn_row);
     if (c->d_dyn_pos) (void)hipFree(c->d_dyn_pos);
+    if (c->d_enc_inv) (void)hipFree(c->d_enc_inv);
+    if (c->d_enc_rtab) (void)hipFree(c->d_enc_rtab);
+    for (Buf *b : {&c->enc_u, &c->enc_x, &c->enc_io})
+        if (b->p) (void)hipFree(b->p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -1250,6 +1254,9 @@ int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
             }
             int rc = polar_create(&g, &subs[(size_t)i]);
             if (!rc) rc = polar_set_stream(subs[(size_t)i], c->stream);
+            if (!rc && c->sys_polar && subs[(size_t)i]->d_crc_tab &&   // the stage reads the table of the mode that is on
+                hipMemcpy(subs[(size_t)i]->d_crc_tab, c->h_crc_tab_sys.data(), (size_t)c->cfg.N * 4, hipMemcpyHostToDevice) != hipSuccess)
+                rc = POLAR_EDEVICE;
             if (rc) {
                 for (polar_ctx *s : subs) polar_destroy(s);
                 return rc;
@@ -1425,6 +1432,10 @@ int polar_count_errors_device(polar_ctx *c, const uint32_t *d_uhat, const uint32
     if (!c || !d_uhat || !d_u || !d_counters) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
+    if (c->sys_polar) {   // systematic polar code: the comparison is on x_hat[I] against x[I]
+        if (B > 0x7fffffffull) return POLAR_EINVAL;
+        return polar_tu::enc_count_sys(c, d_uhat, d_u, B, d_counters, d_frame_err);
+    }
     polar::CountParams P{d_uhat, d_u, c->d_info, d_counters, d_frame_err, c->NW, (int)B};
     const int waves_per_block = 4;
     int grid = (int)std::min<size_t>((B + waves_per_block - 1) / waves_per_block, (size_t)c->num_cu * 8);
@@ -1563,6 +1574,7 @@ int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long l
     }
     P.N = g.N; P.n = c->n; P.K = g.K; P.A = c->A; P.B = (int)B;
     P.out_is_f32 = out_is_f32; P.out_is_y = out_is_y;
+    P.sys_frozen = c->sys_polar ? c->d_frozen : nullptr;   // polar_set_systematic refuses rate-matched and dynamic contexts
     if (c->rm_mode != POLAR_RM_NONE) return polar_tu::rm_generate(c, P);   // [B][E] (include/polar_hip.h rules 1-3)
     if (c->is_dyn) return polar_tu::dyn_generate(c, P);                    // the dynamic bits filled in before the encode
     const int waves = 4;
@@ -1641,6 +1653,228 @@ int polar_fer_batch(polar_ctx *c, unsigned long long seed, unsigned long long fi
     if (rc) return rc;
     *block_errors += h[0];
     *bit_errors += h[1];
+    return POLAR_OK;
+}
+
+// ---- encoder, payload extraction, systematic polar codes (include/polar_hip.h) ------------------------------------------
+namespace {
+
+// x F^{(x)n} on one packed host row, the stages of enc_kernel.h
+void host_transform(uint32_t *w, int NW)
+{
+    static const uint32_t m[5] = {0x55555555u, 0x33333333u, 0x0F0F0F0Fu, 0x00FF00FFu, 0x0000FFFFu};
+    for (int i = 0; i < NW; ++i)
+        for (int s = 0; s < 5; ++s) w[i] ^= (w[i] >> (1 << s)) & m[s];
+    for (int o = 1; o < NW; o <<= 1)
+        for (int i = 0; i < NW; ++i)
+            if (!(i & o)) w[i] ^= w[i + o];
+}
+
+// the tables k_place / k_extract read, built on first use
+int enc_tables(polar_ctx *c)
+{
+    const int N = c->cfg.N, A = c->A;
+    if (!c->d_info_order) {
+        HIP_TRY(c, hipMalloc(&c->d_info_order, sizeof(int) * (size_t)A));
+        HIP_TRY(c, hipMemcpy(c->d_info_order, c->info_order.data(), sizeof(int) * (size_t)A, hipMemcpyHostToDevice));
+    }
+    if (!c->d_enc_rtab) {
+        std::vector<uint32_t> rtab((size_t)A);   // D^i mod g(D): make_crc_table keeps it at position I[i]
+        for (int i = 0; i < A; ++i) rtab[(size_t)i] = c->h_crc_tab[(size_t)c->info_order[(size_t)i]];
+        uint32_t *d = nullptr;
+        if (hipMalloc(&d, rtab.size() * 4) != hipSuccess) return POLAR_ENOMEM;
+        if (hipMemcpy(d, rtab.data(), rtab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            return POLAR_EDEVICE;
+        }
+        c->d_enc_rtab = d;
+    }
+    if (!c->d_enc_inv) {
+        std::vector<uint16_t> inv((size_t)N, (uint16_t)0xFFFFu);
+        for (int i = 0; i < A; ++i) inv[(size_t)c->info_order[(size_t)i]] = (uint16_t)i;
+        uint16_t *d = nullptr;
+        if (hipMalloc(&d, inv.size() * 2) != hipSuccess) return POLAR_ENOMEM;
+        if (hipMemcpy(d, inv.data(), inv.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            return POLAR_EDEVICE;
+        }
+        c->d_enc_inv = d;
+    }
+    return POLAR_OK;
+}
+
+// scratch rows; a failed allocation is POLAR_ENOMEM and leaves the ctx usable
+int enc_scratch(polar_ctx *c, Buf &b, size_t bytes)
+{
+    if (b.cap >= bytes) return POLAR_OK;
+    if (ensure(c, b, bytes)) {
+        (void)hipGetLastError();
+        return POLAR_ENOMEM;
+    }
+    return POLAR_OK;
+}
+
+// the CRC table of systematic mode: tab_sys[j] = XOR over {i : I[i] a subset of j} of crc_tab[I[i]] at unfrozen j, 0 at frozen j
+// (x_c = XOR over {j : c subset of j} of u_j, so the syndrome of x[I] is a XOR over the set u bits as before)
+void make_crc_table_sys(const polar_ctx *c, std::vector<uint32_t> &t)
+{
+    const int N = c->cfg.N;
+    t = c->h_crc_tab;
+    for (int s = 1; s < N; s <<= 1)
+        for (int j = 0; j < N; ++j)
+            if (j & s) t[(size_t)j] ^= t[(size_t)(j ^ s)];
+    for (int j = 0; j < N; ++j)
+        if (c->frozen[(size_t)j]) t[(size_t)j] = 0u;
+}
+
+}  // namespace
+
+int polar_systematic_check(int N, const int *info_order, int A)
+{
+    if (N < 32 || N > 4096 || (N & (N - 1)) || !info_order || A < 1 || A > N) return POLAR_EINVAL;
+    const int NW = N / 32;
+    std::vector<uint32_t> keep((size_t)NW, 0u);
+    for (int i = 0; i < A; ++i) {
+        const int j = info_order[i];
+        if (j < 0 || j >= N || ((keep[(size_t)(j >> 5)] >> (j & 31)) & 1u)) return POLAR_EINVAL;
+        keep[(size_t)(j >> 5)] |= 1u << (j & 31);
+    }
+    // the two-pass encoder on every unit vector of I: x = ((e_j F) restricted to I) F must be e_j on I
+    // (u = x F is then that restriction itself, zero on F)
+    std::vector<uint32_t> w((size_t)NW);
+    for (int i = 0; i < A; ++i) {
+        const int j = info_order[i];
+        std::fill(w.begin(), w.end(), 0u);
+        w[(size_t)(j >> 5)] = 1u << (j & 31);
+        host_transform(w.data(), NW);
+        for (int k = 0; k < NW; ++k) w[(size_t)k] &= keep[(size_t)k];
+        host_transform(w.data(), NW);
+        for (int k = 0; k < NW; ++k)
+            if ((w[(size_t)k] & keep[(size_t)k]) != (k == (j >> 5) ? 1u << (j & 31) : 0u)) return 0;
+    }
+    return 1;
+}
+
+int polar_get_systematic(const polar_ctx *c) { return c && c->sys_polar ? 1 : 0; }
+
+int polar_set_systematic(polar_ctx *c, int on)
+{
+    if (!c || (on != 0 && on != 1)) return POLAR_EINVAL;
+    if ((on != 0) == c->sys_polar) return POLAR_OK;
+    if (on) {
+        if (c->is_dyn || c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
+        if (polar_systematic_check(c->cfg.N, c->info_order.data(), c->A) != 1) return POLAR_EINVAL;
+    }
+    DeviceGuard guard(c->cfg.device);
+    if (c->d_crc_tab) {
+        // CA-SCL, its adaptive stages and SC-Flip test the CRC through this table only: switch it with the mode
+        if (c->h_crc_tab_sys.empty()) make_crc_table_sys(c, c->h_crc_tab_sys);
+        const std::vector<uint32_t> &t = on ? c->h_crc_tab_sys : c->h_crc_tab;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // no queued decode still reads the old table
+        HIP_TRY(c, hipMemcpy(c->d_crc_tab, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+        for (polar_ctx *s : c->stage_ctx)
+            if (s && s->d_crc_tab) HIP_TRY(c, hipMemcpy(s->d_crc_tab, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    }
+    c->sys_polar = on != 0;
+    return POLAR_OK;
+}
+
+int polar_transform_device(polar_ctx *c, const uint32_t *d_in, size_t B, uint32_t *d_out)
+{
+    if (!c || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return polar_tu::enc_transform(c, d_in, nullptr, false, B, d_out);
+}
+
+int polar_encode_device(polar_ctx *c, const uint32_t *d_payload, size_t B, uint32_t *d_u_bits, uint32_t *d_x_bits)
+{
+    if (!c || !d_payload || (!d_u_bits && !d_x_bits) || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    int rc;
+    if ((rc = enc_tables(c))) return rc;
+    const size_t row = (size_t)c->NW * sizeof(uint32_t);
+    uint32_t *u = d_u_bits;
+    if (!u) {
+        if ((rc = enc_scratch(c, c->enc_u, B * row))) return rc;
+        u = (uint32_t *)c->enc_u.p;
+    }
+    const bool rm = c->rm_mode != POLAR_RM_NONE;
+    if (rm && d_x_bits && (rc = enc_scratch(c, c->enc_x, B * row))) return rc;
+    if ((rc = polar_tu::enc_place(c, d_payload, B, u))) return rc;
+    if (c->is_dyn && (rc = polar_tu::enc_dyn_fill(c, u, B))) return rc;
+    // systematic: u = (z F) with the frozen positions cleared; x = u F then carries z on the information set
+    if (c->sys_polar && (rc = polar_tu::enc_transform(c, u, nullptr, true, B, u))) return rc;
+    if (!d_x_bits) return POLAR_OK;
+    if (!rm) return polar_tu::enc_transform(c, u, nullptr, false, B, d_x_bits);
+    if ((rc = polar_tu::enc_transform(c, u, nullptr, false, B, (uint32_t *)c->enc_x.p))) return rc;
+    return polar_tu::enc_rm_select(c, (const uint32_t *)c->enc_x.p, B, d_x_bits);
+}
+
+int polar_payload_device(polar_ctx *c, const uint32_t *d_uhat_bits, size_t B, uint32_t *d_payload, uint32_t *d_crc_ok)
+{
+    if (!c || !d_uhat_bits || !d_payload || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    int rc;
+    if ((rc = enc_tables(c))) return rc;
+    // systematic: the kernel transforms u_hat to x_hat in registers as it loads the row, so no scratch row is needed
+    return polar_tu::enc_extract(c, d_uhat_bits, c->sys_polar, B, d_payload, d_crc_ok);
+}
+
+int polar_encode_batch(polar_ctx *c, const int *payload, size_t B, int *u, int *x)
+{
+    if (!c || !payload || (!u && !x) || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    const int K = c->cfg.K, KW = (K + 31) / 32, N = c->cfg.N, NW = c->NW;
+    const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : N, XW = (W + 31) / 32;
+    int rc;
+    if ((rc = enc_scratch(c, c->in, B * KW * 4))) return rc;
+    if ((rc = enc_scratch(c, c->bits, B * NW * 4))) return rc;
+    if ((rc = enc_scratch(c, c->enc_io, B * XW * 4))) return rc;
+    std::vector<uint32_t> pw(B * (size_t)KW, 0u);
+    for (size_t b = 0; b < B; ++b)
+        for (int k = 0; k < K; ++k)
+            if (payload[b * K + k]) pw[b * KW + (k >> 5)] |= 1u << (k & 31);
+    HIP_TRY(c, hipMemcpyAsync(c->in.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, c->stream));
+    rc = polar_encode_device(c, (const uint32_t *)c->in.p, B, (uint32_t *)c->bits.p, x ? (uint32_t *)c->enc_io.p : nullptr);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    std::vector<uint32_t> hu(u ? B * (size_t)NW : 0), hx(x ? B * (size_t)XW : 0);
+    if (u) HIP_TRY(c, hipMemcpyAsync(hu.data(), c->bits.p, hu.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    if (x) HIP_TRY(c, hipMemcpyAsync(hx.data(), c->enc_io.p, hx.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (u)
+        for (size_t b = 0; b < B; ++b) unpack_words(hu.data() + b * NW, NW, u + b * (size_t)N);
+    if (x)
+        for (size_t b = 0; b < B; ++b)
+            for (int t = 0; t < W; ++t) x[b * (size_t)W + t] = (int)((hx[b * XW + (t >> 5)] >> (t & 31)) & 1u);
+    return POLAR_OK;
+}
+
+int polar_payload_batch(polar_ctx *c, const int *u_hat, size_t B, int *payload, unsigned *crc_ok)
+{
+    if (!c || !u_hat || !payload || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    const int K = c->cfg.K, KW = (K + 31) / 32, N = c->cfg.N, NW = c->NW;
+    int rc;
+    if ((rc = enc_scratch(c, c->in, B * KW * 4))) return rc;
+    if ((rc = enc_scratch(c, c->bits, B * NW * 4))) return rc;
+    if ((rc = enc_scratch(c, c->flags, B * 4))) return rc;
+    std::vector<uint32_t> uw(B * (size_t)NW, 0u);
+    for (size_t b = 0; b < B; ++b)
+        for (int j = 0; j < N; ++j)
+            if (u_hat[b * N + j]) uw[b * NW + (j >> 5)] |= 1u << (j & 31);
+    HIP_TRY(c, hipMemcpyAsync(c->bits.p, uw.data(), uw.size() * 4, hipMemcpyHostToDevice, c->stream));
+    rc = polar_payload_device(c, (const uint32_t *)c->bits.p, B, (uint32_t *)c->in.p, (uint32_t *)c->flags.p);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    std::vector<uint32_t> pw(B * (size_t)KW);
+    HIP_TRY(c, hipMemcpyAsync(pw.data(), c->in.p, pw.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    if (crc_ok) HIP_TRY(c, hipMemcpyAsync(crc_ok, c->flags.p, B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < B; ++b)
+        for (int k = 0; k < K; ++k) payload[b * (size_t)K + k] = (int)((pw[b * KW + (k >> 5)] >> (k & 31)) & 1u);
     return POLAR_OK;
 }
 

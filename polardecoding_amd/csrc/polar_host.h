@@ -70,6 +70,14 @@ struct polar_ctx {
     std::vector<int> dyn_pos;
     uint32_t *d_dyn_mask = nullptr;
     int *d_dyn_row = nullptr, *d_dyn_pos = nullptr;
+    // encoder side (polar_encode_device, polar_payload_device, polar_set_systematic): i with I[i] = j per position
+    // (0xFFFF = frozen), D^i mod g(D) for i < A, both built on first use; the two CRC tables of CA-SCL / SC-Flip (the plain
+    // one of make_crc_table and the systematic-mode one, whichever is live sits in d_crc_tab); scratch rows of the encoder
+    bool sys_polar = false;
+    uint16_t *d_enc_inv = nullptr;
+    uint32_t *d_enc_rtab = nullptr;
+    std::vector<uint32_t> h_crc_tab_sys;
+    Buf enc_u, enc_x, enc_io;
     Buf in2[2], bits2[2];                // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
@@ -181,6 +189,14 @@ int scan_lanes(polar_ctx *c, const polar::ScanParams &P, bool r32, bool in32);
 // k_dyn.hip: dynamic frozen bits (scl_dyn.h): SC / SCL / CA-SCL with c->d_dyn_mask / d_dyn_row, the generator with them
 int scl_dyn(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32);
 int dyn_generate(polar_ctx *c, const polar::GenParams &G);
+// k_enc.hip: the encoder side on packed rows (enc_kernel.h)
+int enc_transform(polar_ctx *c, const uint32_t *d_in, const uint32_t *d_in2, bool clear_frozen, size_t B, uint32_t *d_out);
+int enc_place(polar_ctx *c, const uint32_t *d_payload, size_t B, uint32_t *d_z);                      // needs d_enc_inv, d_enc_rtab
+int enc_extract(polar_ctx *c, const uint32_t *d_z, bool xform, size_t B, uint32_t *d_payload, uint32_t *d_ok);   // d_info_order, d_enc_rtab
+int enc_dyn_fill(polar_ctx *c, uint32_t *d_z, size_t B);
+int enc_rm_select(polar_ctx *c, const uint32_t *d_x, size_t B, uint32_t *d_e);
+int enc_count_sys(polar_ctx *c, const uint32_t *d_uhat, const uint32_t *d_u, size_t B, unsigned long long *d_counters,
+                  uint32_t *d_frame_err);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

@@ -217,6 +217,7 @@ static void usage(void)
                     "                 [--iters I]   (scan: soft-output SCAN with I iterations, 1..64; default 4)\n"
                     "                 [--construct frames --design-snr db [--q-out file]]   (Monte-Carlo construction of the order on the device first;\n"
                     "                                  --q-out: write it in the format --q reads)\n"
+                    "                 [--sys-polar]   (--fast only: systematic polar code, polar_set_systematic; errors are counted on the codeword's information positions)\n"
                     "                 [--E e [--ibil]]   (--fast only: 5G rate matching, e channel values per codeword; --ibil: channel interleaver)\n");
     exit(2);
 }
@@ -229,6 +230,7 @@ int main(int argc, char **argv)
     int flips = -1;               /* --flips: polar_scf_set_flips (-1: the library's default) */
     int scan_iters = -1;          /* --iters: polar_scan_set_iters (-1: the library's default) */
     int rm_E = 0, rm_ibil = 0;    /* --E / --ibil: polar_create_rm (0: no rate matching) */
+    int sys_polar = 0;            /* --sys-polar: polar_set_systematic */
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
     double lo = 1.0, hi = 3.0, step = 0.5;
@@ -268,6 +270,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--ibil")) { rm_ibil = 1; }
         else if (!strcmp(a, "--gpus") && v) { gpus = atoi(v); i++; }   /* --fast only: frames sharded over the GPUs of the node */
         else if (!strcmp(a, "--sys")) { sys = 1; }
+        else if (!strcmp(a, "--sys-polar")) { sys_polar = 1; }   /* systematic polar code (not --sys, the systematic CRC) */
         else if (!strcmp(a, "--bp-stop") && v) {   /* polar_bp_set_stop */
             if (strcmp(v, "g")) usage();
             bp_stop = POLAR_BP_STOP_G;
@@ -405,6 +408,11 @@ int main(int argc, char **argv)
         polar_destroy(ctx);
         ctx = NULL;
         if ((rc = polar_create_rm(&cfg, rm_E, rm_ibil, &ctx)) != 0) { fprintf(stderr, "polar_create_rm: %s\n", polar_strerror(rc)); return 1; }
+    }
+    if (sys_polar) {
+        /* the host Ranq1 frame loop encodes u F; a polar_group builds its contexts from cfg and stays non-systematic */
+        if (!fast || gpus > 1) { fprintf(stderr, "--sys-polar: only with --fast, not with --gpus > 1\n"); return 1; }
+        if ((rc = polar_set_systematic(ctx, 1)) != 0) { fprintf(stderr, "--sys-polar: %s\n", polar_strerror(rc)); return 1; }
     }
     if (bp_stop != POLAR_BP_STOP_NONE) {
         /* the read-outs need fixed iterations; a polar_group builds its contexts from cfg and has no stop rule */
