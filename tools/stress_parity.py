@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Differential sweep GPU (through the C ABI) vs the CPU oracle over many shapes: every kernel family, list sizes,
 code lengths, rates, CRCs, both arithmetic types, ragged batch sizes.  Developer tool (tests/ holds the fixed cases).
---patterns: every configuration on a frozen set of tests/frozen_patterns.py (picked by the tool's rng) instead of the 5G set."""
+--patterns: every configuration on a frozen set of tests/frozen_patterns.py (picked by the tool's rng) instead of the 5G set.
+--dyn FAMILY: instead of the sweep above, k_scl_dyn against the numpy model of tests/test_dyn_host.py (bits, metric, flags by
+==, tie frames included) on a constraint family of tests/dyn_families.py, at larger B than tests/test_gpu_dyn_families.py."""
 import argparse, itertools, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -16,10 +18,45 @@ ap.add_argument("--inputs", choices=("gaussian", "grid", "hard"), default="gauss
                 help="grid: LLRs rounded to step 1, clipped to +-7; hard: +-1 with the channel sign (dense with ties)")
 ap.add_argument("--patterns", action="store_true",
                 help="a frozen set outside the 5G order (tests/frozen_patterns.py) per configuration, K = its size less the CRC")
+ap.add_argument("--dyn", choices=("pac", "all_prev", "bern_half"), default=None,
+                help="dynamic frozen bits: this constraint family on the PAC rm mask, against the numpy model")
 args = ap.parse_args()
 rng = np.random.default_rng(args.seed)
 bad = 0
 t0 = time.time()
+
+
+def dyn_sweep(family):
+    """k_scl_dyn == dscl_model on every frame, N = 32 .. 1024, L = 1 .. 32, f64 and f32"""
+    global bad
+    import dyn_families as DF
+    for N, L, dtype in itertools.product((32, 64, 128, 1024), (1, 2, 8, 32), ("f64", "f32")):
+        mask, io = DF.mask_of(N, "rm")
+        dyn = DF.constraint_families(N, mask, args.seed)[family]
+        B = int(rng.integers(40, 90)) if N == 1024 else int(rng.integers(300, 1200))
+        _, llr = DF.M.make_frames(N, io, dyn, B, int(rng.integers(1, 1 << 30)), dbs=(0.0, 1.0, 2.0, 3.0))
+        llr = llr.astype(np.float32).astype(np.float64)
+        if args.inputs == "grid":
+            llr = np.clip(np.rint(llr), -7, 7)
+        elif args.inputs == "hard":
+            llr = np.where(np.signbit(llr), -1.0, 1.0)
+        npdt = np.float32 if dtype == "f32" else np.float64
+        want = DF.M.dscl_model(mask, dyn, llr, L, dtype=npdt)
+        dec = pa.Decoder(N, N // 2, pa.ALGO_SC if L == 1 else pa.ALGO_SCL, L=L, dtype=pa.F32 if dtype == "f32" else pa.F64,
+                         info_order=io, dyn=dyn)
+        uh, pm, fl = dec.decode_batch(llr)
+        ok = np.array_equal(uh, want[0]) and np.array_equal(pm, want[1]) and np.array_equal(np.asarray(fl).view(np.uint32), want[2])
+        ties = int((want[2] & 1).sum())
+        print(f"{'ok ' if ok else 'BAD'} dyn {family:9s} N={N:4d} L={L:2d} {dtype} {dec.kernel_name[:30]:30s} B={B:4d} tie-frames={ties}",
+              flush=True)
+        bad += (not ok)
+        dec.close()
+
+
+if args.dyn:
+    dyn_sweep(args.dyn)
+    print(f"{bad} mismatching configurations, {time.time() - t0:.0f} s")
+    sys.exit(1 if bad else 0)
 
 
 def q_of(dec, N, K, taps):
