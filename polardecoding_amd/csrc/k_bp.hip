@@ -13,18 +13,12 @@ int launch_bp_r4(polar_ctx *c, const polar::BpParams &P)
     using Cfg = polar::BpR4Cfg<R>;
     auto kern = P.stop ? polar::k_bp_r4<R, IN, true> : polar::k_bp_r4<R, IN>;
     const size_t lds = P.stop ? Cfg::lds_bytes_stop : Cfg::lds_bytes;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, Cfg::THREADS, lds));
-    if (occ < 1) occ = 1;
-    int grid = (int)std::min<long long>((long long)P.B, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), LaunchShape{Cfg::THREADS, lds, P.B, 1}, &pl);
+    if (rc) return rc;
     polar::BpParams Q = P;
-    if ((long long)P.B > (long long)grid) {
-        int rc = work_queue(c, c->scratch, &Q.queue);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds, c->stream, Q);
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(Cfg::THREADS), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }
@@ -36,18 +30,14 @@ int launch_bp_w128(polar_ctx *c, const polar::BpParams &P)
     using Cfg = polar::BpW128Cfg<R>;
     auto kern = P.stop ? polar::k_bp_w128<R, IN, true> : polar::k_bp_w128<R, IN>;
     const size_t lds = Cfg::lds_bytes;
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * Cfg::WAVES, lds));
-    if (occ < 1) occ = 1;
-    const long long blocks_needed = ((long long)P.B + Cfg::WAVES - 1) / Cfg::WAVES;
-    int grid = (int)std::min<long long>(blocks_needed, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
+    LaunchShape s{64 * Cfg::WAVES, lds, P.B, Cfg::WAVES};
+    s.set_lds_attr = false;   // the LDS holds the tables alone: far below the limit a kernel has anyway
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
+    if (rc) return rc;
     polar::BpParams Q = P;
-    if ((long long)P.B > (long long)grid * Cfg::WAVES) {
-        int rc = work_queue(c, c->scratch, &Q.queue);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * Cfg::WAVES), lds, c->stream, Q);
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(64 * Cfg::WAVES), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }
@@ -55,8 +45,9 @@ int launch_bp_w128(polar_ctx *c, const polar::BpParams &P)
 template <typename R, typename IN>
 int launch_bp(polar_ctx *c, const polar::BpParams &P)
 {
-    if (P.N == 1024 && !c->force_generic) return launch_bp_r4<R, IN>(c, P);
-    if (P.N == 128 && !c->force_generic) return launch_bp_w128<R, IN>(c, P);
+    const int variant = polar_tu::bp_variant(c);
+    if (variant == polar_tu::BP_R4) return launch_bp_r4<R, IN>(c, P);
+    if (variant == polar_tu::BP_W128) return launch_bp_w128<R, IN>(c, P);
     const bool stop = P.stop != 0;
     auto kern = stop ? polar::k_bp<R, IN, true> : polar::k_bp<R, IN>;
     const size_t lds = polar::bp_lds_bytes<R>(P.N, P.n, stop);
@@ -71,20 +62,13 @@ int launch_bp(polar_ctx *c, const polar::BpParams &P)
         HIP_TRY(c, hipGetLastError());
         return POLAR_OK;
     }
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
     const int threads = std::max(64, std::min(512, P.N / 2));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
-    if (occ < 1) occ = 1;
-    int grid = std::min<long long>((long long)P.B, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), LaunchShape{threads, lds, P.B, 1}, &pl);
+    if (rc) return rc;
     polar::BpParams Q = P;
-    if ((long long)P.B > (long long)grid) {
-        int rc = work_queue(c, c->scratch, &Q.queue);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, c->stream, Q);
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(threads), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }
@@ -109,6 +93,13 @@ int launch_bp_readout(polar_ctx *c, const polar::BpReadoutParams &P)
 }
 
 }  // namespace
+
+int polar_tu::bp_variant(const polar_ctx *c)
+{
+    if (c->cfg.N == 1024 && !c->force_generic) return BP_R4;
+    if (c->cfg.N == 128 && !c->force_generic) return BP_W128;
+    return BP_PLAIN;
+}
 
 int polar_tu::bp(polar_ctx *c, const polar::BpParams &P, bool r32, bool in32)
 {

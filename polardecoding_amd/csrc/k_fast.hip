@@ -12,29 +12,18 @@ int launch_fast(polar_ctx *c, const polar::SclParams &P)
     auto kern = polar::k_scl_fast<R, IN, NLOG, CRC_ON>;
     constexpr int WAVES = polar::FastCfg<R, NLOG>::WAVES;
     const size_t lds = polar::FastCfg<R, NLOG>::total;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * WAVES, lds));
-    if (occ < 1) occ = 1;
-    long long blocks_needed = ((long long)P.B + WAVES - 1) / WAVES;
-    int grid = (int)std::min<long long>(blocks_needed, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
-    polar::SclParams Q = P;
-    const size_t sc_bytes = polar::FastCfg<R, NLOG>::scratch_elems * sizeof(R) * (size_t)grid * WAVES;
-    if (sc_bytes) {
-        int rc = ensure(c, c->scratch, sc_bytes);
-        if (rc) return rc;
-        Q.scratch = c->scratch.p;
-    }
+    LaunchShape s{64 * WAVES, lds, P.B, WAVES};
+    s.scratch_per_block = polar::FastCfg<R, NLOG>::scratch_elems * sizeof(R) * WAVES;
     // work queue (polar_host.h): + 12 % for N = 128 in f64 (67.8 -> 76.1 M frames/s on one box); the f32 kernel at N = 128 is
     // not short of issue slots and loses 3 % to it (89.5 -> 86.5 M): fixed stride there
-    constexpr bool QUEUE = !(sizeof(R) == 4 && NLOG == 7);
-    if (QUEUE && (long long)P.B > (long long)grid * WAVES) {
-        int rc = work_queue(c, c->scratch, &Q.queue);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, c->stream, Q);
+    s.use_queue = !(sizeof(R) == 4 && NLOG == 7);
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
+    if (rc) return rc;
+    polar::SclParams Q = P;
+    if (pl.scratch) Q.scratch = pl.scratch;
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(64 * WAVES), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

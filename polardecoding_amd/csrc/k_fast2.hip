@@ -12,25 +12,16 @@ int launch_fast2(polar_ctx *c, const polar::SclParams &P)
     auto kern = polar::k_scl_fast2<R, IN, CRC_ON>;
     constexpr int WAVES = Cfg::WAVES;
     const size_t lds = Cfg::total;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * WAVES, lds));
-    if (occ < 1) occ = 1;
     const long long pairs = ((long long)P.B + 1) / 2;
-    long long blocks_needed = (pairs + WAVES - 1) / WAVES;
-    int grid = (int)std::min<long long>(blocks_needed, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
-    polar::SclParams Q = P;
-    const size_t sc_bytes = Cfg::scratch_elems * sizeof(R) * (size_t)grid * WAVES;
-    int rc = ensure(c, c->scratch, sc_bytes);
+    LaunchShape s{64 * WAVES, lds, pairs, WAVES};   // more pairs than resident wavefronts: the rest through the work queue
+    s.scratch_per_block = Cfg::scratch_elems * sizeof(R) * WAVES;
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
     if (rc) return rc;
-    Q.scratch = c->scratch.p;
-    if (pairs > (long long)grid * WAVES) {   // more jobs than resident wavefronts: the rest through the work queue
-        rc = work_queue(c, c->scratch, &Q.queue);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, c->stream, Q);
+    polar::SclParams Q = P;
+    Q.scratch = pl.scratch;
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(64 * WAVES), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

@@ -10,26 +10,18 @@ int launch_scl_v(polar_ctx *c, const polar::SclParams &P)
     auto kern = polar::k_scl_generic<R, IN, LOGL, GA>;
     const size_t lds = polar::scl_generic_lds_bytes<R, LOGL>(P.N, GA);
     if (lds > 160 * 1024) return POLAR_ENOKERNEL;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64, lds));
-    if (occ < 1) occ = 1;
-    if (GA && occ > 8) occ = 8;
-    int grid = std::min<long long>((long long)P.B, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
+    LaunchShape s{64, lds, P.B, 1};
+    if (GA) {   // the levels in global scratch: at most 8 blocks per CU
+        s.scratch_per_block = sizeof(R) * (size_t)((1 << LOGL) + 1) * P.N;
+        s.occ_cap = 8;
+    }
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
+    if (rc) return rc;
     polar::SclParams Q = P;
-    if (GA) {
-        const size_t bytes = sizeof(R) * (size_t)((1 << LOGL) + 1) * P.N * (size_t)grid;
-        int rc = ensure(c, c->scratch, bytes);
-        if (rc) return rc;
-        Q.scratch = c->scratch.p;
-    }
-    if ((long long)P.B > (long long)grid) {
-        int rc = work_queue(c, c->scratch, &Q.queue);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, c->stream, Q);
+    if (GA) Q.scratch = pl.scratch;
+    Q.queue = pl.queue;   // the counter hangs off c->scratch with or without scratch bytes
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(64), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

@@ -12,20 +12,16 @@ int launch_sc_lanes(polar_ctx *c, const polar::SclParams &P)
     auto kern = polar::k_sc_lanes<R, IN>;
     const size_t lds = Cfg::lds_bytes(P.N);
     const int threads = 64 * Cfg::WAVES;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
-    if (occ < 1) occ = 1;
     const long long batches = ((long long)P.B + 63) / 64;
-    int grid = (int)std::min<long long>((batches + Cfg::WAVES - 1) / Cfg::WAVES, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
-    polar::SclParams Q = P;
-    int rc = ensure(c, c->scratch, Cfg::scratch_bytes(P.N) * (size_t)grid * Cfg::WAVES);
+    LaunchShape s{threads, lds, batches, Cfg::WAVES};
+    s.scratch_per_block = Cfg::scratch_bytes(P.N) * Cfg::WAVES;
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
     if (rc) return rc;
-    Q.scratch = c->scratch.p;
-    if (batches > (long long)grid * Cfg::WAVES && (rc = work_queue(c, c->scratch, &Q.queue))) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, c->stream, Q);
+    polar::SclParams Q = P;
+    Q.scratch = pl.scratch;
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(threads), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

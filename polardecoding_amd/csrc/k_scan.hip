@@ -34,20 +34,20 @@ int launch_scan_lanes(polar_ctx *c, const polar::ScanParams &P)
     auto kern = polar::k_scan_lanes<R, IN>;
     const size_t lds = Cfg::lds_bytes();
     const int threads = 64 * Cfg::WAVES;
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
-    if (occ < 1) occ = 1;
     const size_t wg_bytes = Cfg::scratch_bytes(P.N, P.n) * Cfg::WAVES;
     const long long batches = ((long long)P.B + 63) / 64;
-    long long grid = std::min<long long>((batches + Cfg::WAVES - 1) / Cfg::WAVES, (long long)occ * c->num_cu);
-    grid = std::min<long long>(grid, (long long)(SCAN_SCRATCH_BUDGET / wg_bytes));
-    if (grid < 1) grid = 1;
-    polar::ScanParams Q = P;
-    int rc = ensure_scratch(c, c->scratch, wg_bytes * (size_t)grid);
+    LaunchShape s{threads, lds, batches, Cfg::WAVES};
+    s.scratch_per_block = wg_bytes;
+    s.grid_cap = std::max<long long>(1, (long long)(SCAN_SCRATCH_BUDGET / wg_bytes));
+    s.set_lds_attr = false;   // the LDS holds the look-up table alone: far below the limit a kernel has anyway
+    s.alloc = ensure_scratch;
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
     if (rc) return rc;
-    Q.scratch = c->scratch.p;
-    if (batches > grid * Cfg::WAVES && (rc = work_queue(c, c->scratch, &Q.queue))) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, c->stream, Q);
+    polar::ScanParams Q = P;
+    Q.scratch = pl.scratch;
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.grid), dim3(threads), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

@@ -14,21 +14,16 @@ int launch_scf_lanes(polar_ctx *c, const polar::ScfParams &P)
     const size_t lds = Cfg::lds_bytes(P.N, P.T, MODE, waves);
     if (lds > (size_t)160 * 1024) return POLAR_ENOKERNEL;
     const int threads = 64 * waves;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
-    if (occ < 1) occ = 1;
     const long long batches = ((long long)P.B + 63) / 64;
-    int grid = (int)std::min<long long>((batches + waves - 1) / waves, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
-    polar::ScfParams Q = P;
-    int rc = ensure(c, c->scratch, polar::ScLanesCfg<R>::scratch_bytes(P.N) * (size_t)grid * waves);
+    LaunchShape s{threads, lds, batches, waves};
+    s.scratch_per_block = polar::ScLanesCfg<R>::scratch_bytes(P.N) * waves;
+    LaunchPlan pl;
+    int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
     if (rc) return rc;
-    Q.scratch = c->scratch.p;
-    Q.queue = nullptr;
-    if (batches > (long long)grid * waves && (rc = work_queue(c, c->scratch, &Q.queue))) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, c->stream, Q);
+    polar::ScfParams Q = P;
+    Q.scratch = pl.scratch;
+    Q.queue = pl.queue;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(threads), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

@@ -197,6 +197,27 @@ bool fast_ok(const polar_ctx *c, int in_is_f32)
     return true;
 }
 
+// The kernel family the fixed decoder of ctx c runs on a batch of B rows: decode_fixed() launches it, refresh_kernel_name()
+// names it.  scl_big.h for SCL / CA-SCL with N >= 512, L >= 2 (shapes without a tuned kernel); else the generic kernel,
+// LDS-resident when the levels fit (160 KB per CU), global-scratch variant otherwise.
+enum class Family { BP, DYN, SC_LANES, FAST, FAST2, FAST4, BIG, GENERIC };
+Family kernel_family(const polar_ctx *c, int in_is_f32, size_t B)
+{
+    const polar_cfg &g = c->cfg;
+    if (g.algo == POLAR_ALGO_BP) return Family::BP;
+    if (c->is_dyn) return Family::DYN;   // dynamic frozen bits: one kernel for every shape
+    if (sc_lanes_ok(c, B)) return Family::SC_LANES;
+    if (fast_ok(c, in_is_f32)) {
+#ifdef POLAR_TESTING
+        if (g.N == 1024 && c->use_fast4) return Family::FAST4;
+#endif
+        if (g.N == 1024 && c->use_fast2) return Family::FAST2;
+        return Family::FAST;
+    }
+    if (c->logL >= 1 && !c->force_generic && g.algo != POLAR_ALGO_SC && c->n >= 9) return Family::BIG;
+    return Family::GENERIC;
+}
+
 // the fixed decoder of ctx c (its cfg.L / algo): the kernel selection every entry point uses
 int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                  double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
@@ -206,7 +227,8 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     if (B > 0x7fffffffull) return POLAR_EINVAL;
     const polar_cfg &g = c->cfg;
     const bool f32 = g.dtype == POLAR_F32;
-    if (g.algo == POLAR_ALGO_BP) {
+    const Family fam = kernel_family(c, in_is_f32, B);
+    if (fam == Family::BP) {
         polar::BpParams P{};
         P.in = d_in; P.sigma = sigma; P.out_bits = d_bits; P.frozen = d_frozen;
         P.N = g.N; P.n = c->n; P.B = (int)B; P.iters = g.bp_iters;
@@ -231,21 +253,18 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     P.scratch = nullptr;
     P.queue = nullptr;
     const bool in32 = in_is_f32 != 0;
-    if (c->is_dyn) return polar_tu::scl_dyn(c, P, f32, in32);   // dynamic frozen bits: one kernel for every shape
-    if (sc_lanes_ok(c, B)) return polar_tu::sc_lanes(c, P, f32, in32);
-    if (fast_ok(c, in_is_f32)) {
-        const bool crc = g.algo == POLAR_ALGO_CASCL;
+    const bool crc = g.algo == POLAR_ALGO_CASCL;
+    switch (fam) {
+    case Family::DYN: return polar_tu::scl_dyn(c, P, f32, in32);
+    case Family::SC_LANES: return polar_tu::sc_lanes(c, P, f32, in32);
 #ifdef POLAR_TESTING
-        if (P.N == 1024 && c->use_fast4) return polar_tu::scl_fast4(c, P, f32, in32, crc);
+    case Family::FAST4: return polar_tu::scl_fast4(c, P, f32, in32, crc);
 #endif
-        if (P.N == 1024 && c->use_fast2) return polar_tu::scl_fast2(c, P, f32, in32, crc);
-        return polar_tu::scl_fast(c, P, f32, in32, crc);
+    case Family::FAST2: return polar_tu::scl_fast2(c, P, f32, in32, crc);
+    case Family::FAST: return polar_tu::scl_fast(c, P, f32, in32, crc);
+    case Family::BIG: return f32 ? polar_tu::scl_big_f32(c, P, in32) : polar_tu::scl_big_f64(c, P, in32);
+    default: return polar_tu::scl_generic(c, P, f32, in32);
     }
-    // scl_big.h for SCL / CA-SCL with N >= 512, L >= 2 (shapes without a tuned kernel); else the generic kernel,
-    // LDS-resident when the levels fit (160 KB per CU), global-scratch variant otherwise
-    if (c->logL >= 1 && !c->force_generic && !P.sc_mode && P.n >= 9)
-        return f32 ? polar_tu::scl_big_f32(c, P, in32) : polar_tu::scl_big_f64(c, P, in32);
-    return polar_tu::scl_generic(c, P, f32, in32);
 }
 
 // The stage contexts run on this ctx's stream with its test-only kernel choices (include/polar_hip_testing.h).
@@ -453,23 +472,33 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
     return POLAR_OK;
 }
 
-// the kernel instantiation decode_device_impl will launch for this ctx (mirrors its choices)
+// the kernel instantiation decode_device_impl will launch for this ctx: kernel_family() for input of the arithmetic type
+// and a large batch, then the decoders around the fixed one
 void refresh_kernel_name(polar_ctx *c)
 {
     const polar_cfg &g = c->cfg;
     const char *ty = g.dtype == POLAR_F32 ? "float" : "double";
     char nm[128];
-    if (g.algo == POLAR_ALGO_BP)
-        snprintf(nm, sizeof nm, (g.N == 1024 && !c->force_generic) ? "k_bp_r4<%s>%s" : (g.N == 128 && !c->force_generic) ? "k_bp_w128<%s>%s" : "k_bp<%s>%s",
-                 ty, c->bp_stop == POLAR_BP_STOP_G ? " (stop rule G)" : "");
-    else
-        snprintf(nm, sizeof nm, "k_scl_generic<%s,L=%d>", ty, g.L);
-    if (g.algo != POLAR_ALGO_BP && g.algo != POLAR_ALGO_SC && !c->force_generic && c->n >= 9 && g.L >= 2)
-        snprintf(nm, sizeof nm, "k_scl_big<%s,L=%d>", ty, g.L);
-    if (g.algo == POLAR_ALGO_SC && !c->force_generic && g.N <= 2048)
-        snprintf(nm, sizeof nm, "k_sc_lanes<%s> (batches of 64+; k_scl_generic below)", ty);
-    if (fast_ok(c, g.dtype == POLAR_F32))
-        snprintf(nm, sizeof nm, "k_scl_fast%s<%s,N=%d,L=8>", (g.N == 1024 && c->use_fast4) ? "4" : (g.N == 1024 && c->use_fast2) ? "2" : "", ty, g.N);
+    const Family fam = kernel_family(c, g.dtype == POLAR_F32, 64);
+    switch (fam) {
+    case Family::BP: {
+        const int v = polar_tu::bp_variant(c);
+        snprintf(nm, sizeof nm, v == polar_tu::BP_R4 ? "k_bp_r4<%s>%s" : v == polar_tu::BP_W128 ? "k_bp_w128<%s>%s" : "k_bp<%s>%s", ty,
+                 c->bp_stop == POLAR_BP_STOP_G ? " (stop rule G)" : "");
+        break;
+    }
+    case Family::DYN:   // stands alone: replaces the wrappers below as well
+        snprintf(nm, sizeof nm, "k_scl_dyn<%s,L=%d> (D=%d dynamic frozen bits)", ty, g.L, (int)c->dyn_pos.size());
+        break;
+    case Family::SC_LANES: snprintf(nm, sizeof nm, "k_sc_lanes<%s> (batches of 64+; k_scl_generic below)", ty); break;
+    case Family::FAST:
+    case Family::FAST2:
+    case Family::FAST4:
+        snprintf(nm, sizeof nm, "k_scl_fast%s<%s,N=%d,L=8>", fam == Family::FAST4 ? "4" : fam == Family::FAST2 ? "2" : "", ty, g.N);
+        break;
+    case Family::BIG: snprintf(nm, sizeof nm, "k_scl_big<%s,L=%d>", ty, g.L); break;
+    case Family::GENERIC: snprintf(nm, sizeof nm, "k_scl_generic<%s,L=%d>", ty, g.L); break;
+    }
     if (g.algo == POLAR_ALGO_SCF)
         snprintf(nm, sizeof nm, "k_scf_lanes<%s> (SC-Flip, T=%d; pass A, k_ad_fail_count/scan/write, record, pass B, k_scf_resolve)",
                  ty, c->scf_T);
@@ -487,10 +516,7 @@ void refresh_kernel_name(polar_ctx *c)
         c->kernel_name = a;
     }
     if (c->rm_mode != POLAR_RM_NONE) c->kernel_name = "k_rm_recover, then " + c->kernel_name;
-    if (c->is_dyn) {
-        snprintf(nm, sizeof nm, "k_scl_dyn<%s,L=%d> (D=%d dynamic frozen bits)", ty, g.L, (int)c->dyn_pos.size());
-        c->kernel_name = nm;
-    }
+    if (fam == Family::DYN) c->kernel_name = nm;
 }
 
 std::vector<uint32_t> pack_mask(const unsigned char *m, int N, bool invert)

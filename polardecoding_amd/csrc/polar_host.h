@@ -155,6 +155,47 @@ inline int work_queue(polar_ctx *c, Buf &scratch, unsigned **counter)
     return POLAR_OK;
 }
 
+// Launch of a persistent kernel: as many blocks as are resident at once (or as the jobs need, if fewer), each block's
+// slice of c->scratch, and the work queue when there are more jobs than the resident blocks take by their index.  A
+// k_*.hip launcher states what is particular to its kernel in a LaunchShape; plan_launch() does the rest.
+struct LaunchShape {
+    int threads;                        // block size
+    size_t lds;                         // dynamic LDS bytes per block
+    long long jobs;                     // codewords, or groups of 2 / 4 / 64 of them: what one wavefront (or block) takes at a time
+    int jobs_per_block;
+    size_t scratch_per_block = 0;       // bytes of c->scratch per block; 0: the kernel uses none
+    int occ_cap = 0;                    // at most this many blocks per CU; 0: what fits
+    long long grid_cap = 0;             // at most this many blocks; 0: no limit
+    bool set_lds_attr = true;           // raise the kernel's dynamic-LDS limit to lds first
+    bool use_queue = true;              // false: fixed stride even with more jobs than resident slots
+    int (*alloc)(polar_ctx *, Buf &, size_t) = ensure;   // grows c->scratch
+};
+struct LaunchPlan {
+    int grid;
+    void *scratch;     // c->scratch.p, or null without scratch_per_block
+    unsigned *queue;   // the counter of c->scratch, or null: every job has a resident slot
+};
+
+inline int plan_launch(polar_ctx *c, const void *kern, const LaunchShape &s, LaunchPlan *out)
+{
+    if (s.set_lds_attr) HIP_TRY(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+    int occ = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, s.threads, s.lds));
+    if (occ < 1) occ = 1;
+    if (s.occ_cap && occ > s.occ_cap) occ = s.occ_cap;
+    long long grid = std::min<long long>((s.jobs + s.jobs_per_block - 1) / s.jobs_per_block, (long long)occ * c->num_cu);
+    if (s.grid_cap) grid = std::min(grid, s.grid_cap);
+    if (grid < 1) grid = 1;
+    *out = LaunchPlan{(int)grid, nullptr, nullptr};
+    if (s.scratch_per_block) {
+        int rc = s.alloc(c, c->scratch, s.scratch_per_block * (size_t)grid);
+        if (rc) return rc;
+        out->scratch = c->scratch.p;
+    }
+    if (s.use_queue && s.jobs > grid * s.jobs_per_block) return work_queue(c, c->scratch, &out->queue);
+    return POLAR_OK;
+}
+
 // Launchers exported by the kernel translation units.  r32 / in32: arithmetic type / input type is float (else double).
 namespace polar_tu {
 int scl_generic(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32);             // k_generic.hip (uses c->logL, c->force_spill)
@@ -164,6 +205,8 @@ int sc_lanes(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32);     
 int scl_fast(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);      // k_fast.hip: N = 128, N = 1024 one codeword per wave
 int scl_fast2(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast2.hip: N = 1024, two per wave (headline)
 int bp(polar_ctx *c, const polar::BpParams &P, bool r32, bool in32);                       // k_bp.hip
+enum { BP_R4, BP_W128, BP_PLAIN };   // bp()'s kernel for this ctx: k_bp_r4, k_bp_w128, or k_bp / k_bp_global
+int bp_variant(const polar_ctx *c);                                                        // k_bp.hip
 int bp_readout(polar_ctx *c, const polar::BpReadoutParams &P, bool r32, bool in32);        // k_bp.hip
 // k_adaptive.hip: the glue of the adaptive CA-SCL decoder (adaptive_kernel.h)
 int ad_crc_check(polar_ctx *c, const uint32_t *d_bits, uint32_t *d_flags, size_t B);      // CRC syndrome of SC decisions
