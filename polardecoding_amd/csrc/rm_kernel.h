@@ -106,12 +106,12 @@ struct GenRmParams {
     int E, logS, mode;
 };
 
-// k_generate's encoder (payload, CRC multiply or systematic rows, placement, butterfly; same Philox stream 0 payload), then
-// per sent position t: e index k (channel interleaver), y index m (bit selection), codeword position J(m)
+// k_generate's encoder (gen_common.h: payload, CRC multiply or systematic rows, placement, butterfly; same Philox stream 0
+// payload), then per sent position t: e index k (channel interleaver), y index m (bit selection), codeword position J(m)
 __global__ __launch_bounds__(256) void k_generate_rm(GenRmParams R)
 {
     const GenParams &P = R.g;
-    const int N = P.N, NW = N >> 5, KR = N >> 6;
+    const int N = P.N, KR = N >> 6;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     extern __shared__ unsigned char gsm[];
     unsigned char *ub = gsm + (size_t)wave * (N + 2 * 1024);       // u bytes [N], then the codeword bytes
@@ -120,75 +120,18 @@ __global__ __launch_bounds__(256) void k_generate_rm(GenRmParams R)
     const int E = R.E, S1 = (1 << R.logS) - 1;
     for (int f = blockIdx.x * waves + wave; f < P.B; f += gridDim.x * waves) {
         const uint64_t frame = P.first_frame + (uint64_t)f;
-        const int kw = (P.K + 31) >> 5;
-        for (int w = lane; w < kw + 2; w += 64) {
-            uint32_t v = 0;
-            if (w < kw) {
-                v = Philox(P.seed, frame, (uint32_t)w, 0u).c[0];
-                if (w == kw - 1 && (P.K & 31)) v &= (1u << (P.K & 31)) - 1u;
-            }
-            vw[w] = v;
-        }
-        for (int j = lane; j < N; j += 64) ub[j] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (P.gc_rows) {
-            uint32_t par = 0;
-            for (int k = lane; k < P.K; k += 64)
-                if ((vw[k >> 5] >> (k & 31)) & 1u) par ^= P.gc_rows[k];
-            for (int o = 32; o > 0; o >>= 1) par ^= __shfl_xor(par, o);
-            for (int i = lane; i < P.A; i += 64) {
-                const int q = i - P.crc_r;
-                const uint32_t bit = (q < 0) ? ((par >> i) & 1u) : ((vw[q >> 5] >> (q & 31)) & 1u);
-                ub[P.info_order[i]] = (unsigned char)bit;
-            }
-        } else {
-            for (int i = lane; i < P.A; i += 64) {
-                uint32_t bit = 0;
-                for (int t = 0; t <= P.crc_r; ++t) {
-                    const bool tap = (t < 32) ? ((P.crc_mask >> t) & 1u) : (P.crc_top != 0);
-                    const int q = i - t;
-                    if (tap && q >= 0 && q < P.K) bit ^= (vw[q >> 5] >> (q & 31)) & 1u;
-                }
-                ub[P.info_order[i]] = (unsigned char)bit;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint64_t u = 0;
-        for (int k = 0; k < KR; ++k) u |= (uint64_t)(ub[lane + 64 * k] & 1) << k;
-        if (P.u_bits) {
-            for (int k = 0; k < KR; ++k) {
-                const uint64_t m = __ballot((u >> k) & 1ull);
-                if (lane == 0) {
-                    P.u_bits[(size_t)f * NW + 2 * k] = (uint32_t)m;
-                    P.u_bits[(size_t)f * NW + 2 * k + 1] = (uint32_t)(m >> 32);
-                }
-            }
-        }
-        uint64_t x = u;
-        for (int s = 0; s < 6 && s < P.n; ++s) {
-            const uint64_t o = __shfl_xor((unsigned long long)x, 1 << s);
-            if (!(lane & (1 << s))) x ^= o;
-        }
-        for (int s = 6; s < P.n; ++s) {
-            const int sh = 1 << (s - 6);
-            uint64_t msk = 0;
-            for (int k = 0; k < KR; ++k)
-                if (!(k & sh)) msk |= 1ull << k;
-            x ^= (x >> sh) & msk;
-        }
+        gen_place(P, frame, lane, ub, vw);
+        const uint64_t u = gen_pack(ub, lane, KR);
+        gen_emit_u(P, f, u, lane, KR);
+        const uint64_t x = gen_encode(u, lane, P.n, KR);
         __builtin_amdgcn_wave_barrier();   // every lane has read its u bytes before they become codeword bytes
         for (int k = 0; k < KR; ++k) ub[lane + 64 * k] = (unsigned char)((x >> k) & 1ull);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // sent positions t = 2q, 2q + 1: one Philox block (stream 2) per pair, normal (t & 1) of it
         for (int q = lane; 2 * q < E; q += 64) {
-            const Philox g(P.seed, frame, (uint32_t)q, 2u);
-            const double r = sqrt(-2.0 * log(g.u0()));
-            double sn, cs;
-            sincospi(2.0 * g.u1(), &sn, &cs);
-            const double nz[2] = {r * cs, r * sn};
+            double nz[2];
+            gen_normal_pair(P.seed, frame, (uint32_t)q, 2u, nz);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int t = 2 * q + h;
@@ -196,10 +139,7 @@ __global__ __launch_bounds__(256) void k_generate_rm(GenRmParams R)
                 const int k = R.ilv_inv ? (int)R.ilv_inv[t] : t;
                 const int m = (R.mode == RM_REPEAT) ? (k & (N - 1)) : (R.mode == RM_PUNCTURE) ? k + N - E : k;
                 const int j = ((int)kRmP[m >> R.logS] << R.logS) | (m & S1);
-                const double yv = (ub[j] ? -1.0 : 1.0) + P.sigma * nz[h];
-                const double v = P.out_is_y ? yv : 2 * yv / P.sigma / P.sigma;
-                if (P.out_is_f32) reinterpret_cast<float *>(P.out)[(size_t)f * E + t] = (float)v;
-                else reinterpret_cast<double *>(P.out)[(size_t)f * E + t] = v;
+                gen_put(P, (size_t)f * E + t, ub[j], nz[h]);
             }
         }
         __builtin_amdgcn_wave_barrier();

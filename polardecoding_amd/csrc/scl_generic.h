@@ -18,6 +18,9 @@
 // Schedule = the reference's lazy recursion getLLR/updateBit (SCL_1024.c:404-448) in its
 // natural-order form.  This kernel is the correctness baseline and
 // the fallback for shapes without a tuned instantiation; scl_fast.h holds the tuned ones.
+//
+// The kernel text is scl_generic_body<..., DYN>; k_scl_generic is its DYN = false wrapper and k_scl_dyn (scl_dyn.h, which
+// says what DYN adds: a per-path history of the decided bits and the dynamic frozen leaf) its DYN = true wrapper.
 #pragma once
 #include "polar_math.h"
 #include "polar_lut.h"
@@ -47,8 +50,9 @@ __device__ __forceinline__ float ld_bypass(const float *p) { return __hip_atomic
 // GA = false: every LLR level of every path in LDS.  GA = true ("LLRs spill HBM", BASELINE config 5): the
 // level arrays alpha[L][N] live in a per-workgroup slice of a global scratch buffer and the channel LLRs are
 // read from the input; only the bit-packed partial sums stay in LDS.
-template <typename R, typename IN, int LOGL, bool GA>
-__global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
+// DYN = false: dyn_mask and dyn_row are never read.
+template <typename R, typename IN, int LOGL, bool GA, bool DYN>
+__device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint32_t *dyn_mask, const int *dyn_row)
 {
     constexpr int L = 1 << LOGL;
     constexpr int S = 64 / L;
@@ -72,6 +76,9 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
     R *cand = reinterpret_cast<R *>(curw + (size_t)L * NW);
     // table-driven staircase (polar_lut.h): same bits as polar_math.h's chk / phi, a third of the instructions
     unsigned char *lut_mem = reinterpret_cast<unsigned char *>(cand + 2 * L);
+    // DYN: hist[L][NW] behind cand (L * NW may be odd, cand holds doubles) and the tables behind hist
+    uint32_t *hist = reinterpret_cast<uint32_t *>(cand + 2 * L);
+    if constexpr (DYN) lut_mem = reinterpret_cast<unsigned char *>(hist + (size_t)L * NW);
     lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
     Lut<R>::build(lut_mem, lane, 64);
     Lut<R> lut;
@@ -92,11 +99,14 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
                 ch[i] = (R)v;
             }
         }
+        if constexpr (DYN)
+            for (int w = lane; w < L * NW; w += 64) hist[w] = 0u;
         __syncthreads();
 
         R PM = R(0);
         uint64_t ptrA = 0;
         uint32_t crc = 0, bl0 = 0, cur0 = 0;
+        uint32_t h0 = 0;   // DYN: word 0 of the path's history, shuffled with the path like bl0
         uint32_t fl = 0;
         int act = 1;
 
@@ -135,8 +145,25 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
 
             // ================= decision =================
             const bool frozen = (P.frozen[j >> 5] >> (j & 31)) & 1;
+            int row = -1;   // DYN: row of leaf j in the constraint matrix, -1 = not dynamic (wave-uniform, like j)
+            if constexpr (DYN) row = dyn_row[j];
             int bit = 0;
-            if (P.sc_mode) {
+            if (row >= 0) {
+                // dynamic frozen leaf: b = parity of (history AND mask row) over the words 0 .. j >> 5, on every lane of the
+                // wave (lanes of dead paths compute and discard); no fork, no ranking, no tie flag
+                if constexpr (DYN) {
+                    const uint32_t *mrow = dyn_mask + (size_t)row * NW;
+                    uint32_t par = 0;
+                    for (int w = pos; w <= (j >> 5); w += S) {
+                        const uint32_t hw = (w == 0) ? h0 : hist[p * NW + w];
+                        par ^= (uint32_t)__popc(hw & mrow[w]);
+                    }
+                    for (int o = S >> 1; o > 0; o >>= 1) par ^= (uint32_t)__shfl_xor((int)par, o);
+                    bit = (int)(par & 1u);
+                    // PHI(., b) with the rounding of an information leaf's branch b
+                    if (!P.sc_mode && p < act) PM = PM + (lut.tabv(lam) + (bit ? posmax(lam) : negmax(lam)));
+                }
+            } else if (P.sc_mode) {
                 bit = (!frozen && lam < R(0)) ? 1 : 0;  // SC_128.c:426-431
             } else if (frozen) {
                 if (p < act) PM += lut.tabv(lam) + negmax(lam);  // PHI(.,0), SCL_1024.c:601-604, :662-665
@@ -150,8 +177,12 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
                 ptrA = __shfl(ptrA, sl);
                 crc = __shfl(crc, sl);
                 bl0 = __shfl(bl0, sl);
+                if constexpr (DYN) h0 = __shfl(h0, sl);
                 if (is_new) {
-                    for (int w = 1 + pos; w < NW; w += S) blw[p * NW + w] = blw[sg * NW + w];
+                    for (int w = 1 + pos; w < NW; w += S) {
+                        blw[p * NW + w] = blw[sg * NW + w];
+                        if constexpr (DYN) hist[p * NW + w] = hist[sg * NW + w];
+                    }
                     bit = 1;
                     PM = pm_s + (lut.tabv(lam_s) + posmax(lam_s));
                 } else if (p < act) {
@@ -206,8 +237,12 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
                 ptrA = __shfl(ptrA, sl);
                 crc = __shfl(crc, sl);
                 bl0 = __shfl(bl0, sl);
+                if constexpr (DYN) h0 = __shfl(h0, sl);
                 if (refilled) {
-                    for (int w = 1 + pos; w < NW; w += S) blw[p * NW + w] = blw[sg * NW + w];
+                    for (int w = 1 + pos; w < NW; w += S) {
+                        blw[p * NW + w] = blw[sg * NW + w];
+                        if constexpr (DYN) hist[p * NW + w] = hist[sg * NW + w];
+                    }
                     bit = 1;
                     PM = c1_s;
                 } else if (s0) {
@@ -221,6 +256,16 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
                     PM = c0;
                 }
                 __syncthreads();
+            }
+
+            // ================= DYN: bit j of the path's history =================
+            if constexpr (DYN) {
+                if (j < 32) {
+                    h0 |= (uint32_t)bit << j;
+                } else {
+                    if (pos == 0 && p < act && bit) hist[p * NW + (j >> 5)] |= 1u << (j & 31);
+                    __syncthreads();
+                }
             }
 
             // ================= partial sums (updateBit, SCL_1024.c:424-448) =================
@@ -287,8 +332,11 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
             }
             if (any) fl |= 0x2u;
         }
-        // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}
-        if (n <= 5) {
+        // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
+        if constexpr (DYN) {
+            const uint32_t w0 = __shfl(h0, best * S);
+            for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = (w == 0) ? w0 : hist[best * NW + w];
+        } else if (n <= 5) {
             uint32_t x = __shfl(cur0, best * S);
             for (int s = 0; s < n; ++s) {
                 const uint32_t msk = (s == 0) ? 0x55555555u : (s == 1) ? 0x33333333u : (s == 2) ? 0x0F0F0F0Fu
@@ -322,6 +370,12 @@ __global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
         }
         __syncthreads();
     }
+}
+
+template <typename R, typename IN, int LOGL, bool GA>
+__global__ __launch_bounds__(64) void k_scl_generic(SclParams P)
+{
+    scl_generic_body<R, IN, LOGL, GA, false>(P, nullptr, nullptr);
 }
 
 template <typename R, int LOGL>
