@@ -38,6 +38,7 @@ extern "C" {
 /* dtype: the arithmetic type the message passing runs in */
 #define POLAR_F64 0 /* IEEE binary64 like the reference: bit-identical decisions (the parity gate) */
 #define POLAR_F32 1 /* binary32: same operation order, FER-equivalent, not bit-identical           */
+#define POLAR_Q8 2  /* fixed-point min-sum on int8 LLRs (SC / SCL / CA-SCL, N <= 1024): the section below */
 
 /* error codes */
 #define POLAR_OK 0
@@ -71,7 +72,7 @@ typedef struct polar_cfg {
     int bp_iters;          /* BP round trips (reference: iterMax = 100, BP_1024.c:16)                    */
     const int *info_order; /* I[0..K+crc_r): unfrozen positions in reliability order (I[i] = Q[N-(K+r)+i]).
                               NULL -> built from the 5G sequence like the reference does.                 */
-    int dtype;             /* POLAR_F64 | POLAR_F32                                                      */
+    int dtype;             /* POLAR_F64 | POLAR_F32 | POLAR_Q8                                           */
     int device;            /* HIP device ordinal                                                         */
     int crc_systematic;    /* 0: the CRC word is v(D) g(D) (CASCL_1024_L8.c:251-266).  1: CASCL_1024_sys.c:
                               systematic cyclic encoding, w[0..r) = D^r v(D) mod g, w[r..K+r) = v (:776-789), and
@@ -529,6 +530,60 @@ int polar_get_systematic(const polar_ctx *ctx);
 /* host only, touches no device: 1 if the two-pass encoder is systematic on info_order[0..A), 0 if not; POLAR_EINVAL for N not a
  * power of two in 32..4096, A outside 1..N, or positions that are out of range or repeated */
 int polar_systematic_check(int N, const int *info_order, int A);
+
+/* --- Fixed-point min-sum decoding: int8 SC / SCL / CA-SCL (dtype POLAR_Q8; no reference counterpart) ----------------------
+ * The decoder of hardware papers and 5G receivers: quantised LLRs, a check node that is a sign and a minimum, integer path
+ * metrics.  Integer arithmetic has no rounding, so everything below is exact and is tested with == against a numpy model.
+ * A Q8 context has a quantiser (scale, qc, qi): scale > 0 and finite, 2 <= qc <= qi <= 8, Cc = 2^(qc-1) - 1 the clamp of
+ * the channel values and Ci = 2^(qi-1) - 1 the clamp of the internal values.  The defaults scale = 2.0, qc = qi = 8 are a
+ * choice: they have not been tuned and no FER stands behind them.
+ *   1. quantiser: for an input value v, t = v * scale in double with one rounding (a float input is converted to double
+ *      first; with sigma > 0, v = 2*y/sigma/sigma in that order); q = rint(t), ties to even, then clamped to [-Cc, Cc];
+ *      NaN gives 0.  Rows handed in as int8 directly are clamped to [-Cc, Cc] on load, so -128 becomes -Cc.
+ *   2. node arithmetic, all in integers: f(a, b) = s * min(|a|, |b|) with s = -1 iff (a < 0) != (b < 0);
+ *      g(a, b, u) = clamp(b + (u ? -a : a), -Ci, Ci).  The schedule is SC's: leaf j's LLR lambda comes from the channel row
+ *      through f on left branches and g, with the path's partial sums, on right branches: the tree of every decoder here.
+ *   3. list order: the live paths form an ordered list; a path's position in it is its rank r.  At the start there is one
+ *      path, rank 0, PM = 0.  PM is int32.
+ *   4. frozen leaf: the bit is 0; PM += |lambda| if lambda < 0; ranks are unchanged.
+ *   5. information leaf with m live paths: the 2m candidates (p, b) have PM_c = PM_p + (b != [lambda_p < 0] ? |lambda_p| : 0).
+ *      They are sorted ascending by the triple (PM_c, b, r_p) and the first min(2m, L) are kept; the new ranks are the
+ *      positions in that order.  PM <= N * Ci < 2^17, so (PM_c << 6) | (b << 5) | r_p is a 32-bit key, no two equal, and
+ *      ranking by counting on it is exact.  POLAR_FLAG_TIE is set iff at some leaf with 2m > L the candidates at sorted
+ *      positions L - 1 and L have equal PM_c.
+ *   6. output.  POLAR_ALGO_SCL: the path with the smallest (PM, r).  POLAR_ALGO_CASCL: among the paths whose CRC remainder
+ *      (XOR over {j : u_hat_j = 1} of crc_tab[j], crc_tab[I[i]] = D^i mod g(D), as in the float decoders) is 0 the smallest
+ *      (PM, r), with POLAR_FLAG_CRC_PASS set; if no path passes, the smallest (PM, r) overall with the flag clear.
+ *      POLAR_ALGO_SC: L = 1, u_hat_j = [lambda < 0] at information leaves, metric 0, flags 0.  u_hat is 0 at frozen
+ *      positions.  The metric is PM (exact also where an entry point stores it as a double).
+ *   7. composition: a decode of float or double rows on a Q8 context IS rule 1 followed by rules 2-6.
+ * polar_create with dtype POLAR_Q8 accepts POLAR_ALGO_SC, POLAR_ALGO_SCL and POLAR_ALGO_CASCL with 32 <= N <= 1024 and L a
+ * power of two in 1..32 (SC: 1), and returns POLAR_ENOKERNEL, before any device is touched, for N > 1024 and for
+ * POLAR_ALGO_BP, POLAR_ALGO_SCF and POLAR_ALGO_SCAN.  polar_create_crc_file works (it only supplies g(D)).
+ * Honoured through rule 7, the quantised rows in ctx-owned scratch (chunks of at most 256 MiB): polar_decode,
+ * polar_decode_batch(_y) (a frozen_mask override returns POLAR_EINVAL), polar_decode_device, polar_cascl_decode_device /
+ * _batch (d_list = cfg.L), polar_fer_batch (it generates f32 rows, quantises, decodes and counts), polar_stop_rule_batch_y
+ * and polar_time_decode_device (which therefore times the quantiser too).  polar_kernel_name is "k_scl_q8<L=...>",
+ * polar_ctx_info reports dtype 2.  Type-independent calls work unchanged: polar_generate_device, polar_count_errors_device,
+ * the encode / payload / transform calls.  The scratch grows with B on first use: warm a ctx at its largest B before
+ * capturing its stream into a graph.
+ * POLAR_EINVAL, the ctx staying usable: polar_create_rm, polar_create_dyn, polar_group_create and polar_fer_multi_gpu with a
+ * Q8 cfg; polar_set_systematic(ctx, 1), polar_cascl_set_stages, polar_genie_*, polar_construct_batch, polar_bp_*,
+ * polar_scf_* and polar_scan_* on a Q8 ctx; polar_q8_* (but polar_q8_quantize_host) on a ctx of another dtype.
+ * Out of scope: a one-codeword-per-lane int8 SC kernel (SC is L = 1 of the list kernel), N > 1024, rate-matched, dynamic,
+ * systematic and adaptive Q8 contexts, PM saturation or normalisation, offset or normalised min-sum. */
+/* POLAR_EINVAL with the ctx unchanged: not a Q8 ctx, or values out of range */
+int polar_q8_set_quant(polar_ctx *ctx, double scale, int qc, int qi);
+int polar_q8_get_quant(const polar_ctx *ctx, double *scale, int *qc, int *qi);   /* each output nullable */
+/* rule 1 on n host values.  Host only, touches no device.  POLAR_EINVAL: scale or qc out of range, a NaN sigma. */
+int polar_q8_quantize_host(const double *in, size_t n, double sigma, double scale, int qc, int8_t *out);
+/* rule 1 with the ctx's quantiser, asynchronous on the ctx stream: d_in [B][N] double (in_is_f32 = 0) or float -> d_out [B][N] */
+int polar_q8_quantize_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, int8_t *d_out);
+/* rules 2-6 on quantised rows d_q [B][N] (4-byte aligned).  Asynchronous on the ctx stream, no read-back: after a warm-up at
+ * the same B it can be captured into a graph.  d_uhat_bits [B][N/32]; d_pm (nullable) [B] int32; d_flags (nullable) [B]. */
+int polar_q8_decode_device(polar_ctx *ctx, const int8_t *d_q, size_t B, uint32_t *d_uhat_bits, int32_t *d_pm, uint32_t *d_flags);
+/* host-buffer form: q [B][N], u_hat [B][N] ints 0/1, pm and flags (nullable) [B] */
+int polar_q8_decode_batch(polar_ctx *ctx, const int8_t *q, size_t B, int *u_hat, int32_t *pm, unsigned *flags);
 
 /* --- device-side transmit chain, throughput mode (the frame loop of main(), CASCL_1024_L8.c:245-292) -----------
  * Fills B frames: random payload -> CRC multiply by g(D) -> u[I[i]] -> x = u F^{(x)n} -> BPSK + AWGN at

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF, ALGO_SCAN = 0, 1, 2, 3, 4, 5
-F64, F32 = 0, 1
+F64, F32, Q8 = 0, 1, 2   # Q8: fixed-point min-sum on int8 LLRs (SC / SCL / CA-SCL, N <= 1024)
 FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
 RM_NONE, RM_REPEAT, RM_PUNCTURE, RM_SHORTEN = 0, 1, 2, 3   # polar_rm_info modes (5G rate matching)
 RM_SHORT_LLR = 1048576.0   # POLAR_RM_SHORT_LLR: the recovered value at a shortened position
@@ -147,6 +147,12 @@ def load_library(testing=False):
     L.polar_set_systematic.argtypes = [vp, C.c_int]
     L.polar_get_systematic.argtypes = [vp]
     L.polar_systematic_check.argtypes = [C.c_int, ip, C.c_int]
+    L.polar_q8_set_quant.argtypes = [vp, C.c_double, C.c_int, C.c_int]
+    L.polar_q8_get_quant.argtypes = [vp, dp, ip, ip]
+    L.polar_q8_quantize_host.argtypes = [dp, C.c_size_t, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int8)]
+    L.polar_q8_quantize_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp]
+    L.polar_q8_decode_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    L.polar_q8_decode_batch.argtypes = [vp, C.POINTER(C.c_int8), C.c_size_t, ip, C.POINTER(C.c_int32), up]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -192,6 +198,18 @@ def q_sequence(N):
 
 def _ptr(a, ty):
     return a.ctypes.data_as(C.POINTER(ty))
+
+
+def q8_quantize(values, scale=2.0, qc=8, sigma=0.0):
+    """polar_q8_quantize_host (include/polar_hip.h, fixed-point min-sum, rule 1): values of any shape -> int8 of that shape,
+    rint(v * scale) clamped to +-(2^(qc-1) - 1), v = 2*y/sigma/sigma when sigma > 0.  Host only."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    out = np.empty(v.shape, dtype=np.int8)
+    rc = lib.polar_q8_quantize_host(_ptr(v, C.c_double), v.size, float(sigma), float(scale), int(qc), _ptr(out, C.c_int8))
+    if rc != 0:
+        raise PolarError(f"polar_q8_quantize_host: {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return out
 
 
 def rm_select_n(A, E, n_max=10):
@@ -346,8 +364,9 @@ class Decoder:
     """One polar_ctx: a (N, K, CRC, L, algo, dtype) configuration bound to one GPU."""
 
     def __init__(self, N, K, algo, L=1, crc_taps=None, bp_iters=100, dtype=F64, device=0, info_order=None,
-                 systematic=False, crc_file=None, E=None, ibil=False, dyn=None, sys_polar=False, _library=None):
-        """dyn = (pos, sets): dynamic frozen bits (polar_create_dyn): pos ascending frozen positions, sets[d] the earlier
+                 systematic=False, crc_file=None, E=None, ibil=False, dyn=None, sys_polar=False, quant=None, _library=None):
+        """quant = (scale, qc, qi): the quantiser of a dtype=Q8 decoder (polar_q8_set_quant; None: scale 2.0, 8 and 8 bits).
+        dyn = (pos, sets): dynamic frozen bits (polar_create_dyn): pos ascending frozen positions, sets[d] the earlier
         positions whose decided bits u_hat[pos[d]] is the XOR of (SC / SCL / CA-SCL only; see dyn_pac, dyn_pc5g).
         E: 5G rate matching (polar_create_rm): every decode takes rows of E channel values and generate_device writes
         them; ibil: with the channel interleaver (uplink).
@@ -401,6 +420,9 @@ class Decoder:
         self._sys_polar = False
         if sys_polar:
             self.set_systematic(True)
+        self._quant = None
+        if quant is not None:
+            self.set_quant(*quant)
 
     def _create(self):
         if self._dyn is not None:
@@ -435,6 +457,8 @@ class Decoder:
         if self._sys_polar:
             self._sys_polar = False
             self.set_systematic(True)
+        if self._quant is not None:
+            self.set_quant(*self._quant)
 
     @property
     def info_order(self):
@@ -504,6 +528,69 @@ class Decoder:
         (PolarError, decoder unchanged) on dynamic and rate-matched decoders and when systematic_check fails."""
         self._check(self._lib.polar_set_systematic(self._h, 1 if on else 0), "polar_set_systematic")
         self._sys_polar = bool(on)
+
+    def set_quant(self, scale, qc=8, qi=8):
+        """polar_q8_set_quant (dtype=Q8 decoders): scale > 0, 2 <= qc <= qi <= 8 bits for the channel / the internal LLRs."""
+        self._check(self._lib.polar_q8_set_quant(self._h, float(scale), int(qc), int(qi)), "polar_q8_set_quant")
+        self._quant = (float(scale), int(qc), int(qi))
+
+    @property
+    def quant(self):
+        """polar_q8_get_quant: (scale, qc, qi) of a dtype=Q8 decoder"""
+        sc, qc, qi = C.c_double(), C.c_int(), C.c_int()
+        self._check(self._lib.polar_q8_get_quant(self._h, C.byref(sc), C.byref(qc), C.byref(qi)), "polar_q8_get_quant")
+        return sc.value, qc.value, qi.value
+
+    def quantize(self, rows, sigma=0.0):
+        """rule 1 with this decoder's quantiser on host values (q8_quantize): rows of LLRs, or of y when sigma > 0 -> int8"""
+        sc, qc, _ = self.quant
+        return q8_quantize(rows, sc, qc, sigma)
+
+    def quantize_device(self, d_in, sigma=0.0, out=None):
+        """polar_q8_quantize_device: d_in [B][N] float64 / float32 CUDA tensor -> int8 tensor [B][N].  Asynchronous."""
+        import torch
+        B = self._dev_rows(d_in)
+        if d_in.dtype not in (torch.float64, torch.float32):
+            raise ValueError("input must be float64 or float32")
+        if out is None:
+            out = torch.empty((B, self.N), dtype=torch.int8, device=d_in.device)
+        if out.dtype != torch.int8 or not out.is_contiguous() or out.numel() < B * self.N:
+            raise ValueError("out must be a contiguous int8 tensor with B * N elements")
+        self._check(self._lib.polar_q8_quantize_device(self._h, C.c_void_p(d_in.data_ptr()), 1 if d_in.dtype == torch.float32 else 0,
+                                                       float(sigma), B, C.c_void_p(out.data_ptr())), "polar_q8_quantize_device")
+        return out
+
+    def decode_q8_device(self, d_q, out_bits=None, pm=None, flags=None):
+        """polar_q8_decode_device: d_q int8 CUDA tensor [B][N] -> out_bits int32 [B][N/32]; pm (int32 [B]) and flags (int32
+        [B]) are optional tensors.  Asynchronous, no read-back."""
+        import torch
+        B = self._dev_rows(d_q)
+        if d_q.dtype != torch.int8:
+            raise ValueError("input must be int8")
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_q.device)
+        for t in (pm, flags):
+            if t is not None and (t.numel() < B or t.element_size() != 4 or not t.is_contiguous()):
+                raise ValueError("pm / flags must be contiguous 32-bit tensors of at least B elements")
+        self._check(self._lib.polar_q8_decode_device(
+            self._h, C.c_void_p(d_q.data_ptr()), B, C.c_void_p(out_bits.data_ptr()),
+            C.c_void_p(pm.data_ptr()) if pm is not None else None,
+            C.c_void_p(flags.data_ptr()) if flags is not None else None), "polar_q8_decode_device")
+        return out_bits
+
+    def decode_q8_batch(self, q):
+        """polar_q8_decode_batch: q int8 [B][N] -> (u_hat [B][N] int32, pm [B] int32, flags [B] uint32)"""
+        q = np.ascontiguousarray(q, dtype=np.int8)
+        if q.ndim == 0 or q.shape[-1] != self.N:
+            raise ValueError(f"rows must have {self.N} values (shape [B][{self.N}])")
+        q = q.reshape(-1, self.N)
+        B = q.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        pm = np.zeros(B, dtype=np.int32)
+        fl = np.zeros(B, dtype=np.uint32)
+        self._check(self._lib.polar_q8_decode_batch(self._h, _ptr(q, C.c_int8), B, _ptr(uh, C.c_int), _ptr(pm, C.c_int32),
+                                                    _ptr(fl, C.c_uint)), "polar_q8_decode_batch")
+        return uh, pm, fl
 
     @property
     def sys_polar(self):

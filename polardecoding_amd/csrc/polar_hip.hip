@@ -218,6 +218,30 @@ Family kernel_family(const polar_ctx *c, int in_is_f32, size_t B)
     return Family::GENERIC;
 }
 
+// A Q8 ctx on float or double rows (include/polar_hip.h, fixed-point min-sum, rule 7): rule 1 into ctx scratch in chunks of
+// at most 256 MiB of quantised rows, then k_scl_q8; the int32 metric reaches a double d_pm through q8_pm.  c->q8_rows belongs
+// to c->stream (polar_fer_batch swaps it with q8_rows_b).
+int q8_decode_rows(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
+                   uint32_t *d_flags)
+{
+    const size_t esz = in_is_f32 ? 4 : 8;
+    if (reinterpret_cast<uintptr_t>(d_in) % esz) return POLAR_EINVAL;
+    const size_t N = (size_t)c->cfg.N;
+    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / N));
+    int rc;
+    if ((rc = ensure(c, c->q8_rows, CH * N))) return rc;
+    if (d_pm && (rc = ensure(c, c->q8_pm, CH * sizeof(int32_t)))) return rc;
+    for (size_t off = 0; off < B; off += CH) {
+        const size_t nc = std::min(CH, B - off);
+        int8_t *rows = (int8_t *)c->q8_rows.p;
+        int32_t *pm = d_pm ? (int32_t *)c->q8_pm.p : nullptr;
+        if ((rc = polar_tu::q8_quantize(c, (const char *)d_in + off * N * esz, in_is_f32 != 0, sigma, nc * N, rows))) return rc;
+        if ((rc = polar_tu::q8_decode(c, rows, nc, d_bits + off * (size_t)c->NW, pm, d_flags ? d_flags + off : nullptr))) return rc;
+        if (d_pm && (rc = polar_tu::q8_pm_f64(c, pm, nc, d_pm + off))) return rc;
+    }
+    return POLAR_OK;
+}
+
 // the fixed decoder of ctx c (its cfg.L / algo): the kernel selection every entry point uses
 int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                  double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr)
@@ -226,6 +250,7 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     if (B == 0) return POLAR_OK;
     if (B > 0x7fffffffull) return POLAR_EINVAL;
     const polar_cfg &g = c->cfg;
+    if (g.dtype == POLAR_Q8) return q8_decode_rows(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags);
     const bool f32 = g.dtype == POLAR_F32;
     const Family fam = kernel_family(c, in_is_f32, B);
     if (fam == Family::BP) {
@@ -503,6 +528,7 @@ void refresh_kernel_name(polar_ctx *c)
         snprintf(nm, sizeof nm, "k_scf_lanes<%s> (SC-Flip, T=%d; pass A, k_ad_fail_count/scan/write, record, pass B, k_scf_resolve)",
                  ty, c->scf_T);
     if (g.algo == POLAR_ALGO_SCAN) snprintf(nm, sizeof nm, "k_scan_lanes<%s> (SCAN, I=%d)", ty, c->scan_I);
+    if (g.dtype == POLAR_Q8) snprintf(nm, sizeof nm, "k_scl_q8<L=%d>", g.L);   // one kernel for SC / SCL / CA-SCL and every shape
     c->kernel_name = nm;
     if (!c->cascl_stages.empty()) {
         sync_stage_ctx(c);
@@ -558,7 +584,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : N;   // values per input row
     const uint32_t *d_frozen = c->d_frozen;
     if (frozen_mask) {
-        if (has_crc(c->cfg.algo) || c->rm_mode != POLAR_RM_NONE || c->is_dyn) return POLAR_EINVAL;
+        if (has_crc(c->cfg.algo) || c->rm_mode != POLAR_RM_NONE || c->is_dyn || c->cfg.dtype == POLAR_Q8) return POLAR_EINVAL;
         std::vector<uint32_t> w = pack_mask(frozen_mask, N, false);
         if (!c->d_frozen_override) HIP_TRY(c, hipMalloc(&c->d_frozen_override, NW * sizeof(uint32_t)));
         HIP_TRY(c, hipMemcpyAsync(c->d_frozen_override, w.data(), NW * sizeof(uint32_t), hipMemcpyHostToDevice,
@@ -737,7 +763,7 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     if (N < 32 || N > 4096 || (N & (N - 1))) return POLAR_EINVAL;
     if (cfg->K < 1 || cfg->crc_r < 0 || cfg->crc_r > 32 || cfg->K + cfg->crc_r > N) return POLAR_EINVAL;
     if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCAN) return POLAR_EINVAL;
-    if (cfg->dtype != POLAR_F64 && cfg->dtype != POLAR_F32) return POLAR_EINVAL;
+    if (cfg->dtype != POLAR_F64 && cfg->dtype != POLAR_F32 && cfg->dtype != POLAR_Q8) return POLAR_EINVAL;
     int L = cfg->L;
     if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF || cfg->algo == POLAR_ALGO_SCAN) L = 1;
     if (L < 1 || L > 32 || (L & (L - 1))) return POLAR_EINVAL;
@@ -745,6 +771,9 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     if (cfg->algo == POLAR_ALGO_BP && cfg->bp_iters < 1) return POLAR_EINVAL;
     if (cfg->algo == POLAR_ALGO_SCF && N > 2048) return POLAR_ENOKERNEL;   // one codeword per lane: N <= 2048
     if (cfg->algo == POLAR_ALGO_SCAN && N > polar::SCAN_MAX_N) return POLAR_ENOKERNEL;
+    // fixed-point min-sum: SC / SCL / CA-SCL up to N = 1024
+    if (cfg->dtype == POLAR_Q8 && (N > 1024 || (cfg->algo != POLAR_ALGO_SC && cfg->algo != POLAR_ALGO_SCL && cfg->algo != POLAR_ALGO_CASCL)))
+        return POLAR_ENOKERNEL;
 
     polar_ctx *c = new (std::nothrow) polar_ctx();
     if (!c) return POLAR_ENOMEM;
@@ -865,7 +894,7 @@ void polar_destroy(polar_ctx *c)
     }
     for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
     for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
-                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->scan_llr, &c->scan_ext, &c->rm_rows, &c->rm_rows_b, &c->genie_rows})
+                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->scan_llr, &c->scan_ext, &c->rm_rows, &c->rm_rows_b, &c->genie_rows, &c->q8_rows, &c->q8_rows_b, &c->q8_pm})
         if (b->p) (void)hipFree(b->p);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
@@ -962,6 +991,7 @@ int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out)
     if (!cfg || !out) return POLAR_EINVAL;
     *out = nullptr;
     if (cfg->info_order || (ibil != 0 && ibil != 1)) return POLAR_EINVAL;
+    if (cfg->dtype == POLAR_Q8) return POLAR_EINVAL;   // no rate-matched fixed-point contexts
     if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCAN) return POLAR_EINVAL;
     const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
     if (cfg->K < 1 || r < 0 || r > 32) return POLAR_EINVAL;
@@ -1014,6 +1044,7 @@ int polar_create_dyn(const polar_cfg *cfg, const polar_dyn *dyn, polar_ctx **out
     const int N = cfg->N;
     if (N < 32 || N > 4096 || (N & (N - 1))) return POLAR_EINVAL;
     if (cfg->algo != POLAR_ALGO_SC && cfg->algo != POLAR_ALGO_SCL && cfg->algo != POLAR_ALGO_CASCL) return POLAR_EINVAL;
+    if (cfg->dtype == POLAR_Q8) return POLAR_EINVAL;   // no dynamic fixed-point contexts
     const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
     if (cfg->K < 1 || r < 0 || r > 32 || cfg->K + r > N) return POLAR_EINVAL;
     if (N > 1024) return POLAR_ENOKERNEL;
@@ -1256,7 +1287,7 @@ int polar_bp_set_stop(polar_ctx *c, int rule)
 
 int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
 {
-    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || c->is_dyn || n < 0 || n > 6 || (n > 0 && !stages)) return POLAR_EINVAL;
+    if (!c || c->cfg.algo != POLAR_ALGO_CASCL || c->is_dyn || c->cfg.dtype == POLAR_Q8 || n < 0 || n > 6 || (n > 0 && !stages)) return POLAR_EINVAL;
     for (int i = 0; i < n; ++i) {
         const int L = stages[i];
         if (L < 1 || L > 32 || (L & (L - 1)) || (i && L <= stages[i - 1])) return POLAR_EINVAL;
@@ -1523,7 +1554,7 @@ int polar_stop_rule_batch_y(polar_ctx *c, const double *y, double sigma, const u
 // ---- Monte-Carlo construction (include/polar_hip.h) ---------------------------------------------------------------------
 int polar_genie_count_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint64_t *d_counts)
 {
-    if (!c || c->rm_mode != POLAR_RM_NONE || !d_in || !d_counts || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_in || !d_counts || B > 0x7fffffffull) return POLAR_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_in) % (in_is_f32 ? 4 : 8)) || (reinterpret_cast<uintptr_t>(d_counts) % 8)) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::genie_count(c, d_in, in_is_f32 != 0, sigma, B, reinterpret_cast<unsigned long long *>(d_counts));
@@ -1532,7 +1563,7 @@ int polar_genie_count_device(polar_ctx *c, const void *d_in, int in_is_f32, doub
 int polar_genie_rows_device(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
                             void *d_out, int out_is_f32)
 {
-    if (!c || c->rm_mode != POLAR_RM_NONE || !d_out || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
+    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_out || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_out) % (out_is_f32 ? 4 : 8)) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::genie_rows(c, seed, first_frame, sigma, B, d_out, out_is_f32 != 0);
@@ -1542,7 +1573,7 @@ int polar_genie_rows_device(polar_ctx *c, unsigned long long seed, unsigned long
 int polar_construct_batch(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
                           uint64_t *d_counts)
 {
-    if (!c || c->rm_mode != POLAR_RM_NONE || !d_counts || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
+    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_counts || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_counts) % 8) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
@@ -1617,7 +1648,7 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
 {
     const int NW = c->NW;
     const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : c->cfg.N;   // values per generated row
-    const bool f32 = c->cfg.dtype == POLAR_F32;
+    const bool f32 = c->cfg.dtype != POLAR_F64;   // a Q8 ctx generates f32 rows and quantises them
     int rc;
     if ((rc = ensure(c, c->gen_llr, B * W * (f32 ? 4 : 8)))) return rc;
     if ((rc = ensure(c, c->gen_u, B * NW * 4))) return rc;
@@ -1651,11 +1682,13 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
         std::swap(c->stream, c->stream_b);
         std::swap(c->scratch, c->scratch_b);
         std::swap(c->rm_rows, c->rm_rows_b);
+        std::swap(c->q8_rows, c->q8_rows_b);
         rc = run_part(half, B - half);
         hipError_t e = hipEventRecord(c->ev_b, c->stream);
         std::swap(c->stream, c->stream_b);
         std::swap(c->scratch, c->scratch_b);
         std::swap(c->rm_rows, c->rm_rows_b);
+        std::swap(c->q8_rows, c->q8_rows_b);
         if (rc) return rc;
         HIP_TRY(c, e);
     }
@@ -1679,6 +1712,82 @@ int polar_fer_batch(polar_ctx *c, unsigned long long seed, unsigned long long fi
     if (rc) return rc;
     *block_errors += h[0];
     *bit_errors += h[1];
+    return POLAR_OK;
+}
+
+// ---- fixed-point min-sum decoding (include/polar_hip.h, POLAR_Q8) ---------------------------------------------------------
+static bool q8_quant_ok(double scale, int qc, int qi) { return scale > 0 && std::isfinite(scale) && qc >= 2 && qc <= qi && qi <= 8; }
+
+int polar_q8_set_quant(polar_ctx *c, double scale, int qc, int qi)
+{
+    if (!c || c->cfg.dtype != POLAR_Q8 || !q8_quant_ok(scale, qc, qi)) return POLAR_EINVAL;
+    c->q8_scale = scale;
+    c->q8_qc = qc;
+    c->q8_qi = qi;
+    return POLAR_OK;
+}
+
+int polar_q8_get_quant(const polar_ctx *c, double *scale, int *qc, int *qi)
+{
+    if (!c || c->cfg.dtype != POLAR_Q8) return POLAR_EINVAL;
+    if (scale) *scale = c->q8_scale;
+    if (qc) *qc = c->q8_qc;
+    if (qi) *qi = c->q8_qi;
+    return POLAR_OK;
+}
+
+int polar_q8_quantize_host(const double *in, size_t n, double sigma, double scale, int qc, int8_t *out)
+{
+    if ((n && (!in || !out)) || !q8_quant_ok(scale, qc, 8) || sigma != sigma) return POLAR_EINVAL;
+    polar_tu::q8_quantize_host(in, n, sigma, scale, (1 << (qc - 1)) - 1, out);
+    return POLAR_OK;
+}
+
+int polar_q8_quantize_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, int8_t *d_out)
+{
+    if (!c || c->cfg.dtype != POLAR_Q8 || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    const size_t esz = in_is_f32 ? 4 : 8;
+    if (reinterpret_cast<uintptr_t>(d_in) % esz) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    const size_t total = B * (size_t)c->cfg.N, CH = (size_t)1 << 30;   // elements per launch
+    for (size_t off = 0; off < total; off += CH) {
+        const int rc = polar_tu::q8_quantize(c, (const char *)d_in + off * esz, in_is_f32 != 0, sigma, std::min(CH, total - off), d_out + off);
+        if (rc) return rc;
+    }
+    return POLAR_OK;
+}
+
+int polar_q8_decode_device(polar_ctx *c, const int8_t *d_q, size_t B, uint32_t *d_uhat_bits, int32_t *d_pm, uint32_t *d_flags)
+{
+    if (!c || c->cfg.dtype != POLAR_Q8 || !d_q || !d_uhat_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_q) % 4) return POLAR_EINVAL;   // the kernel loads the rows as dwords
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    return polar_tu::q8_decode(c, d_q, B, d_uhat_bits, d_pm, d_flags);
+}
+
+int polar_q8_decode_batch(polar_ctx *c, const int8_t *q, size_t B, int *u_hat, int32_t *pm, unsigned *flags)
+{
+    if (!c || c->cfg.dtype != POLAR_Q8 || !q || !u_hat || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    DeviceGuard guard(c->cfg.device);
+    const size_t N = (size_t)c->cfg.N, NW = (size_t)c->NW;
+    int rc;
+    if ((rc = ensure(c, c->q8_rows, B * N))) return rc;
+    if ((rc = ensure(c, c->bits, B * NW * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->q8_pm, B * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, c->flags, B * sizeof(uint32_t)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->q8_rows.p, q, B * N, hipMemcpyHostToDevice, c->stream));
+    if ((rc = polar_tu::q8_decode(c, (const int8_t *)c->q8_rows.p, B, (uint32_t *)c->bits.p, (int32_t *)c->q8_pm.p, (uint32_t *)c->flags.p))) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    std::vector<uint32_t> w(B * NW);
+    HIP_TRY(c, hipMemcpyAsync(w.data(), c->bits.p, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (pm) HIP_TRY(c, hipMemcpyAsync(pm, c->q8_pm.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (flags) HIP_TRY(c, hipMemcpyAsync(flags, c->flags.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t f = 0; f < B; ++f) unpack_words(w.data() + f * NW, (int)NW, u_hat + f * N);
     return POLAR_OK;
 }
 
@@ -1788,7 +1897,7 @@ int polar_set_systematic(polar_ctx *c, int on)
     if (!c || (on != 0 && on != 1)) return POLAR_EINVAL;
     if ((on != 0) == c->sys_polar) return POLAR_OK;
     if (on) {
-        if (c->is_dyn || c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
+        if (c->is_dyn || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8) return POLAR_EINVAL;
         if (polar_systematic_check(c->cfg.N, c->info_order.data(), c->A) != 1) return POLAR_EINVAL;
     }
     DeviceGuard guard(c->cfg.device);
@@ -2059,6 +2168,7 @@ int polar_group_create(const polar_cfg *cfg, int ngpus, polar_group **out)
 {
     if (!cfg || !out || ngpus < 1 || ngpus > 64) return POLAR_EINVAL;
     *out = nullptr;
+    if (cfg->dtype == POLAR_Q8) return POLAR_EINVAL;   // the groups build float contexts only
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ngpus > ndev) return POLAR_EDEVICE;
     RcclApi &R = rccl();

@@ -78,6 +78,11 @@ struct polar_ctx {
     uint32_t *d_enc_rtab = nullptr;
     std::vector<uint32_t> h_crc_tab_sys;
     Buf enc_u, enc_x, enc_io;
+    // fixed-point min-sum (dtype POLAR_Q8): the quantiser (polar_q8_set_quant), the quantised rows of the float entry points
+    // (one buffer per stream of polar_fer_batch) and the int32 metrics behind their double d_pm
+    double q8_scale = 2.0;
+    int q8_qc = 8, q8_qi = 8;
+    Buf q8_rows, q8_rows_b, q8_pm;
     Buf in2[2], bits2[2];                // chunked host pipeline: ping-pong device buffers
     uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
     size_t h_bits_cap = 0;
@@ -240,6 +245,11 @@ int enc_dyn_fill(polar_ctx *c, uint32_t *d_z, size_t B);
 int enc_rm_select(polar_ctx *c, const uint32_t *d_x, size_t B, uint32_t *d_e);
 int enc_count_sys(polar_ctx *c, const uint32_t *d_uhat, const uint32_t *d_u, size_t B, unsigned long long *d_counters,
                   uint32_t *d_frame_err);
+// k_q8.hip: fixed-point min-sum SC / SCL / CA-SCL (scl_q8.h) with the quantiser of c (q8_scale, q8_qc, q8_qi)
+int q8_decode(polar_ctx *c, const int8_t *d_q, size_t B, uint32_t *d_bits, int32_t *d_pm, uint32_t *d_flags);
+int q8_quantize(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t count, int8_t *d_out);   // count < 2^32 * 256
+int q8_pm_f64(polar_ctx *c, const int32_t *d_pm, size_t B, double *d_out);
+void q8_quantize_host(const double *in, size_t n, double sigma, double scale, int Cc, int8_t *out);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

@@ -210,7 +210,8 @@ static int construct_order(int N, int dtype, long long frames, double sigma, uin
 static void usage(void)
 {
     fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf|scan --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
-                    "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
+                    "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32|q8 [--quant scale,qc,qi]] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
+                    "                 [--quant s,qc,qi]   (--dtype q8, fixed-point min-sum sc|scl|cascl: LLR scale, channel and internal bits; default 2,8,8)\n"
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
                     "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n"
@@ -231,6 +232,8 @@ int main(int argc, char **argv)
     int scan_iters = -1;          /* --iters: polar_scan_set_iters (-1: the library's default) */
     int rm_E = 0, rm_ibil = 0;    /* --E / --ibil: polar_create_rm (0: no rate matching) */
     int sys_polar = 0;            /* --sys-polar: polar_set_systematic */
+    double q8_scale = 0;          /* --quant: polar_q8_set_quant (0: the library's default) */
+    int q8_qc = 8, q8_qi = 8;
     long min_run = 0;   /* --min-run m: `errBlock < BLE || run < m`, the rule of the published L = 32 logs (m = 2000) */
     uint64_t seed = 1024;
     double lo = 1.0, hi = 3.0, step = 0.5;
@@ -299,7 +302,11 @@ int main(int argc, char **argv)
             if (end == v || *end || scan_iters < 0) usage();
             i++;
         }
-        else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : POLAR_F64; i++; }
+        else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : !strcmp(v, "q8") ? POLAR_Q8 : POLAR_F64; i++; }
+        else if (!strcmp(a, "--quant") && v) {   /* polar_q8_set_quant */
+            if (sscanf(v, "%lf,%d,%d", &q8_scale, &q8_qc, &q8_qi) != 3 || !(q8_scale > 0)) usage();
+            i++;
+        }
         else if (!strcmp(a, "--snr-list") && v) {
             const char *q = v;
             while (*q && npts < 64) {
@@ -380,7 +387,7 @@ int main(int argc, char **argv)
         if (!have_design) { fprintf(stderr, "--construct needs --design-snr\n"); return 1; }
         if (qfile) { fprintf(stderr, "--construct and --q exclude each other\n"); return 1; }
         qorder = (int *)malloc(sizeof(int) * (size_t)N);
-        if (!qorder || construct_order(N, dtype, construct, pow(10, design_db / ((double)-20)), seed, qorder)) return 1;
+        if (!qorder || construct_order(N, dtype == POLAR_Q8 ? POLAR_F32 : dtype /* the genie kernels are float */, construct, pow(10, design_db / ((double)-20)), seed, qorder)) return 1;
     } else if (have_design) { fprintf(stderr, "--design-snr needs --construct\n"); return 1; }
     if (qout) {
         if (!qorder) { fprintf(stderr, "--q-out needs --construct or --q\n"); return 1; }
@@ -408,6 +415,11 @@ int main(int argc, char **argv)
         polar_destroy(ctx);
         ctx = NULL;
         if ((rc = polar_create_rm(&cfg, rm_E, rm_ibil, &ctx)) != 0) { fprintf(stderr, "polar_create_rm: %s\n", polar_strerror(rc)); return 1; }
+    }
+    if (q8_scale > 0) {
+        /* a polar_group builds float contexts only */
+        if (dtype != POLAR_Q8) { fprintf(stderr, "--quant: only with --dtype q8\n"); return 1; }
+        if ((rc = polar_q8_set_quant(ctx, q8_scale, q8_qc, q8_qi)) != 0) { fprintf(stderr, "--quant: %s\n", polar_strerror(rc)); return 1; }
     }
     if (sys_polar) {
         /* the host Ranq1 frame loop encodes u F; a polar_group builds its contexts from cfg and stays non-systematic */
