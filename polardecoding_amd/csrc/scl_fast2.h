@@ -55,18 +55,22 @@ __device__ __forceinline__ double quadp(double x) { return quad_lanes<QP>(x); }
 template <int QP>
 __device__ __forceinline__ float quadp(float x) { return quad_lanes<QP>(x); }
 
-template <typename R, typename IN, bool CRC_ON>
-struct Fast2Dec {
+// The channel vector is LLRs (FROM_Y = false: the device-resident callers, the benchmark) or channel observations y that
+// every read converts with sigma (FROM_Y = true).  Only the second form has the member sigma and the f64 divisions of
+// llr_from_y at its channel reads (the root step, from_top's two prefetches): the first form's chv() is the bare load.
+template <bool FROM_Y>
+struct Fast2Sigma { double sigma; };
+template <>
+struct Fast2Sigma<false> {};
+
+template <typename R, typename IN, bool CRC_ON, bool FROM_Y>
+struct Fast2Dec : Fast2Sigma<FROM_Y> {
     using C = Fast2Cfg<R>;
     static constexpr int N = C::N, NW = C::NW, TOP = C::TOP, HI = C::HI, L = 8, NFA = C::NFA;
 
     R A[C::NA];      // levels 2..6
     R a1;            // level 1 (pos 0, 1)
     R bp_s, bp_d, bp_ts, bp_td;   // by-products of the last level-0 check node: x + y, x - y, T(|x + y|), T(|x - y|)
-    // Written, never read: they served a bound-based trivial-prune test that lost its A/B run.  Dropping the members or
-    // their stores changes k_scl_fast2's register allocation and schedule (same operations).
-    R mb65;
-    bool mb_ok;
     R PM;            // valid at pos 0
     uint32_t ptr, crc, bl0, fl;
     int logact;
@@ -124,7 +128,6 @@ struct Fast2Dec {
         __device__ __forceinline__ Ref operator[](int k) const { return Ref{d, off + (unsigned)k}; }
     };
     static __device__ __forceinline__ R ld_sc(SPtr q) { return ld_buf(q.d->rs_scr, q.off, R(0), 1); }
-    double sigma;
 
     __device__ __forceinline__ int pa(int t) const { return (ptr >> (3 * (t - 4))) & 7; }
     __device__ __forceinline__ void set_pa(int t, int v) { ptr = (ptr & ~(7u << (3 * (t - 4)))) | ((uint32_t)v << (3 * (t - 4))); }
@@ -140,7 +143,7 @@ struct Fast2Dec {
     __device__ __forceinline__ R chv(int e) const
     {
         double v = (double)ld_buf(rs_in, csrc + (unsigned)e, IN(0), 0);
-        if (sigma > 0) v = llr_from_y(v, sigma);
+        if constexpr (FROM_Y) v = llr_from_y(v, this->sigma);
         return (R)v;
     }
     // The row addresses are recomputed where they are used (a few instructions, 16 times per frame) instead of
@@ -152,10 +155,6 @@ struct Fast2Dec {
     }
     __device__ __forceinline__ SPtr l8(int slot) const { return SPtr{this, fresh(cscr + (unsigned)(C::sc_l8 + slot * 256))}; }
     __device__ __forceinline__ SPtr l7(int slot) const { return SPtr{this, fresh(cscr + (unsigned)(C::sc_l7 + slot * 128))}; }
-    // A slot's level-6 scratch row.  Nothing is stored there (level 6 is in registers), but from_top, from_l8 and from_l7
-    // still form it: fresh()'s empty asm pins its offset to a VGPR, and dropping it changes k_scl_fast2's register
-    // allocation and schedule (same operations).
-    __device__ __forceinline__ SPtr l6s(int slot) const { return SPtr{this, fresh(cscr + (unsigned)(C::sc_l6 + slot * 64))}; }
     __device__ __forceinline__ SPtr tls() const { return SPtr{this, fresh(cscr + (unsigned)C::sc_tl)}; }
 
     // ---- register levels: f on own data ----
@@ -224,8 +223,6 @@ struct Fast2Dec {
         const uint32_t *bt = blw + pb(TOP) * NW + 16;  // beta_9: words 16..31
         const uint32_t *bh = blw + pb(HI) * NW + 8;    // beta_8: words 8..15
         const SPtr o8 = l8(p), o7 = l7(p);
-        const SPtr o6 = l6s(p);
-        (void)o6;
         const int w32 = (int)fresh((unsigned)(p * 4 + pos));   // lane index inside the codeword (recomputed here: the staged
                                                                // elements' offsets are not worth a register each across the frame loop)
         const int nld = right ? 8 : 4;                 // staged elements per lane and chunk
@@ -284,8 +281,6 @@ struct Fast2Dec {
         const SPtr s8 = l8(pa(8));
         const uint32_t *b7 = blw + pb(7) * NW + 4;  // beta_7: words 4..7
         const SPtr o7 = l7(p);
-        const SPtr o6 = l6s(p);
-        (void)o6;
         constexpr int CP = sizeof(R) == 8 ? 2 : 4;   // passes per chunk (4 loads each); f64: 8 in flight is the measured optimum
         for (int q = 0; q < 16 / CP; ++q) {
             R *in = A;       // levels 2..5: dead here, recomputed by the f chain below
@@ -317,8 +312,6 @@ struct Fast2Dec {
         const SPtr s7 = l7(pa(7)) + pos;
         const uint32_t *b6 = blw + pb(6) * NW + 2;  // beta_6: words 2, 3
         const uint32_t w0 = b6[0] >> pos, w1 = b6[1] >> pos;
-        const SPtr o6 = l6s(p);
-        (void)o6;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const R x = ld_sc(s7 + 4 * r), y = ld_sc(s7 + 4 * r + 64);
@@ -503,10 +496,8 @@ struct Fast2Dec {
         uint32_t bit = 0;
         if (frozen) {
             PM += tt + negmax(lam);  // PHI(.,0)
-            mb_ok = false;
         } else {
             if (logact < 3) {
-                mb_ok = false;
                 const R ph0 = tt + negmax(lam), ph1 = tt + posmax(lam);  // PHI(.,0), PHI(.,1)
                 bit = (p >> logact) & 1;
                 PM += bit ? ph1 : ph0;
@@ -656,7 +647,6 @@ struct Fast2Dec {
             lg = (pos & 1) ? gg : fg;
         }
         const R pf = lut.tabv(lf) + negmax(lf), pg = lut.tabv(lg) + negmax(lg);  // PHI(lambda_k, 0)
-        mb_ok = false;
         PM += pf;
         PM += quadp<0x55>(pf);  // lane 1 of the quad
         PM += quadp<0xAA>(pf);  // lane 2
@@ -741,10 +731,10 @@ struct Fast2Dec {
     }
 };
 
-template <typename R, typename IN, bool CRC_ON>
-__global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_fast2(SclParams P)
+template <typename R, typename IN, bool CRC_ON, bool FROM_Y>
+__device__ __forceinline__ void scl_fast2_body(const SclParams &P)
 {
-    using D = Fast2Dec<R, IN, CRC_ON>;
+    using D = Fast2Dec<R, IN, CRC_ON, FROM_Y>;
     using C = Fast2Cfg<R>;
     constexpr int N = C::N, NW = C::NW, L = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -784,7 +774,7 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
     s.cand = reinterpret_cast<R *>(base + C::off_cd) + s.c * 16;
     s.keys = reinterpret_cast<uint32_t *>(base + C::off_ky) + s.c * 16;
     s.stg = reinterpret_cast<R *>(base + C::off_sg) + s.c * 256;
-    s.sigma = P.sigma;
+    if constexpr (FROM_Y) s.sigma = P.sigma;
     {   // rank network: lane (row, i): rows 0,1 -> codeword 0, rows 2,3 -> codeword 1; candidate i is
         // (slot i & 7, branch i >> 3) stored at keys[cw][2*slot + branch]
         const int i = s.lane & 15, row = s.lane >> 4, cwr = row >> 1, h = row & 1;
@@ -832,8 +822,6 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
         for (int r = 0; r < C::NA; ++r) s.A[r] = R(0);
         s.fl = 0;
         s.logact = 0;
-        s.mb65 = R(0);
-        s.mb_ok = false;
         uint32_t fword = 0;
 
         int o_first = 0;
@@ -902,6 +890,19 @@ __global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
         lds_fence();
         pair = next_job_wave(P.queue, pair, waves_total, (P.B + 1) >> 1);
     }
+}
+
+// k_scl_fast2: the input rows are LLRs (P.sigma is not read).  k_scl_fast2_y: they are y, P.sigma > 0.  The host picks by
+// P.sigma (k_fast2.hip).
+template <typename R, typename IN, bool CRC_ON>
+__global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_fast2(SclParams P)
+{
+    scl_fast2_body<R, IN, CRC_ON, false>(P);
+}
+template <typename R, typename IN, bool CRC_ON>
+__global__ __launch_bounds__(256, (Fast2Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_fast2_y(SclParams P)
+{
+    scl_fast2_body<R, IN, CRC_ON, true>(P);
 }
 
 }  // namespace polar
