@@ -16,10 +16,9 @@ int polar_testing_math(int op, int is_f32, const void *a, const void *b, void *o
     if (n == 0) return POLAR_OK;
     DeviceGuard guard(device);
     const size_t es = is_f32 ? 4 : 8;
-    void *da = nullptr, *db = nullptr, *d_out = nullptr;
+    DevMem<char> da, db, d_out;
     int rc = POLAR_OK;
-    if (hipMalloc(&da, n * es) != hipSuccess || hipMalloc(&db, n * es) != hipSuccess || hipMalloc(&d_out, n * es) != hipSuccess)
-        rc = POLAR_ENOMEM;
+    if (da.alloc(n * es) != hipSuccess || db.alloc(n * es) != hipSuccess || d_out.alloc(n * es) != hipSuccess) rc = POLAR_ENOMEM;
     if (!rc && (hipMemcpy(da, a, n * es, hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(db, b, n * es, hipMemcpyHostToDevice) != hipSuccess))
         rc = POLAR_EDEVICE;
@@ -27,17 +26,14 @@ int polar_testing_math(int op, int is_f32, const void *a, const void *b, void *o
         const int grid = (int)std::min<size_t>((n + 255) / 256, 1024);
         if (is_f32)
             hipLaunchKernelGGL(polar::k_probe_math<float>, dim3(grid), dim3(256), polar::Lut<float>::bytes + 16 + 64 * sizeof(float) + polar::Stair<float>::bytes, 0, op,
-                               (const float *)da, (const float *)db, (float *)d_out, n);
+                               (const float *)da.get(), (const float *)db.get(), (float *)d_out.get(), n);
         else
             hipLaunchKernelGGL(polar::k_probe_math<double>, dim3(grid), dim3(256), polar::Lut<double>::bytes + 16 + 64 * sizeof(double) + polar::Stair<double>::bytes, 0, op,
-                               (const double *)da, (const double *)db, (double *)d_out, n);
+                               (const double *)da.get(), (const double *)db.get(), (double *)d_out.get(), n);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipMemcpy(out, d_out, n * es, hipMemcpyDeviceToHost) != hipSuccess)
             rc = POLAR_EDEVICE;
     }
-    if (da) (void)hipFree(da);
-    if (db) (void)hipFree(db);
-    if (d_out) (void)hipFree(d_out);
     return rc;
 }
 

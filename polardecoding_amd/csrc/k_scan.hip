@@ -8,25 +8,6 @@ namespace {
 // byte budget for the ctx scratch as well as by the occupancy: at most 4 GiB.
 constexpr size_t SCAN_SCRATCH_BUDGET = (size_t)4 << 30;
 
-// like ensure(), but a failed allocation is POLAR_ENOMEM and leaves the ctx usable
-int ensure_scratch(polar_ctx *c, Buf &b, size_t bytes)
-{
-    if (b.cap >= bytes) return POLAR_OK;
-    if (b.p) HIP_TRY(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    const hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        c->last_error = "SCAN scratch: out of device memory";
-        return POLAR_ENOMEM;
-    }
-    if (e != hipSuccess) return fail(c, e, "hipMalloc(SCAN scratch)");
-    b.cap = bytes;
-    return POLAR_OK;
-}
-
 template <typename R, typename IN>
 int launch_scan_lanes(polar_ctx *c, const polar::ScanParams &P)
 {
@@ -40,7 +21,7 @@ int launch_scan_lanes(polar_ctx *c, const polar::ScanParams &P)
     s.scratch_per_block = wg_bytes;
     s.grid_cap = std::max<long long>(1, (long long)(SCAN_SCRATCH_BUDGET / wg_bytes));
     s.set_lds_attr = false;   // the LDS holds the look-up table alone: far below the limit a kernel has anyway
-    s.alloc = ensure_scratch;
+    s.nomem_what = "SCAN scratch";   // a budget-sized request: out of memory leaves the ctx usable
     LaunchPlan pl;
     int rc = plan_launch(c, reinterpret_cast<const void *>(kern), s, &pl);
     if (rc) return rc;

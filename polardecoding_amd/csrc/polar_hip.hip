@@ -73,6 +73,13 @@ std::vector<uint32_t> make_crc_table(int N, int r, const std::vector<int> &taps,
     return tab;
 }
 
+// Rows per pass where a batch goes through ctx scratch in chunks: at most 256 MiB of rows, at least `floor` of them, never
+// more than the batch.
+size_t chunk_rows(size_t B, size_t row_bytes, size_t floor = 64)
+{
+    return std::min(B, std::max(floor, ((size_t)256 << 20) / row_bytes));
+}
+
 // contexts whose code carries a CRC: r, crc_tab, the generator's CRC multiply, the systematic K-bit error metric
 bool has_crc(int algo) { return algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF; }
 
@@ -182,6 +189,15 @@ int dyn_emit(const std::vector<int> &P, const std::vector<std::vector<int>> &row
     return POLAR_OK;
 }
 
+// I[0..A) on the device, built on first use: the generators and the encoder side read it
+int info_order_table(polar_ctx *c)
+{
+    if (c->d_info_order) return POLAR_OK;
+    hipError_t e = hipSuccess;
+    if (c->d_info_order.upload(c->info_order.data(), (size_t)c->A, &e)) return fail(c, e, "info_order table");
+    return POLAR_OK;
+}
+
 static bool sc_lanes_ok(const polar_ctx *c, size_t B)
 {
     return c->cfg.algo == POLAR_ALGO_SC && !c->force_generic && c->cfg.N <= 2048 && B >= 64;
@@ -220,14 +236,14 @@ Family kernel_family(const polar_ctx *c, int in_is_f32, size_t B)
 
 // A Q8 ctx on float or double rows (include/polar_hip.h, fixed-point min-sum, rule 7): rule 1 into ctx scratch in chunks of
 // at most 256 MiB of quantised rows, then k_scl_q8; the int32 metric reaches a double d_pm through q8_pm.  c->q8_rows belongs
-// to c->stream (polar_fer_batch swaps it with q8_rows_b).
+// to c->stream (it is part of the lane, polar_host.h).
 int q8_decode_rows(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
                    uint32_t *d_flags)
 {
     const size_t esz = in_is_f32 ? 4 : 8;
     if (reinterpret_cast<uintptr_t>(d_in) % esz) return POLAR_EINVAL;
     const size_t N = (size_t)c->cfg.N;
-    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / N));
+    const size_t CH = chunk_rows(B, N);
     int rc;
     if ((rc = ensure(c, c->q8_rows, CH * N))) return rc;
     if (d_pm && (rc = ensure(c, c->q8_pm, CH * sizeof(int32_t)))) return rc;
@@ -298,7 +314,7 @@ void sync_stage_ctx(polar_ctx *c)
 {
     for (polar_ctx *s : c->stage_ctx) {
         if (!s) continue;
-        s->stream = c->stream;
+        s->stream.adopt(c->stream);
         s->force_generic = c->force_generic;
         s->force_spill = c->force_spill;
         s->use_fast2 = c->use_fast2;
@@ -321,7 +337,7 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
     const int m = (int)st.size(), N = c->cfg.N, NW = c->NW;
     const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
     // later stages run in chunks of at most 256 MiB of gathered input
-    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
+    const size_t CH = chunk_rows(B, row);
     int rc;
     // every buffer of the call, before its first launch
     if (!d_flags) {
@@ -414,7 +430,7 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     if ((rc = polar_tu::scf_lanes(c, R, polar::SCF_RECORD, r32, in32))) return rc;
     // pass B: frames [off, off + nc) of the list, T pairs each
     const size_t pair_bytes = (size_t)NW * sizeof(uint32_t);
-    const size_t CH = std::min(n, std::max<size_t>(1, ((size_t)256 << 20) / (pair_bytes * (size_t)T)));
+    const size_t CH = chunk_rows(n, pair_bytes * (size_t)T, 1);
     if ((rc = ensure(c, c->scf_bits, CH * (size_t)T * pair_bytes))) return rc;
     if ((rc = ensure(c, c->scf_pass, CH * (size_t)T * sizeof(uint32_t)))) return rc;
     for (size_t off = 0; off < n; off += CH) {
@@ -467,7 +483,7 @@ int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double si
 
 // every decode of the C ABI.  On a rate-matched ctx (polar_create_rm) the rows hold E values: k_rm_recover turns them into
 // N-wide rows of the input type in ctx scratch (chunks of at most 256 MiB), which the ctx's own decoder reads with sigma = 0
-// (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (polar_fer_batch swaps it with rm_rows_b).
+// (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (it is part of the lane, polar_host.h).
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr,
                        void *d_llr_u = nullptr, void *d_ext_x = nullptr)
@@ -480,7 +496,7 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
     if (!d_in || (!d_bits && !scan) || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     const size_t row = (size_t)c->cfg.N * esz;
-    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
+    const size_t CH = chunk_rows(B, row);
     int rc;
     if ((rc = ensure(c, c->rm_rows, CH * row))) return rc;
     for (size_t off = 0; off < B; off += CH) {
@@ -586,7 +602,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     if (frozen_mask) {
         if (has_crc(c->cfg.algo) || c->rm_mode != POLAR_RM_NONE || c->is_dyn || c->cfg.dtype == POLAR_Q8) return POLAR_EINVAL;
         std::vector<uint32_t> w = pack_mask(frozen_mask, N, false);
-        if (!c->d_frozen_override) HIP_TRY(c, hipMalloc(&c->d_frozen_override, NW * sizeof(uint32_t)));
+        if (!c->d_frozen_override) HIP_TRY(c, c->d_frozen_override.alloc((size_t)NW));
         HIP_TRY(c, hipMemcpyAsync(c->d_frozen_override, w.data(), NW * sizeof(uint32_t), hipMemcpyHostToDevice,
                                   c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // w goes out of scope
@@ -631,32 +647,18 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         if ((rc = ensure(c, c->in2[i], chf * W * sizeof(double)))) return rc;
         if ((rc = ensure(c, c->bits2[i], chf * NW * sizeof(uint32_t)))) return rc;
     }
-    if (c->h_bits_cap < chf * NW * sizeof(uint32_t)) {
-        c->h_bits_cap = 0;   // a failure below leaves "nothing allocated", not the old size over freed pointers
-        for (int i = 0; i < 2; ++i) {
-            if (c->h_bits[i]) HIP_TRY(c, hipHostFree(c->h_bits[i]));
-            c->h_bits[i] = nullptr;
-            HIP_TRY(c, hipHostMalloc((void **)&c->h_bits[i], chf * NW * sizeof(uint32_t), hipHostMallocDefault));
-        }
-        c->h_bits_cap = chf * NW * sizeof(uint32_t);
+    const bool staged = nch >= 3;
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(c, c->h_bits[i].ensure(chf * NW * sizeof(uint32_t)));
+        if (staged) HIP_TRY(c, c->h_in[i].ensure(chf * W * sizeof(double)));
     }
     if (!c->copy_stream) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        HIP_TRY(c, c->copy_stream.create(hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
-            HIP_TRY(c, hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming));
-            HIP_TRY(c, hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
-            HIP_TRY(c, hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming));
+            HIP_TRY(c, c->ev_in[i].create(hipEventDisableTiming));
+            HIP_TRY(c, c->ev_free[i].create(hipEventDisableTiming));
+            HIP_TRY(c, c->ev_out[i].create(hipEventDisableTiming));
         }
-    }
-    const bool staged = nch >= 3;
-    if (staged && c->h_in_cap < chf * W * sizeof(double)) {
-        c->h_in_cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (c->h_in[i]) HIP_TRY(c, hipHostFree(c->h_in[i]));
-            c->h_in[i] = nullptr;
-            HIP_TRY(c, hipHostMalloc((void **)&c->h_in[i], chf * W * sizeof(double), hipHostMallocDefault));
-        }
-        c->h_in_cap = chf * W * sizeof(double);
     }
     auto stage_chunk = [&](size_t k) {    // caller's rows of chunk k -> pinned h_in[k & 1], four threads
         const size_t f0 = off[k], nf = off[k + 1] - off[k];
@@ -831,9 +833,8 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
         polar_destroy(c);
         return rc;
     };
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return cleanup(POLAR_EDEVICE);
-    c->own_stream = true;
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return cleanup(POLAR_EDEVICE);
+    if (c->stream.create(hipStreamNonBlocking) != hipSuccess) return cleanup(POLAR_EDEVICE);
+    if (c->ev0.create(hipEventDefault) != hipSuccess || c->ev1.create(hipEventDefault) != hipSuccess) return cleanup(POLAR_EDEVICE);
     std::vector<uint32_t> fw = pack_mask(c->frozen.data(), N, false);
     std::vector<uint32_t> iw = pack_mask(c->frozen.data(), N, true);
     c->cfg.crc_systematic = (cfg->crc_systematic && r > 0) ? 1 : 0;
@@ -853,20 +854,14 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
             rem <<= 1;
             if (rem & top) rem = (rem ^ top) ^ glow;
         }
-        if (hipMalloc(&c->d_gc_rows, rows.size() * 4) != hipSuccess) return cleanup(POLAR_ENOMEM);
-        if (hipMemcpy(c->d_gc_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return cleanup(POLAR_EDEVICE);
+        if (int rc = c->d_gc_rows.upload(rows.data(), rows.size())) return cleanup(rc);
     }
-    if (hipMalloc(&c->d_frozen, c->NW * 4) != hipSuccess || hipMalloc(&c->d_info, c->NW * 4) != hipSuccess)
-        return cleanup(POLAR_ENOMEM);
-    if (hipMemcpy(c->d_frozen, fw.data(), c->NW * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_info, iw.data(), c->NW * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(POLAR_EDEVICE);
-    if (r > 0) {
-        if (hipMalloc(&c->d_crc_tab, N * 4) != hipSuccess) return cleanup(POLAR_ENOMEM);
-        if (hipMemcpy(c->d_crc_tab, c->h_crc_tab.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return cleanup(POLAR_EDEVICE);
-    }
+    // both allocations before either copy: out of memory is reported before a failed copy
+    if (c->d_frozen.alloc((size_t)c->NW) != hipSuccess || c->d_info.alloc((size_t)c->NW) != hipSuccess) return cleanup(POLAR_ENOMEM);
+    if (int rc = c->d_frozen.upload(fw.data(), (size_t)c->NW)) return cleanup(rc);
+    if (int rc = c->d_info.upload(iw.data(), (size_t)c->NW)) return cleanup(rc);
+    if (r > 0)
+        if (int rc = c->d_crc_tab.upload(c->h_crc_tab.data(), (size_t)N)) return cleanup(rc);
     refresh_kernel_name(c);
     *out = c;
     return POLAR_OK;
@@ -876,64 +871,22 @@ void polar_destroy(polar_ctx *c)
 {
     if (!c) return;
     DeviceGuard guard(c->cfg.device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
-    for (Buf *b : {&c->in, &c->bits, &c->pm, &c->flags, &c->bp_iters, &c->scratch, &c->gen_llr, &c->gen_u, &c->gen_cnt, &c->in2[0],
-                   &c->in2[1], &c->bits2[0], &c->bits2[1], &c->scratch_b})
-    {
-        if (b->p) (void)hipFree(b->p);
-        if (b->queue) (void)hipFree(b->queue);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (c->h_bits[i]) (void)hipHostFree(c->h_bits[i]);
-        if (c->h_in[i]) (void)hipHostFree(c->h_in[i]);
-        if (c->ev_in[i]) (void)hipEventDestroy(c->ev_in[i]);
-        if (c->ev_free[i]) (void)hipEventDestroy(c->ev_free[i]);
-        if (c->ev_out[i]) (void)hipEventDestroy(c->ev_out[i]);
-    }
-    for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they share c->stream (synchronized above) and own none
-    for (Buf *b : {&c->ad_flags, &c->ad_idx[0], &c->ad_idx[1], &c->ad_blk, &c->ad_cnt, &c->ad_in, &c->ad_bits,
-                   &c->ad_pm, &c->ad_sflags, &c->scf_flips, &c->scf_pass, &c->scf_bits, &c->scan_llr, &c->scan_ext, &c->rm_rows, &c->rm_rows_b, &c->genie_rows, &c->q8_rows, &c->q8_rows_b, &c->q8_pm})
-        if (b->p) (void)hipFree(b->p);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->stream_b) (void)hipStreamDestroy(c->stream_b);
-    if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-    if (c->d_frozen) (void)hipFree(c->d_frozen);
-    if (c->d_info) (void)hipFree(c->d_info);
-    if (c->d_crc_tab) (void)hipFree(c->d_crc_tab);
-    if (c->d_frozen_override) (void)hipFree(c->d_frozen_override);
-    if (c->d_info_order) (void)hipFree(c->d_info_order);
-    if (c->d_gc_rows) (void)hipFree(c->d_gc_rows);
-    if (c->d_rm_ilv) (void)hipFree(c->d_rm_ilv);
-    if (c->d_rm_ilv_inv) (void)hipFree(c->d_rm_ilv_inv);
-    if (c->d_dyn_mask) (void)hipFree(c->d_dyn_mask);
-    if (c->d_dyn_row) (void)hipFree(c->d_dyn_row);
-    if (c->d_dyn_pos) (void)hipFree(c->d_dyn_pos);
-    if (c->d_enc_inv) (void)hipFree(c->d_enc_inv);
-    if (c->d_enc_rtab) (void)hipFree(c->d_enc_rtab);
-    for (Buf *b : {&c->enc_u, &c->enc_x, &c->enc_io})
-        if (b->p) (void)hipFree(b->p);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    for (hipStream_t st : {c->stream.get(), c->copy_stream.get(), c->lane_b.stream.get()})
+        if (st) (void)hipStreamSynchronize(st);
+    for (polar_ctx *s : c->stage_ctx) polar_destroy(s);   // they borrow c->stream (synchronized above)
+    delete c;   // every member releases what it owns, on c's device
 }
 
 int polar_set_stream(polar_ctx *c, void *s)
 {
     if (!c) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
-    if (c->own_stream && c->stream) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipStreamDestroy(c->stream);
-    }
-    c->stream = (hipStream_t)s;
-    c->own_stream = false;
+    if (c->stream.is_owned()) (void)hipStreamSynchronize(c->stream);
+    c->stream.adopt((hipStream_t)s);   // destroys the stream polar_create made; the caller's is never destroyed here
     return POLAR_OK;
 }
 
-void *polar_get_stream(polar_ctx *c) { return c ? (void *)c->stream : nullptr; }
+void *polar_get_stream(polar_ctx *c) { return c ? (void *)c->stream.get() : nullptr; }
 
 int polar_synchronize(polar_ctx *c)
 {
@@ -1011,15 +964,9 @@ int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out)
         std::vector<uint16_t> inv((size_t)E);
         for (int k = 0; k < E; ++k) inv[pos[(size_t)k]] = (uint16_t)k;
         DeviceGuard guard(cfg->device);
-        const size_t bytes = (size_t)E * sizeof(uint16_t);
-        if (hipMalloc(&c->d_rm_ilv, bytes) != hipSuccess || hipMalloc(&c->d_rm_ilv_inv, bytes) != hipSuccess) {
+        if ((rc = c->d_rm_ilv.upload(pos.data(), (size_t)E)) || (rc = c->d_rm_ilv_inv.upload(inv.data(), (size_t)E))) {
             polar_destroy(c);
-            return POLAR_ENOMEM;
-        }
-        if (hipMemcpy(c->d_rm_ilv, pos.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_rm_ilv_inv, inv.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            polar_destroy(c);
-            return POLAR_EDEVICE;
+            return rc;
         }
     }
     refresh_kernel_name(c);
@@ -1084,17 +1031,11 @@ int polar_create_dyn(const polar_cfg *cfg, const polar_dyn *dyn, polar_ctx **out
     c->is_dyn = true;
     c->dyn_pos.assign(dyn->pos, dyn->pos + D);
     DeviceGuard guard(cfg->device);
-    const size_t mb = mask.size() * sizeof(uint32_t), pb = (size_t)std::max(D, 1) * sizeof(int);
-    if (hipMalloc(&c->d_dyn_mask, mb) != hipSuccess || hipMalloc(&c->d_dyn_row, (size_t)N * sizeof(int)) != hipSuccess ||
-        hipMalloc(&c->d_dyn_pos, pb) != hipSuccess) {
+    if (c->d_dyn_pos.alloc((size_t)std::max(D, 1)) != hipSuccess) rc = POLAR_ENOMEM;   // never empty, D = 0 included
+    if (rc || (rc = c->d_dyn_mask.upload(mask.data(), mask.size())) || (rc = c->d_dyn_row.upload(row.data(), (size_t)N)) ||
+        (rc = c->d_dyn_pos.upload(dyn->pos, (size_t)D))) {
         polar_destroy(c);
-        return POLAR_ENOMEM;
-    }
-    if (hipMemcpy(c->d_dyn_mask, mask.data(), mb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_dyn_row, row.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        (D > 0 && hipMemcpy(c->d_dyn_pos, dyn->pos, (size_t)D * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)) {
-        polar_destroy(c);
-        return POLAR_EDEVICE;
+        return rc;
     }
     refresh_kernel_name(c);
     *out = c;
@@ -1310,7 +1251,7 @@ int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
                 g.crc_systematic = 0;
             }
             int rc = polar_create(&g, &subs[(size_t)i]);
-            if (!rc) rc = polar_set_stream(subs[(size_t)i], c->stream);
+            if (!rc) rc = polar_set_stream(subs[(size_t)i], c->stream.get());
             if (!rc && c->sys_polar && subs[(size_t)i]->d_crc_tab &&   // the stage reads the table of the mode that is on
                 hipMemcpy(subs[(size_t)i]->d_crc_tab, c->h_crc_tab_sys.data(), (size_t)c->cfg.N * 4, hipMemcpyHostToDevice) != hipSuccess)
                 rc = POLAR_EDEVICE;
@@ -1579,7 +1520,7 @@ int polar_construct_batch(polar_ctx *c, unsigned long long seed, unsigned long l
     DeviceGuard guard(c->cfg.device);
     const bool f32 = c->cfg.dtype == POLAR_F32;
     const size_t row = (size_t)c->cfg.N * (f32 ? 4 : 8);
-    const size_t CH = std::min<size_t>(B, std::max<size_t>(64, ((size_t)256 << 20) / row));
+    const size_t CH = chunk_rows(B, row);
     int rc;
     if ((rc = ensure(c, c->genie_rows, CH * row))) return rc;
     for (size_t off = 0; off < B; off += CH) {
@@ -1614,10 +1555,7 @@ int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long l
     if (B == 0) return POLAR_OK;
     const polar_cfg &g = c->cfg;
     if (g.N < 64) return POLAR_EINVAL;
-    if (!c->d_info_order) {
-        HIP_TRY(c, hipMalloc(&c->d_info_order, sizeof(int) * (size_t)c->A));
-        HIP_TRY(c, hipMemcpy(c->d_info_order, c->info_order.data(), sizeof(int) * (size_t)c->A, hipMemcpyHostToDevice));
-    }
+    if (int rc = info_order_table(c)) return rc;
     polar::GenParams P{};
     P.out = d_out; P.u_bits = d_u_bits; P.info_order = c->d_info_order;
     P.seed = seed; P.first_frame = first_frame;
@@ -1661,9 +1599,9 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
     // (not with an adaptive CA-SCL rule: its stage buffers belong to one stream and it syncs between stages)
     // (nor for SC-Flip, for the same reasons)
     const size_t half = (B >= 32768 && c->cascl_stages.empty() && c->cfg.algo != POLAR_ALGO_SCF) ? (B / 2 + 63) / 64 * 64 : B;
-    if (half < B && !c->stream_b) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming));
+    if (half < B && !c->lane_b.stream) {
+        HIP_TRY(c, c->lane_b.stream.create(hipStreamNonBlocking));
+        HIP_TRY(c, c->ev_b.create(hipEventDisableTiming));
     }
     const size_t esz = f32 ? 4 : 8;
     auto run_part = [&](size_t f0, size_t nf) -> int {
@@ -1676,19 +1614,15 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
                                          (unsigned long long *)c->gen_cnt.p, d_frame_err ? d_frame_err + f0 : nullptr);
     };
     if (half < B) {
-        // second half on stream_b, after the counters were cleared on the main stream
+        // second half on lane_b's stream, after the counters were cleared on the main stream
         HIP_TRY(c, hipEventRecord(c->ev_b, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream_b, c->ev_b, 0));
-        std::swap(c->stream, c->stream_b);
-        std::swap(c->scratch, c->scratch_b);
-        std::swap(c->rm_rows, c->rm_rows_b);
-        std::swap(c->q8_rows, c->q8_rows_b);
-        rc = run_part(half, B - half);
-        hipError_t e = hipEventRecord(c->ev_b, c->stream);
-        std::swap(c->stream, c->stream_b);
-        std::swap(c->scratch, c->scratch_b);
-        std::swap(c->rm_rows, c->rm_rows_b);
-        std::swap(c->q8_rows, c->q8_rows_b);
+        HIP_TRY(c, hipStreamWaitEvent(c->lane_b.stream, c->ev_b, 0));
+        hipError_t e;
+        {
+            OtherLane other(c);
+            rc = run_part(half, B - half);
+            e = hipEventRecord(c->ev_b, c->stream);   // behind the second half's work, before the first half is enqueued
+        }
         if (rc) return rc;
         HIP_TRY(c, e);
     }
@@ -1809,45 +1743,22 @@ void host_transform(uint32_t *w, int NW)
 int enc_tables(polar_ctx *c)
 {
     const int N = c->cfg.N, A = c->A;
-    if (!c->d_info_order) {
-        HIP_TRY(c, hipMalloc(&c->d_info_order, sizeof(int) * (size_t)A));
-        HIP_TRY(c, hipMemcpy(c->d_info_order, c->info_order.data(), sizeof(int) * (size_t)A, hipMemcpyHostToDevice));
-    }
+    if (int rc = info_order_table(c)) return rc;
     if (!c->d_enc_rtab) {
         std::vector<uint32_t> rtab((size_t)A);   // D^i mod g(D): make_crc_table keeps it at position I[i]
         for (int i = 0; i < A; ++i) rtab[(size_t)i] = c->h_crc_tab[(size_t)c->info_order[(size_t)i]];
-        uint32_t *d = nullptr;
-        if (hipMalloc(&d, rtab.size() * 4) != hipSuccess) return POLAR_ENOMEM;
-        if (hipMemcpy(d, rtab.data(), rtab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return POLAR_EDEVICE;
-        }
-        c->d_enc_rtab = d;
+        if (int rc = c->d_enc_rtab.upload(rtab.data(), rtab.size())) return rc;
     }
     if (!c->d_enc_inv) {
         std::vector<uint16_t> inv((size_t)N, (uint16_t)0xFFFFu);
         for (int i = 0; i < A; ++i) inv[(size_t)c->info_order[(size_t)i]] = (uint16_t)i;
-        uint16_t *d = nullptr;
-        if (hipMalloc(&d, inv.size() * 2) != hipSuccess) return POLAR_ENOMEM;
-        if (hipMemcpy(d, inv.data(), inv.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return POLAR_EDEVICE;
-        }
-        c->d_enc_inv = d;
+        if (int rc = c->d_enc_inv.upload(inv.data(), inv.size())) return rc;
     }
     return POLAR_OK;
 }
 
-// scratch rows; a failed allocation is POLAR_ENOMEM and leaves the ctx usable
-int enc_scratch(polar_ctx *c, Buf &b, size_t bytes)
-{
-    if (b.cap >= bytes) return POLAR_OK;
-    if (ensure(c, b, bytes)) {
-        (void)hipGetLastError();
-        return POLAR_ENOMEM;
-    }
-    return POLAR_OK;
-}
+// scratch rows of the encoder grow with ensure_nomem: out of memory is POLAR_ENOMEM and leaves the ctx usable
+const char *const kEncScratch = "encoder scratch";
 
 // the CRC table of systematic mode: tab_sys[j] = XOR over {i : I[i] a subset of j} of crc_tab[I[i]] at unfrozen j, 0 at frozen j
 // (x_c = XOR over {j : c subset of j} of u_j, so the syndrome of x[I] is a XOR over the set u bits as before)
@@ -1931,11 +1842,11 @@ int polar_encode_device(polar_ctx *c, const uint32_t *d_payload, size_t B, uint3
     const size_t row = (size_t)c->NW * sizeof(uint32_t);
     uint32_t *u = d_u_bits;
     if (!u) {
-        if ((rc = enc_scratch(c, c->enc_u, B * row))) return rc;
+        if ((rc = ensure_nomem(c, c->enc_u, B * row, kEncScratch))) return rc;
         u = (uint32_t *)c->enc_u.p;
     }
     const bool rm = c->rm_mode != POLAR_RM_NONE;
-    if (rm && d_x_bits && (rc = enc_scratch(c, c->enc_x, B * row))) return rc;
+    if (rm && d_x_bits && (rc = ensure_nomem(c, c->enc_x, B * row, kEncScratch))) return rc;
     if ((rc = polar_tu::enc_place(c, d_payload, B, u))) return rc;
     if (c->is_dyn && (rc = polar_tu::enc_dyn_fill(c, u, B))) return rc;
     // systematic: u = (z F) with the frozen positions cleared; x = u F then carries z on the information set
@@ -1965,9 +1876,9 @@ int polar_encode_batch(polar_ctx *c, const int *payload, size_t B, int *u, int *
     const int K = c->cfg.K, KW = (K + 31) / 32, N = c->cfg.N, NW = c->NW;
     const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : N, XW = (W + 31) / 32;
     int rc;
-    if ((rc = enc_scratch(c, c->in, B * KW * 4))) return rc;
-    if ((rc = enc_scratch(c, c->bits, B * NW * 4))) return rc;
-    if ((rc = enc_scratch(c, c->enc_io, B * XW * 4))) return rc;
+    if ((rc = ensure_nomem(c, c->in, B * KW * 4, kEncScratch))) return rc;
+    if ((rc = ensure_nomem(c, c->bits, B * NW * 4, kEncScratch))) return rc;
+    if ((rc = ensure_nomem(c, c->enc_io, B * XW * 4, kEncScratch))) return rc;
     std::vector<uint32_t> pw(B * (size_t)KW, 0u);
     for (size_t b = 0; b < B; ++b)
         for (int k = 0; k < K; ++k)
@@ -1994,9 +1905,9 @@ int polar_payload_batch(polar_ctx *c, const int *u_hat, size_t B, int *payload, 
     DeviceGuard guard(c->cfg.device);
     const int K = c->cfg.K, KW = (K + 31) / 32, N = c->cfg.N, NW = c->NW;
     int rc;
-    if ((rc = enc_scratch(c, c->in, B * KW * 4))) return rc;
-    if ((rc = enc_scratch(c, c->bits, B * NW * 4))) return rc;
-    if ((rc = enc_scratch(c, c->flags, B * 4))) return rc;
+    if ((rc = ensure_nomem(c, c->in, B * KW * 4, kEncScratch))) return rc;
+    if ((rc = ensure_nomem(c, c->bits, B * NW * 4, kEncScratch))) return rc;
+    if ((rc = ensure_nomem(c, c->flags, B * 4, kEncScratch))) return rc;
     std::vector<uint32_t> uw(B * (size_t)NW, 0u);
     for (size_t b = 0; b < B; ++b)
         for (int j = 0; j < N; ++j)
@@ -2061,6 +1972,7 @@ struct polar_group {
     std::vector<polar_ctx *> ctx;
     std::vector<void *> comms;   // ncclComm_t per GPU
     std::vector<Buf> ferr;       // per GPU: its shard's per-frame error counts (exact stop rule)
+    std::vector<Buf> recv;       // per GPU above 0: where the all-gather of the stop rule lands (GPU 0 receives into gathered)
     Buf gathered;                // GPU 0: the counts of all shards in frame order
     Buf cut_out;                 // GPU 0: k_stop_cut's three numbers
 };
@@ -2150,15 +2062,15 @@ void polar_group_destroy(polar_group *g)
     RcclApi &R = rccl();
     for (void *cm : g->comms)
         if (cm && R.ok) (void)R.CommDestroy(cm);
-    for (size_t i = 0; i < g->ferr.size(); ++i)
-        if (g->ferr[i].p) {
-            DeviceGuard guard((int)i);
-            (void)hipFree(g->ferr[i].p);
-        }
+    for (size_t i = 0; i < g->ferr.size(); ++i) {
+        DeviceGuard guard((int)i);
+        g->ferr[i].reset();
+        g->recv[i].reset();
+    }
     {
         DeviceGuard guard(0);
-        if (g->gathered.p) (void)hipFree(g->gathered.p);
-        if (g->cut_out.p) (void)hipFree(g->cut_out.p);
+        g->gathered.reset();
+        g->cut_out.reset();
     }
     for (polar_ctx *c : g->ctx) polar_destroy(c);
     delete g;
@@ -2177,7 +2089,8 @@ int polar_group_create(const polar_cfg *cfg, int ngpus, polar_group **out)
     if (!g) return POLAR_ENOMEM;
     g->ctx.assign((size_t)ngpus, nullptr);
     g->comms.assign((size_t)ngpus, nullptr);
-    g->ferr.assign((size_t)ngpus, Buf{});
+    g->ferr.resize((size_t)ngpus);
+    g->recv.resize((size_t)ngpus);
     std::vector<int> devs((size_t)ngpus);
     for (int i = 0; i < ngpus; ++i) {
         devs[(size_t)i] = i;
@@ -2302,23 +2215,20 @@ int polar_group_stop_rule_batch(polar_group *g, unsigned long long seed, unsigne
         if (rcs[(size_t)i]) return rcs[(size_t)i];
     // rank i's counts land at [i * frames_per_gpu, (i + 1) * frames_per_gpu) of every rank's receive buffer; only
     // GPU 0's copy is used (ranks > 0 receive into a buffer of the same size, as the collective requires)
-    std::vector<Buf> recv((size_t)ngpus);
-    recv[0] = g->gathered;
+    // (the buffers belong to the group and only grow: nothing is allocated between GroupStart and GroupEnd)
+    std::vector<void *> recv((size_t)ngpus);
+    recv[0] = g->gathered.p;
     for (int i = 1; i < ngpus && !rc; ++i) {
         DeviceGuard guard(i);
-        if (hipMalloc(&recv[(size_t)i].p, total * 4) != hipSuccess) rc = POLAR_ENOMEM;
+        rc = ensure_nomem(g->ctx[(size_t)i], g->recv[(size_t)i], total * 4, "group receive buffer");
+        recv[(size_t)i] = g->recv[(size_t)i].p;
     }
     if (!rc && !group_collective(g, [&](int i) {
-            return R.AllGather(g->ferr[(size_t)i].p, recv[(size_t)i].p, frames_per_gpu, kNcclUint32, g->comms[(size_t)i],
+            return R.AllGather(g->ferr[(size_t)i].p, recv[(size_t)i], frames_per_gpu, kNcclUint32, g->comms[(size_t)i],
                                g->ctx[(size_t)i]->stream);
         }))
         rc = POLAR_EDEVICE;
     if (!rc && !group_sync(g)) rc = POLAR_EDEVICE;
-    for (int i = 1; i < ngpus; ++i)
-        if (recv[(size_t)i].p) {
-            DeviceGuard guard(i);
-            (void)hipFree(recv[(size_t)i].p);
-        }
     if (rc) return rc;
     unsigned long long h[3] = {0, 0, 0};
     {

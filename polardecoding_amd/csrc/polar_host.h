@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_owned.h"
 #include "polar_params.h"
 
 namespace polar {
@@ -20,34 +21,45 @@ struct GenParams;   // gen_common.h
 struct ScanParams;  // scan_lanes.h
 }
 
-struct PolarBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    unsigned *queue = nullptr;   // job counter of the persistent kernels that use this scratch buffer (work_queue() below)
+// What belongs to one stream of a ctx.  The rule: a buffer that a decode on c->stream writes and that the two halves of
+// fer_batch_impl (polar_hip.hip) would share belongs here, beside the stream.  A polar_ctx IS its current lane (c->stream,
+// c->scratch, ... are the names the k_*.hip launchers read) and holds a second one, lane_b; swap_lane() below is the only
+// code that exchanges the two, so a member added here is swapped without another line.
+// Deliberately outside the lane: the ad_* / scf_* buffers (fer_batch_impl does not split for adaptive CA-SCL or SC-Flip)
+// and q8_pm (fer_batch_impl passes no d_pm, so the halves never touch it).
+struct Lane {
+    Stream stream;    // before the buffers: they are released first
+    Buf scratch;      // per-wave scratch of the persistent kernels, with their work queue
+    Buf rm_rows;      // polar_create_rm: the recovered N-wide rows of one chunk
+    Buf q8_rows;      // POLAR_Q8: the quantised rows of the float entry points, one chunk
 };
-typedef PolarBuf Buf;
 
-struct polar_ctx {
+// Every device resource of a ctx is a member of an owning type (dev_owned.h): polar_destroy only synchronises and deletes.
+// The streams are declared before the buffers, so that the buffers are released first.
+struct polar_ctx : Lane {
     polar_cfg cfg{};
     int n = 0, A = 0, NW = 0, logL = 0;
     std::vector<int> info_order;          // I[]
     std::vector<unsigned char> frozen;    // [N]
     std::vector<int> taps;
     std::vector<uint32_t> h_crc_tab;      // [N]
-    uint32_t *d_frozen = nullptr;         // [NW] bit = frozen
-    uint32_t *d_info = nullptr;           // [NW] bit = unfrozen
-    uint32_t *d_crc_tab = nullptr;        // [N] or null
-    uint32_t *d_gc_rows = nullptr;        // [K] systematic CRC generator rows (D^(r+k) mod g), or null
-    uint32_t *d_frozen_override = nullptr;
-    int *d_info_order = nullptr;          // [A] for the device-side generator
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    Stream copy_stream;                   // host -> device copies overlap the decode of the previous chunk
+    Lane lane_b;                          // polar_fer_batch runs its two halves on two streams: the second one's lane
+    Event ev_b;
+    Event ev_in[2], ev_free[2], ev_out[2];   // chunked host pipeline
+    Event ev0, ev1;                       // polar_time_decode_device
+    DevMem<uint32_t> d_frozen;            // [NW] bit = frozen
+    DevMem<uint32_t> d_info;              // [NW] bit = unfrozen
+    DevMem<uint32_t> d_crc_tab;           // [N] or empty
+    DevMem<uint32_t> d_gc_rows;           // [K] systematic CRC generator rows (D^(r+k) mod g), or empty
+    DevMem<uint32_t> d_frozen_override;
+    DevMem<int> d_info_order;             // [A] for the device-side generator and the encoder (info_order_table)
     int num_cu = 0;
     Buf in, bits, pm, flags;              // staging for the host-pointer entry points
     Buf bp_iters;                         // polar_bp_decode_batch: round trips per frame
     int bp_stop = POLAR_BP_STOP_NONE;     // polar_bp_set_stop
     // adaptive CA-SCL (polar_cascl_set_stages): list sizes of the stages (empty = the fixed decoder) and one context per
-    // stage (an SC context for L = 1, null for L = cfg.L: this context's own fixed decoder)
+    // stage (an SC context for L = 1, null for L = cfg.L: this context's own fixed decoder); they borrow this ctx's stream
     std::vector<int> cascl_stages;
     std::vector<polar_ctx *> stage_ctx;
     Buf ad_flags;                         // per-frame flags when the caller passes none
@@ -59,42 +71,33 @@ struct polar_ctx {
     int scan_I = 4;                       // SCAN (POLAR_ALGO_SCAN): iterations (polar_scan_set_iters)
     Buf scan_llr, scan_ext;               // polar_scan_decode_batch: staging of the soft outputs
     // 5G rate matching (polar_create_rm): E, POLAR_RM_* mode (POLAR_RM_NONE: a plain ctx), channel interleaver, its tables
-    // (sent-row position of e_k, and the inverse) and the recovered rows, one buffer per stream of polar_fer_batch
+    // (sent-row position of e_k, and the inverse); the recovered rows are the lane's rm_rows
     int rm_E = 0, rm_mode = POLAR_RM_NONE, rm_ibil = 0;
-    uint16_t *d_rm_ilv = nullptr, *d_rm_ilv_inv = nullptr;
-    Buf rm_rows, rm_rows_b;
+    DevMem<uint16_t> d_rm_ilv, d_rm_ilv_inv;
     Buf genie_rows;                       // polar_construct_batch: one chunk of design rows
     // dynamic frozen bits (polar_create_dyn): positions (ascending), dense constraint rows [D][NW] and the row index of
     // every leaf (-1: not dynamic) on the device
     bool is_dyn = false;
     std::vector<int> dyn_pos;
-    uint32_t *d_dyn_mask = nullptr;
-    int *d_dyn_row = nullptr, *d_dyn_pos = nullptr;
+    DevMem<uint32_t> d_dyn_mask;
+    DevMem<int> d_dyn_row, d_dyn_pos;
     // encoder side (polar_encode_device, polar_payload_device, polar_set_systematic): i with I[i] = j per position
     // (0xFFFF = frozen), D^i mod g(D) for i < A, both built on first use; the two CRC tables of CA-SCL / SC-Flip (the plain
     // one of make_crc_table and the systematic-mode one, whichever is live sits in d_crc_tab); scratch rows of the encoder
     bool sys_polar = false;
-    uint16_t *d_enc_inv = nullptr;
-    uint32_t *d_enc_rtab = nullptr;
+    DevMem<uint16_t> d_enc_inv;
+    DevMem<uint32_t> d_enc_rtab;
     std::vector<uint32_t> h_crc_tab_sys;
     Buf enc_u, enc_x, enc_io;
-    // fixed-point min-sum (dtype POLAR_Q8): the quantiser (polar_q8_set_quant), the quantised rows of the float entry points
-    // (one buffer per stream of polar_fer_batch) and the int32 metrics behind their double d_pm
+    // fixed-point min-sum (dtype POLAR_Q8): the quantiser (polar_q8_set_quant) and the int32 metrics behind the double d_pm
+    // of the float entry points; their quantised rows are the lane's q8_rows
     double q8_scale = 2.0;
     int q8_qc = 8, q8_qi = 8;
-    Buf q8_rows, q8_rows_b, q8_pm;
+    Buf q8_pm;
     Buf in2[2], bits2[2];                // chunked host pipeline: ping-pong device buffers
-    uint32_t *h_bits[2] = {nullptr, nullptr};   // pinned host copies of the packed decisions
-    size_t h_bits_cap = 0;
-    double *h_in[2] = {nullptr, nullptr};       // pinned staging of the caller's (pageable) input chunks, big batches only
-    size_t h_in_cap = 0;
-    hipStream_t copy_stream = nullptr;    // host -> device copies overlap the decode of the previous chunk
-    hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    Buf scratch;                          // k_scl_fast per-wave scratch
+    PinnedMem<uint32_t> h_bits[2];       // pinned host copies of the packed decisions
+    PinnedMem<double> h_in[2];           // pinned staging of the caller's (pageable) input chunks, big batches only
     Buf gen_llr, gen_u, gen_cnt;          // polar_fer_batch
-    Buf scratch_b;                        // second decode scratch: polar_fer_batch runs its two halves on two streams
-    hipStream_t stream_b = nullptr;
-    hipEvent_t ev_b = nullptr;
     std::string last_error;
     std::string kernel_name;
     // kernel selection overrides, set only through include/polar_hip_testing.h (cross-checks of the tuned kernels)
@@ -103,7 +106,18 @@ struct polar_ctx {
     bool use_fast4 = false;     // four codewords per wavefront (k_scl_fast4) at N = 1024
     bool force_spill = false;   // no tuned L = 8 kernel; with force_generic: the global-scratch variant of k_scl_generic
     int big_split = 0;          // 35 | 46 | 57: LDS / scratch split of k_scl_big; 0 = the measured best
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+// c's lane <-> c->lane_b: work enqueued through c afterwards runs on the other stream with the other stream's buffers
+inline void swap_lane(polar_ctx *c) { std::swap(static_cast<Lane &>(*c), c->lane_b); }
+
+// c works on its other lane while this object lives, and on its own again on every way out of the scope
+struct OtherLane {
+    polar_ctx *c;
+    explicit OtherLane(polar_ctx *ctx) : c(ctx) { swap_lane(c); }
+    ~OtherLane() { swap_lane(c); }
+    OtherLane(const OtherLane &) = delete;
+    OtherLane &operator=(const OtherLane &) = delete;
 };
 
 // Every entry point that allocates or launches runs on the ctx's device whatever the calling thread had current,
@@ -146,6 +160,27 @@ inline int ensure(polar_ctx *c, Buf &b, size_t bytes)
     return POLAR_OK;
 }
 
+// ensure() where the caller chooses the size freely (encoder rows, SCAN scratch, the groups' receive buffers): running out
+// of device memory is POLAR_ENOMEM, the runtime's error is cleared and the ctx stays usable; any other failure is
+// POLAR_EDEVICE.
+inline int ensure_nomem(polar_ctx *c, Buf &b, size_t bytes, const char *what)
+{
+    if (b.cap >= bytes) return POLAR_OK;
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        c->last_error = std::string(what) + ": out of device memory";
+        return POLAR_ENOMEM;
+    }
+    if (e != hipSuccess) return fail(c, e, what);
+    b.cap = bytes;
+    return POLAR_OK;
+}
+
 // Work queue of a persistent kernel.  The resident wavefronts take their first job by their index and every further one
 // from a counter (atomic add), so a wavefront that gets fewer issue slots simply takes fewer jobs: a launch ends when the
 // work does, not when the slowest statically assigned wavefront does.  One counter per scratch buffer
@@ -173,7 +208,7 @@ struct LaunchShape {
     long long grid_cap = 0;             // at most this many blocks; 0: no limit
     bool set_lds_attr = true;           // raise the kernel's dynamic-LDS limit to lds first
     bool use_queue = true;              // false: fixed stride even with more jobs than resident slots
-    int (*alloc)(polar_ctx *, Buf &, size_t) = ensure;   // grows c->scratch
+    const char *nomem_what = nullptr;   // set: c->scratch grows with ensure_nomem(..., nomem_what), else with ensure()
 };
 struct LaunchPlan {
     int grid;
@@ -193,7 +228,8 @@ inline int plan_launch(polar_ctx *c, const void *kern, const LaunchShape &s, Lau
     if (grid < 1) grid = 1;
     *out = LaunchPlan{(int)grid, nullptr, nullptr};
     if (s.scratch_per_block) {
-        int rc = s.alloc(c, c->scratch, s.scratch_per_block * (size_t)grid);
+        const size_t bytes = s.scratch_per_block * (size_t)grid;
+        int rc = s.nomem_what ? ensure_nomem(c, c->scratch, bytes, s.nomem_what) : ensure(c, c->scratch, bytes);
         if (rc) return rc;
         out->scratch = c->scratch.p;
     }
