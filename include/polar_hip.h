@@ -34,6 +34,7 @@ extern "C" {
 #define POLAR_ALGO_CASCL 3 /* CASCL      CASCL_1024_L8.c:601-761               */
 #define POLAR_ALGO_SCF 4   /* CRC-aided SC-Flip (no reference counterpart; polar_scf_set_flips below) */
 #define POLAR_ALGO_SCAN 5  /* soft-output SCAN (no reference counterpart; polar_scan_set_iters below) */
+#define POLAR_ALGO_BPL 6   /* BP list decoding over permuted factor graphs (polar_bpl_set_graphs below) */
 
 /* dtype: the arithmetic type the message passing runs in */
 #define POLAR_F64 0 /* IEEE binary64 like the reference: bit-identical decisions (the parity gate) */
@@ -317,6 +318,66 @@ int polar_scan_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, do
 /* Host-buffer form: llr_in [B][N] LLRs (E per row on a rate-matched ctx); u_hat [B][N], llr_u and ext_x [B][N] of the ctx
  * dtype; each of the three outputs may be NULL. */
 int polar_scan_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, void *llr_u, void *ext_x);
+
+/* --- BP list decoding over permuted factor graphs (Elkelesh, Ebada, Cammerer and ten Brink, 2018) --------------------------
+ * A polar code of length N = 2^n has n! factor graphs, one per ordering of its n stages.  A frame whose messages do not
+ * settle on one graph often settles on another.  A permutation of the stages is a permutation of the bits of the position
+ * index (Doan, Hashemi, Mondelli and Gross, GLOBECOM 2018), so every attempt below is the BP decoder of this library,
+ * unchanged, on a permuted row with a permuted frozen mask.  (The reference's BP_128_fag.c is the graph with the stage order
+ * reversed.)
+ * Context.  A POLAR_ALGO_BPL context takes the cfg of a BP context, bp_iters = iterMax of one attempt.  A CRC is optional:
+ * crc_r = 0 means none; crc_r >= 1 with its taps works as for CA-SCL: A = K + r positions are unfrozen, and the generator and
+ * the error counters treat the CRC exactly as they do for POLAR_ALGO_CASCL, crc_systematic included.  (POLAR_ALGO_BP ignores
+ * crc_r as before.)  cfg.L is ignored and reported as 1.  dtypes POLAR_F64 and POLAR_F32 and every N the BP kernels take;
+ * POLAR_Q8 returns POLAR_ENOKERNEL, as for BP.
+ * Graphs.  A graph is a permutation pi of {0 .. n-1}.  It maps positions by
+ *       sigma_pi(j) = sum over b of ((j >> b) & 1) << pi[b],
+ * which moves index bit b to bit pi[b].  A context holds an ordered list pi_0 .. pi_{P-1}, 1 <= P <= 32.
+ * Rules, for a context with frozen mask fz, CRC table crc_tab (crc_tab[I[i]] = D^i mod g(D), the table the list kernels use)
+ * and one input row l[0..N) (LLRs, or y with sigma > 0, left as they are):
+ *   1. attempt p is POLAR_ALGO_BP with POLAR_BP_STOP_G and the same bp_iters and dtype, run on row_p[j] = l[sigma_p(j)] with
+ *      frozen mask fz_p[j] = fz[sigma_p(j)].  It yields decisions u'_p, round trips t_p and converged flag c_p, bit for bit
+ *      what a BP context built on that permuted code returns for that row.  Then u_hat_p[sigma_p(j)] = u'_p[j].
+ *   2. with sigma > 0 the permutation moves the y values, and the BP kernel forms 2*y/sigma/sigma on load as it does today.
+ *   3. crcok_p = (XOR over {j : u_hat_p[j] = 1} of crc_tab[j]) == 0.  It is defined only with a CRC.
+ *   4. attempt p is accepted iff c_p, and with a CRC also crcok_p.  An attempt that converges and then fails the CRC is
+ *      over: it is not iterated further.
+ *   5. the output is the first accepted attempt, graph = p.  If none is accepted the output is attempt 0 with graph = P.  A
+ *      frame accepted at attempt p is never touched again.
+ *   6. with q the reported attempt (graph, or 0 on fallback): iters = t_q; the flags word has POLAR_FLAG_BP_CONVERGED iff c_q
+ *      and POLAR_FLAG_CRC_PASS iff the context has a CRC and crcok_q; total_iters is the sum of t_p over every attempt run
+ *      for the frame; the metric is 0.0.
+ *   7. identity: P = 1, pi_0 = identity and no CRC is a BP context with POLAR_BP_STOP_G, bit for bit, iters included.
+ *   8. if pi_p is the identity, no permutation kernel needs to run for that attempt.
+ * Default list: the cyclic shifts pi_s[b] = (b + s) mod n, s = 0 .. P-1, with P = min(n, 8).  This is a choice; no FER stands
+ * behind it yet.
+ * Honoured by polar_decode, polar_decode_batch(_y) (a frozen_mask override returns POLAR_EINVAL, as for SCF),
+ * polar_decode_device, polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device, polar_kernel_name, polar_ctx_info
+ * and polar_info_order.  A polar_create_rm context decodes the recovered N-wide row.  polar_group_* and polar_fer_multi_gpu
+ * run the default list.
+ * The host reads the count of open frames between attempts: one 4-byte copy and a stream sync per attempt run after the
+ * first, and it stops after an attempt that leaves no frame open.  A decode while the ctx stream is capturing a graph returns
+ * POLAR_EINVAL, as for the adaptive rule.
+ * Refused with POLAR_EINVAL, the ctx staying usable: polar_bp_*, polar_cascl_*, polar_scf_*, polar_scan_* and polar_q8_* on a
+ * BPL context; polar_bpl_* (but polar_bpl_cyclic_graphs) on any other context; polar_set_systematic(ctx, 1), polar_create_dyn
+ * and polar_create_crc_file with a BPL cfg.
+ * Out of scope: choosing among non-converged candidates by Euclidean distance; searching for good permutations; BPL on
+ * systematic or CRC-file contexts; the reference's *_fag.c programs as a second oracle. */
+/* perms [P][n], row p = pi_p.  POLAR_EINVAL, with the ctx unchanged: not a BPL ctx, P outside 1..32, or a row that is not a
+ * permutation of 0 .. n-1. */
+int polar_bpl_set_graphs(polar_ctx *ctx, const int *perms, int P);
+/* the list of the ctx: *P and perms [P][n]; both outputs nullable */
+int polar_bpl_get_graphs(const polar_ctx *ctx, int *P, int *perms);
+/* the cyclic shifts out[s][b] = (b + s) mod n, s = 0 .. P-1; 5 <= n <= 12, 1 <= P <= 32.  Host only. */
+int polar_bpl_cyclic_graphs(int n, int P, int *out);
+/* polar_decode_device for a BPL ctx, plus per frame (each nullable, [B] uint32): d_iters and d_flags of rule 6, d_graph of
+ * rule 5 and d_total_iters of rule 6. */
+int polar_bpl_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                            uint32_t *d_iters, uint32_t *d_flags, uint32_t *d_graph, uint32_t *d_total_iters);
+/* Host-buffer form: llr_in [B][N] LLRs (E per row on a rate-matched ctx), u_hat [B][N]; iters, flags, graph, total_iters
+ * (nullable) [B]. */
+int polar_bpl_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *iters, unsigned *flags,
+                           unsigned *graph, unsigned *total_iters);
 
 /* --- 5G NR rate matching (TS 38.212 5.4.1; no reference counterpart) -------------------------------------------------
  * A rate-matched context sends E channel values per codeword instead of N.  Notation of 38.212: A = K + r bits enter the

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF, ALGO_SCAN = 0, 1, 2, 3, 4, 5
+ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF, ALGO_SCAN, ALGO_BPL = 0, 1, 2, 3, 4, 5, 6
 F64, F32, Q8 = 0, 1, 2   # Q8: fixed-point min-sum on int8 LLRs (SC / SCL / CA-SCL, N <= 1024)
 FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
 RM_NONE, RM_REPEAT, RM_PUNCTURE, RM_SHORTEN = 0, 1, 2, 3   # polar_rm_info modes (5G rate matching)
@@ -100,6 +100,11 @@ def load_library(testing=False):
     L.polar_scf_set_flips.argtypes = [vp, C.c_int]
     L.polar_scf_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
     L.polar_scf_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
+    L.polar_bpl_set_graphs.argtypes = [vp, ip, C.c_int]
+    L.polar_bpl_get_graphs.argtypes = [vp, ip, ip]
+    L.polar_bpl_cyclic_graphs.argtypes = [C.c_int, C.c_int, ip]
+    L.polar_bpl_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp, vp, vp]
+    L.polar_bpl_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up, up, up]
     L.polar_scan_set_iters.argtypes = [vp, C.c_int]
     L.polar_scan_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
     L.polar_scan_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, vp, vp]
@@ -209,6 +214,17 @@ def q8_quantize(values, scale=2.0, qc=8, sigma=0.0):
     rc = lib.polar_q8_quantize_host(_ptr(v, C.c_double), v.size, float(sigma), float(scale), int(qc), _ptr(out, C.c_int8))
     if rc != 0:
         raise PolarError(f"polar_q8_quantize_host: {lib.polar_strerror(rc).decode()} (rc={rc})")
+    return out
+
+
+def bpl_cyclic_graphs(n, P):
+    """polar_bpl_cyclic_graphs: the cyclic shifts pi_s[b] = (b + s) mod n, s = 0 .. P-1, as an int32 array [P][n] (the default
+    list of a BPL decoder is bpl_cyclic_graphs(n, min(n, 8))).  Host only."""
+    lib = load_library()
+    out = np.zeros((max(int(P), 1), max(int(n), 1)), dtype=np.int32)
+    rc = lib.polar_bpl_cyclic_graphs(int(n), int(P), _ptr(out, C.c_int))
+    if rc != 0:
+        raise PolarError(f"polar_bpl_cyclic_graphs({n}, {P}): {lib.polar_strerror(rc).decode()} (rc={rc})")
     return out
 
 
@@ -397,6 +413,7 @@ class Decoder:
         self.cascl_stages = ()
         self.scf_flips = None   # None: the library's default (min(8, K + r))
         self.scan_iters = None  # None: the library's default (4)
+        self._bpl_graphs = None # None: the library's default list (min(n, 8) cyclic shifts)
         self._rm = (int(E), 1 if ibil else 0) if E is not None else None
         self._dyn = None
         if dyn is not None:
@@ -454,6 +471,8 @@ class Decoder:
             self.set_scf_flips(self.scf_flips)
         if self.scan_iters is not None:
             self.set_scan_iters(self.scan_iters)
+        if self._bpl_graphs is not None:
+            self.set_bpl_graphs(self._bpl_graphs)
         if self._sys_polar:
             self._sys_polar = False
             self.set_systematic(True)
@@ -522,6 +541,26 @@ class Decoder:
         """SCAN iteration count (polar_scan_set_iters): 1 <= iters <= 64, default 4."""
         self._check(self._lib.polar_scan_set_iters(self._h, int(iters)), "polar_scan_set_iters")
         self.scan_iters = int(iters)
+
+    def set_bpl_graphs(self, graphs):
+        """BP list decoding (polar_bpl_set_graphs): the ordered list of factor graphs, [P][n] permutations of 0 .. n-1 with
+        1 <= P <= 32; pi[b] is the index bit that bit b of a position moves to.  Refused (PolarError, decoder unchanged) on a
+        decoder that is not BPL and for a row that is not a permutation."""
+        n = self.N.bit_length() - 1
+        g = np.ascontiguousarray(graphs, dtype=np.int32)
+        if g.ndim != 2 or g.shape[1] != n:
+            raise ValueError(f"graphs must have shape [P][{n}]")
+        self._check(self._lib.polar_bpl_set_graphs(self._h, _ptr(g, C.c_int), int(g.shape[0])), "polar_bpl_set_graphs")
+        self._bpl_graphs = g.copy()
+
+    @property
+    def bpl_graphs(self):
+        """polar_bpl_get_graphs: the list of a BPL decoder as an int32 array [P][n]"""
+        P = C.c_int()
+        self._check(self._lib.polar_bpl_get_graphs(self._h, C.byref(P), None), "polar_bpl_get_graphs")
+        out = np.zeros((P.value, self.N.bit_length() - 1), dtype=np.int32)
+        self._check(self._lib.polar_bpl_get_graphs(self._h, None, _ptr(out, C.c_int)), "polar_bpl_get_graphs")
+        return out
 
     def set_systematic(self, on):
         """Systematic polar code (polar_set_systematic): the codeword carries the CRC word on the information set.  Refused
@@ -763,6 +802,37 @@ class Decoder:
         self._check(self._lib.polar_scf_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
                                                      _ptr(fl, C.c_uint), _ptr(at, C.c_uint)), "polar_scf_decode_batch")
         return uh, fl, at
+
+    def decode_bpl_device(self, d_in, sigma=0.0, out_bits=None, iters=None, flags=None, graph=None, total_iters=None):
+        """polar_bpl_decode_device: like decode_device, plus per frame (optional int32 tensors [B]) the round trips of the
+        reported attempt (`iters`), FLAG_BP_CONVERGED / FLAG_CRC_PASS (`flags`), the graph that decided the frame (`graph`, P
+        when none did) and the round trips of every attempt run for it (`total_iters`).  Returns out_bits."""
+        import torch
+        B = self._dev_rows(d_in)
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        for t in (iters, flags, graph, total_iters):
+            if t is not None and (t.numel() < B or t.element_size() != 4 or not t.is_contiguous()):
+                raise ValueError("iters / flags / graph / total_iters must be contiguous 32-bit tensors of at least B elements")
+        opt = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (iters, flags, graph, total_iters)]
+        self._check(self._lib.polar_bpl_decode_device(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B, C.c_void_p(out_bits.data_ptr()), *opt),
+            "polar_bpl_decode_device")
+        return out_bits
+
+    def decode_bpl_batch(self, llr):
+        """polar_bpl_decode_batch: llr [B][N] -> (u_hat [B][N] int32, iters, flags, graph, total_iters: [B] uint32 each)."""
+        llr = self._rows(llr)
+        B = llr.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        it, fl, gr, tot = (np.zeros(B, dtype=np.uint32) for _ in range(4))
+        self._check(self._lib.polar_bpl_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int), _ptr(it, C.c_uint),
+                                                     _ptr(fl, C.c_uint), _ptr(gr, C.c_uint), _ptr(tot, C.c_uint)),
+                    "polar_bpl_decode_batch")
+        return uh, it, fl, gr, tot
 
     def decode_scan_device(self, d_in, sigma=0.0, out_bits=None, llr_u=None, ext_x=None):
         """polar_scan_decode_device: soft-output SCAN.  llr_u and ext_x are optional tensors [B][N] of the decoder's dtype
@@ -1107,6 +1177,18 @@ def SCFlip(N, K, T=8, crc_taps=CRC24C_TAPS, crc_file=None, **kw):
         dec = Decoder(N, K, ALGO_SCF, L=1, crc_taps=crc_taps, **kw)
     if T != 8:
         dec.set_scf_flips(T)
+    return dec
+
+
+def BPL(N, K, iterMax=100, graphs=None, crc_taps=None, **kw):
+    """BP list decoding over permuted factor graphs (include/polar_hip.h, POLAR_ALGO_BPL): BP with the G-matrix stop rule and
+    iterMax round trips per attempt; a frame that does not converge (or, with ``crc_taps``, converges to a word that fails the
+    CRC) is decoded again on the next graph of the list.  ``graphs``: None (the default list, min(n, 8) cyclic shifts), an
+    int P (the first P cyclic shifts) or a list of permutations of 0 .. n-1 (Decoder.set_bpl_graphs)."""
+    dec = Decoder(N, K, ALGO_BPL, L=1, bp_iters=iterMax, crc_taps=crc_taps, **kw)
+    if graphs is not None:
+        n = int(N).bit_length() - 1
+        dec.set_bpl_graphs(bpl_cyclic_graphs(n, graphs) if isinstance(graphs, (int, np.integer)) else graphs)
     return dec
 
 

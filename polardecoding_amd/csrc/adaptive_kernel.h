@@ -3,8 +3,9 @@
 // The stage decoders are the existing kernels, unchanged; what runs between two stages is here:
 //   k_ad_crc_check   CRC syndrome of packed SC decisions (first stage L = 1): POLAR_FLAG_CRC_PASS into the flags word
 //   k_ad_fail_count  \
-//   k_ad_fail_scan    > stable compaction of the frames whose flags lack POLAR_FLAG_CRC_PASS into an index list + count
-//   k_ad_fail_write  /  (wave64 ballot + mbcnt inside a block, one-block scan of the block counts; no atomics)
+//   k_ad_fail_scan    > stable compaction of the frames whose flags lack a bit of `need` (POLAR_FLAG_CRC_PASS here; BP list
+//   k_ad_fail_write  /  decoding, bpl_kernel.h, asks for its own bits) into an index list + count
+//                       (wave64 ballot + mbcnt inside a block, one-block scan of the block counts; no atomics)
 //   k_ad_gather      rows idx[k] of the caller's input -> a contiguous stage buffer (16-byte loads when aligned)
 //   k_ad_scatter     a stage's packed decisions, metric, flags and list size -> the original frame indices
 #pragma once
@@ -58,8 +59,8 @@ __global__ __launch_bounds__(AD_THREADS) void k_ad_crc_check(const uint32_t *__r
     }
 }
 
-// number of failing frames (no POLAR_FLAG_CRC_PASS) among the AD_CHUNK frames of each block
-__global__ __launch_bounds__(AD_THREADS) void k_ad_fail_count(const uint32_t *__restrict__ flags, int n,
+// number of failing frames ((flags & need) != need) among the AD_CHUNK frames of each block
+__global__ __launch_bounds__(AD_THREADS) void k_ad_fail_count(const uint32_t *__restrict__ flags, int n, uint32_t need,
                                                               uint32_t *__restrict__ blk_cnt)
 {
     __shared__ uint32_t wsum[AD_THREADS / 64];
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(AD_THREADS) void k_ad_fail_count(const uint32_t *__
 #pragma unroll
     for (int r = 0; r < AD_ROUNDS; ++r) {
         const long long i = base + r * AD_THREADS + threadIdx.x;
-        const bool fail = i < n && !(flags[i] & AD_CRC_PASS);
+        const bool fail = i < n && (flags[i] & need) != need;
         cnt += (uint32_t)__popcll(__ballot(fail));
     }
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(AD_SCAN_THREADS) void k_ad_fail_scan(const uint32_t
 
 // idx_out[blk_off[block] + rank] = idx_in[i] (or i when idx_in is null) for every failing i, in ascending order of i
 __global__ __launch_bounds__(AD_THREADS) void k_ad_fail_write(const uint32_t *__restrict__ flags,
-                                                              const uint32_t *__restrict__ idx_in, int n,
+                                                              const uint32_t *__restrict__ idx_in, int n, uint32_t need,
                                                               const uint32_t *__restrict__ blk_off,
                                                               uint32_t *__restrict__ idx_out)
 {
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(AD_THREADS) void k_ad_fail_write(const uint32_t *__
     const long long base = (long long)blockIdx.x * AD_CHUNK;
     for (int r = 0; r < AD_ROUNDS; ++r) {
         const long long i = base + r * AD_THREADS + threadIdx.x;
-        const bool fail = i < n && !(flags[i] & AD_CRC_PASS);
+        const bool fail = i < n && (flags[i] & need) != need;
         const unsigned long long m = __ballot(fail);
         if (lane == 0) wcnt[wave] = (uint32_t)__popcll(m);
         __syncthreads();

@@ -19,14 +19,14 @@ int log2i(long long v)
 
 }  // namespace
 
-int polar_tu::ad_crc_check(polar_ctx *c, const uint32_t *d_bits, uint32_t *d_flags, size_t B)
+int polar_tu::ad_crc_check(polar_ctx *c, const uint32_t *d_bits, const uint32_t *d_crc_tab, uint32_t *d_flags, size_t B)
 {
     const int NW = c->NW;
     const int G = NW < 64 ? NW : 64;
     const long long waves = ((long long)B * G + 63) / 64;
     const int grid = grid_for(c, waves * 64);
     const size_t lds = sizeof(uint32_t) * (size_t)NW * 32;
-    hipLaunchKernelGGL(polar::k_ad_crc_check, dim3(grid), dim3(polar::AD_THREADS), lds, c->stream, d_bits, c->d_crc_tab,
+    hipLaunchKernelGGL(polar::k_ad_crc_check, dim3(grid), dim3(polar::AD_THREADS), lds, c->stream, d_bits, d_crc_tab,
                        d_flags, NW, (int)B);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
@@ -34,18 +34,19 @@ int polar_tu::ad_crc_check(polar_ctx *c, const uint32_t *d_bits, uint32_t *d_fla
 
 size_t polar_tu::ad_blocks(size_t n) { return (n + polar::AD_CHUNK - 1) / polar::AD_CHUNK; }
 
-int polar_tu::ad_compact(polar_ctx *c, const uint32_t *d_flags, const uint32_t *d_idx_in, size_t n, uint32_t *d_blk,
-                         uint32_t *d_idx_out, uint32_t *d_count)
+int polar_tu::ad_compact(polar_ctx *c, const uint32_t *d_flags, const uint32_t *d_idx_in, size_t n, uint32_t need,
+                         uint32_t *d_blk, uint32_t *d_idx_out, uint32_t *d_count)
 {
     const int nblk = (int)ad_blocks(n);
     uint32_t *blk_cnt = d_blk, *blk_off = d_blk + nblk;
-    hipLaunchKernelGGL(polar::k_ad_fail_count, dim3(nblk), dim3(polar::AD_THREADS), 0, c->stream, d_flags, (int)n, blk_cnt);
+    hipLaunchKernelGGL(polar::k_ad_fail_count, dim3(nblk), dim3(polar::AD_THREADS), 0, c->stream, d_flags, (int)n, need,
+                       blk_cnt);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(polar::k_ad_fail_scan, dim3(1), dim3(polar::AD_SCAN_THREADS), 0, c->stream, blk_cnt, nblk, blk_off,
                        d_count);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(polar::k_ad_fail_write, dim3(nblk), dim3(polar::AD_THREADS), 0, c->stream, d_flags, d_idx_in, (int)n,
-                       blk_off, d_idx_out);
+                       need, blk_off, d_idx_out);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

@@ -81,7 +81,8 @@ size_t chunk_rows(size_t B, size_t row_bytes, size_t floor = 64)
 }
 
 // contexts whose code carries a CRC: r, crc_tab, the generator's CRC multiply, the systematic K-bit error metric
-bool has_crc(int algo) { return algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF; }
+// (BP list decoding: optional, crc_r = 0 is a code without one)
+bool has_crc(int algo) { return algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF || algo == POLAR_ALGO_BPL; }
 
 // ---- 5G rate matching, host side (include/polar_hip.h rules 1-5) ----
 const int kRmP[32] = {0, 1, 2, 4, 3, 5, 6, 7, 8, 16, 9, 17, 10, 18, 11, 19, 12, 20, 13, 21, 14, 22, 15, 23, 24, 25, 26, 28, 27, 29, 30, 31};
@@ -220,7 +221,7 @@ enum class Family { BP, DYN, SC_LANES, FAST, FAST2, FAST4, BIG, GENERIC };
 Family kernel_family(const polar_ctx *c, int in_is_f32, size_t B)
 {
     const polar_cfg &g = c->cfg;
-    if (g.algo == POLAR_ALGO_BP) return Family::BP;
+    if (g.algo == POLAR_ALGO_BP || g.algo == POLAR_ALGO_BPL) return Family::BP;   // BPL: the kernel of every attempt
     if (c->is_dyn) return Family::DYN;   // dynamic frozen bits: one kernel for every shape
     if (sc_lanes_ok(c, B)) return Family::SC_LANES;
     if (fast_ok(c, in_is_f32)) {
@@ -354,13 +355,14 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
 
     polar_ctx *s0 = c->stage_ctx[0] ? c->stage_ctx[0] : c;
     if ((rc = decode_fixed(s0, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, s0->d_frozen))) return rc;
-    if (st[0] == 1 && (rc = polar_tu::ad_crc_check(c, d_bits, d_flags, B))) return rc;
+    if (st[0] == 1 && (rc = polar_tu::ad_crc_check(c, d_bits, c->d_crc_tab, d_flags, B))) return rc;
     if (d_list) HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_list), st[0], B, c->stream));
     const uint32_t *cur_idx = nullptr, *cur_flags = d_flags;
     size_t n = B;
     for (int s = 1; s < m; ++s) {
         uint32_t *idx = (uint32_t *)c->ad_idx[(s - 1) & 1].p;
-        if ((rc = polar_tu::ad_compact(c, cur_flags, cur_idx, n, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p)))
+        if ((rc = polar_tu::ad_compact(c, cur_flags, cur_idx, n, POLAR_FLAG_CRC_PASS, (uint32_t *)c->ad_blk.p, idx,
+                                          (uint32_t *)c->ad_cnt.p)))
             return rc;
         uint32_t h = 0;
         HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -415,7 +417,8 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
     uint32_t *idx = (uint32_t *)c->ad_idx[0].p;
-    if ((rc = polar_tu::ad_compact(c, d_flags, nullptr, B, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p))) return rc;
+    if ((rc = polar_tu::ad_compact(c, d_flags, nullptr, B, POLAR_FLAG_CRC_PASS, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p)))
+        return rc;
     uint32_t h = 0;
     HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -446,6 +449,94 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     return POLAR_OK;
 }
 
+// BP list decoding (POLAR_ALGO_BPL, include/polar_hip.h).  Attempt 0 runs on the whole batch: with pi_0 = identity straight
+// into the caller's outputs (no permutation kernel), else through the staging buffers like every later attempt.  A later
+// attempt compacts the frames that are still open (the adaptive rule's glue, asked for CONVERGED and, with a CRC, CRC_PASS),
+// gathers their rows permuted, runs the ctx's BP kernel with the permuted frozen mask and scatters the accepted frames back
+// un-permuted, in chunks of at most 256 MiB of gathered rows.  One 4-byte copy and a stream sync per later attempt.
+int bpl_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
+               uint32_t *d_flags, uint32_t *d_iters, uint32_t *d_graph, uint32_t *d_total)
+{
+    if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B == 0) return POLAR_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the host reads the count of open frames
+    const int P = (int)c->bpl_ident.size(), N = c->cfg.N, NW = c->NW;
+    const bool crc = c->cfg.crc_r > 0, direct = c->bpl_ident[0] != 0;
+    const uint32_t need = POLAR_FLAG_BP_CONVERGED | (crc ? POLAR_FLAG_CRC_PASS : 0u);
+    const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
+    const size_t CH = chunk_rows(B, row);
+    int rc;
+    // every buffer of the call, before its first launch
+    if ((rc = ensure(c, c->bpl_siters, B * sizeof(uint32_t)))) return rc;
+    if (!d_flags && (P > 1 || crc || d_graph || d_total)) {
+        if ((rc = ensure(c, c->ad_flags, B * sizeof(uint32_t)))) return rc;
+        d_flags = (uint32_t *)c->ad_flags.p;
+    }
+    if (P > 1 || !direct) {
+        for (Buf *b : {&c->ad_idx[0], &c->ad_idx[1], &c->ad_sflags})
+            if ((rc = ensure(c, *b, B * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(c, c->ad_in, CH * row))) return rc;
+        if ((rc = ensure(c, c->ad_bits, CH * NW * sizeof(uint32_t)))) return rc;
+    }
+    if (d_pm) HIP_TRY(c, hipMemsetAsync(d_pm, 0, B * sizeof(double), c->stream));
+    uint32_t *siters = (uint32_t *)c->bpl_siters.p, *sflags = (uint32_t *)c->ad_sflags.p, *sbits = (uint32_t *)c->ad_bits.p;
+    auto tables = [&](int p, const uint16_t **sig, const uint16_t **sinv, const uint32_t **fz, const uint32_t **tab) {
+        const bool id = c->bpl_ident[(size_t)p] != 0;
+        *sig = id ? nullptr : c->d_bpl_sigma + (size_t)p * N;
+        *sinv = id ? nullptr : c->d_bpl_sinv + (size_t)p * N;
+        *fz = c->d_bpl_frozen + (size_t)p * NW;
+        *tab = crc ? c->d_bpl_crc + (size_t)p * N : nullptr;
+    };
+    // one chunk of attempt p through the staging buffers: frames idx[0..nc), or base .. base + nc when idx is null
+    auto staged = [&](int p, const uint32_t *idx, size_t base, size_t nc, uint32_t *fl, uint32_t *it) -> int {
+        const uint16_t *sig, *sinv;
+        const uint32_t *fz, *tab;
+        tables(p, &sig, &sinv, &fz, &tab);
+        int r;
+        if ((r = polar_tu::bpl_gather(c, d_in, in_is_f32 != 0, c->ad_in.p, idx, base, sig, nc))) return r;
+        if ((r = decode_fixed(c, c->ad_in.p, in_is_f32, sigma, nc, sbits, nullptr, fl, fz, it))) return r;
+        if (crc && (r = polar_tu::ad_crc_check(c, sbits, tab, fl, nc))) return r;
+        return polar_tu::bpl_scatter(c, sbits, it, fl, idx, base, nc, sinv, need, p, P, p == 0, d_bits, d_iters, d_flags,
+                                     d_graph, d_total);
+    };
+    const uint32_t *cur_flags;
+    if (direct) {
+        uint32_t *it0 = d_iters ? d_iters : siters;
+        if ((rc = decode_fixed(c, d_in, in_is_f32, sigma, B, d_bits, nullptr, d_flags, c->d_bpl_frozen, it0))) return rc;
+        if (crc && (rc = polar_tu::ad_crc_check(c, d_bits, c->d_bpl_crc, d_flags, B))) return rc;
+        if ((d_graph || d_total) &&
+            (rc = polar_tu::bpl_scatter(c, nullptr, it0, d_flags, nullptr, 0, B, nullptr, need, 0, P, true, d_bits, it0, d_flags,
+                                        d_graph, d_total)))
+            return rc;
+        cur_flags = d_flags;
+    } else {
+        for (size_t off = 0; off < B; off += CH)
+            if ((rc = staged(0, nullptr, off, std::min(CH, B - off), sflags + off, siters + off))) return rc;
+        cur_flags = sflags;
+    }
+    const uint32_t *cur_idx = nullptr;
+    size_t n = B;
+    for (int p = 1; p < P; ++p) {
+        uint32_t *idx = (uint32_t *)c->ad_idx[(p - 1) & 1].p;
+        if ((rc = polar_tu::ad_compact(c, cur_flags, cur_idx, n, need, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p)))
+            return rc;
+        uint32_t h = 0;
+        HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        n = h;
+        if (n == 0) break;
+        for (size_t off = 0; off < n; off += CH)
+            if ((rc = staged(p, idx + off, 0, std::min(CH, n - off), sflags + off, siters + off))) return rc;
+        cur_idx = idx;
+        cur_flags = sflags;
+    }
+    return POLAR_OK;
+}
+
 // SCAN (POLAR_ALGO_SCAN, include/polar_hip.h): one launch of k_scan_lanes, no host read-back.  Every output is nullable
 // here: the soft-output entry point may ask for LLRs only.
 int scan_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
@@ -465,10 +556,12 @@ int scan_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, siz
 
 // the decoder of ctx c on N-wide rows: the fixed decoder, or for a CA-SCL ctx with a stage rule the adaptive one, or SC-Flip.
 // d_iters: BP round trips per frame; CA-SCL: the list size that decided each frame; SC-Flip: the attempt that decided it.
+// d_graph, d_total: BP list decoding only.
 int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                         double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters, void *d_llr_u = nullptr,
-                        void *d_ext_x = nullptr)
+                        void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr)
 {
+    if (c && c->cfg.algo == POLAR_ALGO_BPL) return bpl_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters, d_graph, d_total);
     if (c && c->cfg.algo == POLAR_ALGO_SCAN) return scan_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_llr_u, d_ext_x);
     if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
     if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
@@ -486,10 +579,11 @@ int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double si
 // (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (it is part of the lane, polar_host.h).
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr,
-                       void *d_llr_u = nullptr, void *d_ext_x = nullptr)
+                       void *d_llr_u = nullptr, void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr)
 {
     if (!c || c->rm_mode == POLAR_RM_NONE)
-        return decode_device_plain(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters, d_llr_u, d_ext_x);
+        return decode_device_plain(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters, d_llr_u, d_ext_x,
+                                   d_graph, d_total);
     const size_t esz = in_is_f32 ? 4 : 8;
     const bool scan = c->cfg.algo == POLAR_ALGO_SCAN;   // its three outputs are nullable
     const size_t soft_row = (size_t)c->cfg.N * (c->cfg.dtype == POLAR_F32 ? 4 : 8);
@@ -507,7 +601,8 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
         if ((rc = decode_device_plain(c, c->rm_rows.p, in_is_f32, 0.0, nc, d_bits ? d_bits + off * (size_t)c->NW : nullptr,
                                       d_pm ? d_pm + off : nullptr, d_flags ? d_flags + off : nullptr, d_frozen,
                                       d_iters ? d_iters + off : nullptr, d_llr_u ? (char *)d_llr_u + off * soft_row : nullptr,
-                                      d_ext_x ? (char *)d_ext_x + off * soft_row : nullptr)))
+                                      d_ext_x ? (char *)d_ext_x + off * soft_row : nullptr, d_graph ? d_graph + off : nullptr,
+                                      d_total ? d_total + off : nullptr)))
             return rc;
     }
     return POLAR_OK;
@@ -544,6 +639,11 @@ void refresh_kernel_name(polar_ctx *c)
         snprintf(nm, sizeof nm, "k_scf_lanes<%s> (SC-Flip, T=%d; pass A, k_ad_fail_count/scan/write, record, pass B, k_scf_resolve)",
                  ty, c->scf_T);
     if (g.algo == POLAR_ALGO_SCAN) snprintf(nm, sizeof nm, "k_scan_lanes<%s> (SCAN, I=%d)", ty, c->scan_I);
+    if (g.algo == POLAR_ALGO_BPL) {
+        const std::string bp = nm;
+        snprintf(nm, sizeof nm, "%s x %d graphs%s; glue k_bpl_gather, k_bpl_scatter", bp.c_str(), (int)c->bpl_ident.size(),
+                 g.crc_r > 0 ? " (CRC-aided)" : "");
+    }
     if (g.dtype == POLAR_Q8) snprintf(nm, sizeof nm, "k_scl_q8<L=%d>", g.L);   // one kernel for SC / SCL / CA-SCL and every shape
     c->kernel_name = nm;
     if (!c->cascl_stages.empty()) {
@@ -591,7 +691,8 @@ void unpack_words(const uint32_t *w, int NW, int *out)
 // helper threads per direction of the host pipeline (staging of the caller's rows / unpacking of the decisions)
 constexpr unsigned HOST_THREADS = 6;   // 4 -> 6: end_to_end 4.4 -> 4.6-4.7 M frames/s; 8 and 12 no more (run 35)
 int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char *frozen_mask, size_t B,
-               int *u_hat, double *pm_out, unsigned *flags, unsigned *iters = nullptr)
+               int *u_hat, double *pm_out, unsigned *flags, unsigned *iters = nullptr, unsigned *graph = nullptr,
+               unsigned *total = nullptr)
 {
     if (!c || !in || !u_hat) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
@@ -612,6 +713,8 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     if ((rc = ensure(c, c->pm, B * sizeof(double)))) return rc;
     if ((rc = ensure(c, c->flags, B * sizeof(uint32_t)))) return rc;
     if (iters && (rc = ensure(c, c->bp_iters, B * sizeof(uint32_t)))) return rc;
+    if (graph && (rc = ensure(c, c->bpl_graph, B * sizeof(uint32_t)))) return rc;
+    if (total && (rc = ensure(c, c->bpl_total, B * sizeof(uint32_t)))) return rc;
     // Chunked pipeline: while chunk k is decoded, chunk k+1 crosses PCIe on a second stream and the decisions of
     // chunk k-1 are unpacked to the caller's int array by helper threads.  The input is pageable caller memory: a
     // hipMemcpyAsync from it is a single-threaded staging copy inside the runtime (about 18 GB/s) that blocks this thread.
@@ -713,7 +816,9 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         // h_bits[s] / bits2[s] were last used by chunk k-2, whose unpacking ran during the copy above
         if (worker.joinable()) worker.join();
         rc = decode_device_impl(c, c->in2[s].p, 0, sigma, nf, (uint32_t *)c->bits2[s].p, (double *)c->pm.p + f0,
-                                (uint32_t *)c->flags.p + f0, d_frozen, iters ? (uint32_t *)c->bp_iters.p + f0 : nullptr);
+                                (uint32_t *)c->flags.p + f0, d_frozen, iters ? (uint32_t *)c->bp_iters.p + f0 : nullptr, nullptr,
+                                nullptr, graph ? (uint32_t *)c->bpl_graph.p + f0 : nullptr,
+                                total ? (uint32_t *)c->bpl_total.p + f0 : nullptr);
         if (rc) return fail_join(rc);
         if (hipEventRecord(c->ev_free[s], c->stream) != hipSuccess) return fail_join(POLAR_EDEVICE);
         if (hipMemcpyAsync(c->h_bits[s], c->bits2[s].p, nf * NW * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) !=
@@ -731,8 +836,18 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     if (pm_out) HIP_TRY(c, hipMemcpyAsync(pm_out, c->pm.p, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (flags) HIP_TRY(c, hipMemcpyAsync(flags, c->flags.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (iters) HIP_TRY(c, hipMemcpyAsync(iters, c->bp_iters.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (graph) HIP_TRY(c, hipMemcpyAsync(graph, c->bpl_graph.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(c, hipMemcpyAsync(total, c->bpl_total.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return POLAR_OK;
+}
+
+// sigma_pi(j) = sum over b of ((j >> b) & 1) << pi[b] (include/polar_hip.h, BP list decoding)
+int bpl_sigma(const int *pi, int n, int j)
+{
+    int v = 0;
+    for (int b = 0; b < n; ++b) v |= ((j >> b) & 1) << pi[b];
+    return v;
 }
 
 }  // namespace
@@ -764,13 +879,16 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     const int N = cfg->N;
     if (N < 32 || N > 4096 || (N & (N - 1))) return POLAR_EINVAL;
     if (cfg->K < 1 || cfg->crc_r < 0 || cfg->crc_r > 32 || cfg->K + cfg->crc_r > N) return POLAR_EINVAL;
-    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCAN) return POLAR_EINVAL;
+    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_BPL) return POLAR_EINVAL;
     if (cfg->dtype != POLAR_F64 && cfg->dtype != POLAR_F32 && cfg->dtype != POLAR_Q8) return POLAR_EINVAL;
     int L = cfg->L;
-    if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF || cfg->algo == POLAR_ALGO_SCAN) L = 1;
+    if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF || cfg->algo == POLAR_ALGO_SCAN ||
+        cfg->algo == POLAR_ALGO_BPL)
+        L = 1;
     if (L < 1 || L > 32 || (L & (L - 1))) return POLAR_EINVAL;
-    if (has_crc(cfg->algo) && (cfg->crc_r < 1 || !cfg->crc_taps || cfg->n_taps < 2)) return POLAR_EINVAL;
-    if (cfg->algo == POLAR_ALGO_BP && cfg->bp_iters < 1) return POLAR_EINVAL;
+    const bool crc_optional = cfg->algo == POLAR_ALGO_BPL && cfg->crc_r == 0;   // BP list decoding: crc_r = 0 means none
+    if (has_crc(cfg->algo) && !crc_optional && (cfg->crc_r < 1 || !cfg->crc_taps || cfg->n_taps < 2)) return POLAR_EINVAL;
+    if ((cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_BPL) && cfg->bp_iters < 1) return POLAR_EINVAL;
     if (cfg->algo == POLAR_ALGO_SCF && N > 2048) return POLAR_ENOKERNEL;   // one codeword per lane: N <= 2048
     if (cfg->algo == POLAR_ALGO_SCAN && N > polar::SCAN_MAX_N) return POLAR_ENOKERNEL;
     // fixed-point min-sum: SC / SCL / CA-SCL up to N = 1024
@@ -862,6 +980,13 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     if (int rc = c->d_info.upload(iw.data(), (size_t)c->NW)) return cleanup(rc);
     if (r > 0)
         if (int rc = c->d_crc_tab.upload(c->h_crc_tab.data(), (size_t)N)) return cleanup(rc);
+    if (cfg->algo == POLAR_ALGO_BPL) {   // every attempt stops by rule G; the default list: min(n, 8) cyclic shifts
+        c->bp_stop = POLAR_BP_STOP_G;
+        const int P = std::min(c->n, 8);
+        std::vector<int> perms((size_t)P * c->n);
+        polar_bpl_cyclic_graphs(c->n, P, perms.data());
+        if (int rc = polar_bpl_set_graphs(c, perms.data(), P)) return cleanup(rc);
+    }
     refresh_kernel_name(c);
     *out = c;
     return POLAR_OK;
@@ -945,7 +1070,7 @@ int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out)
     *out = nullptr;
     if (cfg->info_order || (ibil != 0 && ibil != 1)) return POLAR_EINVAL;
     if (cfg->dtype == POLAR_Q8) return POLAR_EINVAL;   // no rate-matched fixed-point contexts
-    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_SCAN) return POLAR_EINVAL;
+    if (cfg->algo < POLAR_ALGO_SC || cfg->algo > POLAR_ALGO_BPL) return POLAR_EINVAL;
     const int r = has_crc(cfg->algo) ? cfg->crc_r : 0;
     if (cfg->K < 1 || r < 0 || r > 32) return POLAR_EINVAL;
     const int N = cfg->N, A = cfg->K + r;
@@ -1291,6 +1416,81 @@ int polar_scf_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_
     return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, nullptr, flags, attempts);
 }
 
+int polar_bpl_cyclic_graphs(int n, int P, int *out)
+{
+    if (n < 5 || n > 12 || P < 1 || P > 32 || !out) return POLAR_EINVAL;
+    for (int s = 0; s < P; ++s)
+        for (int b = 0; b < n; ++b) out[s * n + b] = (b + s) % n;
+    return POLAR_OK;
+}
+
+int polar_bpl_set_graphs(polar_ctx *c, const int *perms, int P)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BPL || !perms || P < 1 || P > 32) return POLAR_EINVAL;
+    const int n = c->n, N = c->cfg.N, NW = c->NW;
+    std::vector<unsigned char> ident((size_t)P, 1);
+    for (int p = 0; p < P; ++p) {
+        unsigned seen = 0;
+        for (int b = 0; b < n; ++b) {
+            const int v = perms[p * n + b];
+            if (v < 0 || v >= n || ((seen >> v) & 1u)) return POLAR_EINVAL;
+            seen |= 1u << v;
+            if (v != b) ident[(size_t)p] = 0;
+        }
+    }
+    const bool crc = c->cfg.crc_r > 0;
+    std::vector<uint16_t> sig((size_t)P * N), sinv((size_t)P * N);
+    std::vector<uint32_t> fz((size_t)P * NW, 0u), tab(crc ? (size_t)P * N : 0);
+    for (int p = 0; p < P; ++p)
+        for (int j = 0; j < N; ++j) {
+            const int t = bpl_sigma(perms + p * n, n, j);
+            sig[(size_t)p * N + j] = (uint16_t)t;
+            sinv[(size_t)p * N + t] = (uint16_t)j;
+            if (c->frozen[(size_t)t]) fz[(size_t)p * NW + (j >> 5)] |= 1u << (j & 31);
+            if (crc) tab[(size_t)p * N + j] = c->h_crc_tab[(size_t)t];
+        }
+    DeviceGuard guard(c->cfg.device);
+    DevMem<uint16_t> d_sig, d_sinv;
+    DevMem<uint32_t> d_fz, d_tab;
+    int rc;
+    if ((rc = d_sig.upload(sig.data(), sig.size())) || (rc = d_sinv.upload(sinv.data(), sinv.size())) ||
+        (rc = d_fz.upload(fz.data(), fz.size())) || (crc && (rc = d_tab.upload(tab.data(), tab.size()))))
+        return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // no queued decode still reads the old tables
+    c->d_bpl_sigma = std::move(d_sig);
+    c->d_bpl_sinv = std::move(d_sinv);
+    c->d_bpl_frozen = std::move(d_fz);
+    c->d_bpl_crc = std::move(d_tab);
+    c->bpl_perms.assign(perms, perms + (size_t)P * n);
+    c->bpl_ident = ident;
+    refresh_kernel_name(c);
+    return POLAR_OK;
+}
+
+int polar_bpl_get_graphs(const polar_ctx *c, int *P, int *perms)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BPL) return POLAR_EINVAL;
+    if (P) *P = (int)c->bpl_ident.size();
+    if (perms) std::copy(c->bpl_perms.begin(), c->bpl_perms.end(), perms);
+    return POLAR_OK;
+}
+
+int polar_bpl_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                            uint32_t *d_iters, uint32_t *d_flags, uint32_t *d_graph, uint32_t *d_total_iters)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BPL) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, nullptr, d_flags, c->d_frozen, d_iters, nullptr, nullptr,
+                              d_graph, d_total_iters);
+}
+
+int polar_bpl_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, unsigned *iters, unsigned *flags,
+                           unsigned *graph, unsigned *total_iters)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_BPL) return POLAR_EINVAL;
+    return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, nullptr, flags, iters, graph, total_iters);
+}
+
 int polar_scan_set_iters(polar_ctx *c, int I)
 {
     if (!c || c->cfg.algo != POLAR_ALGO_SCAN || I < 1 || I > polar::SCAN_MAX_ITERS) return POLAR_EINVAL;
@@ -1597,8 +1797,8 @@ static int fer_batch_impl(polar_ctx *c, unsigned long long seed, unsigned long l
     // pass of its decode overlap the other half's decode.  Frame i of the batch is the same frame either way
     // (the generator is counter-based), and the two counters are atomics.
     // (not with an adaptive CA-SCL rule: its stage buffers belong to one stream and it syncs between stages)
-    // (nor for SC-Flip, for the same reasons)
-    const size_t half = (B >= 32768 && c->cascl_stages.empty() && c->cfg.algo != POLAR_ALGO_SCF) ? (B / 2 + 63) / 64 * 64 : B;
+    // (nor for SC-Flip and BP list decoding, for the same reasons)
+    const size_t half = (B >= 32768 && c->cascl_stages.empty() && c->cfg.algo != POLAR_ALGO_SCF && c->cfg.algo != POLAR_ALGO_BPL) ? (B / 2 + 63) / 64 * 64 : B;
     if (half < B && !c->lane_b.stream) {
         HIP_TRY(c, c->lane_b.stream.create(hipStreamNonBlocking));
         HIP_TRY(c, c->ev_b.create(hipEventDisableTiming));
@@ -1808,7 +2008,7 @@ int polar_set_systematic(polar_ctx *c, int on)
     if (!c || (on != 0 && on != 1)) return POLAR_EINVAL;
     if ((on != 0) == c->sys_polar) return POLAR_OK;
     if (on) {
-        if (c->is_dyn || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8) return POLAR_EINVAL;
+        if (c->is_dyn || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || c->cfg.algo == POLAR_ALGO_BPL) return POLAR_EINVAL;
         if (polar_systematic_check(c->cfg.N, c->info_order.data(), c->A) != 1) return POLAR_EINVAL;
     }
     DeviceGuard guard(c->cfg.device);

@@ -68,6 +68,16 @@ struct polar_ctx : Lane {
     // SC-Flip (POLAR_ALGO_SCF): flip budget T (polar_scf_set_flips), the failing frames' flip positions, pass B's pairs
     int scf_T = 8;
     Buf scf_flips, scf_pass, scf_bits;
+    // BP list decoding (POLAR_ALGO_BPL): the graphs pi_p[b] (polar_bpl_set_graphs), per graph whether it is the identity,
+    // and on the device sigma_p, its inverse, the permuted frozen masks and (with a CRC) the permuted CRC tables; the
+    // attempts' round trips per open frame, and graph / total_iters of the host-pointer entry points.  The open-frame lists
+    // and the gathered rows are the ad_* buffers above
+    std::vector<int> bpl_perms;           // [P][n]
+    std::vector<unsigned char> bpl_ident; // [P]
+    DevMem<uint16_t> d_bpl_sigma, d_bpl_sinv;   // [P][N]
+    DevMem<uint32_t> d_bpl_frozen;        // [P][NW]
+    DevMem<uint32_t> d_bpl_crc;           // [P][N] or empty
+    Buf bpl_siters, bpl_graph, bpl_total;
     int scan_I = 4;                       // SCAN (POLAR_ALGO_SCAN): iterations (polar_scan_set_iters)
     Buf scan_llr, scan_ext;               // polar_scan_decode_batch: staging of the soft outputs
     // 5G rate matching (polar_create_rm): E, POLAR_RM_* mode (POLAR_RM_NONE: a plain ctx), channel interleaver, its tables
@@ -250,13 +260,19 @@ enum { BP_R4, BP_W128, BP_PLAIN };   // bp()'s kernel for this ctx: k_bp_r4, k_b
 int bp_variant(const polar_ctx *c);                                                        // k_bp.hip
 int bp_readout(polar_ctx *c, const polar::BpReadoutParams &P, bool r32, bool in32);        // k_bp.hip
 // k_adaptive.hip: the glue of the adaptive CA-SCL decoder (adaptive_kernel.h)
-int ad_crc_check(polar_ctx *c, const uint32_t *d_bits, uint32_t *d_flags, size_t B);      // CRC syndrome of SC decisions
+int ad_crc_check(polar_ctx *c, const uint32_t *d_bits, const uint32_t *d_crc_tab, uint32_t *d_flags, size_t B);   // CRC syndrome of packed decisions
 size_t ad_blocks(size_t n);                                                               // compaction blocks for n frames
-int ad_compact(polar_ctx *c, const uint32_t *d_flags, const uint32_t *d_idx_in, size_t n, uint32_t *d_blk,
-               uint32_t *d_idx_out, uint32_t *d_count);                                   // d_blk: 2 * ad_blocks(n) words
+int ad_compact(polar_ctx *c, const uint32_t *d_flags, const uint32_t *d_idx_in, size_t n, uint32_t need, uint32_t *d_blk,
+               uint32_t *d_idx_out, uint32_t *d_count);   // frames with (flags & need) != need; d_blk: 2 * ad_blocks(n) words
 int ad_gather(polar_ctx *c, const void *d_src, void *d_dst, const uint32_t *d_idx, size_t n, size_t row_bytes);
 int ad_scatter(polar_ctx *c, const uint32_t *s_bits, const double *s_pm, const uint32_t *s_flags, const uint32_t *d_idx,
                size_t n, uint32_t *d_bits, double *d_pm, uint32_t *d_flags, uint32_t *d_list, int L);
+// k_bpl.hip: the glue of the BP list decoder (bpl_kernel.h)
+int bpl_gather(polar_ctx *c, const void *d_src, bool in32, void *d_dst, const uint32_t *d_idx, size_t base,
+               const uint16_t *d_sigma, size_t n);
+int bpl_scatter(polar_ctx *c, const uint32_t *s_bits, const uint32_t *s_iters, const uint32_t *s_flags, const uint32_t *d_idx,
+                size_t base, size_t n, const uint16_t *d_sinv, uint32_t need, int p, int P, bool all, uint32_t *d_bits,
+                uint32_t *d_iters, uint32_t *d_flags, uint32_t *d_graph, uint32_t *d_total);
 // k_scf.hip: SC-Flip (scf_lanes.h); mode = polar::SCF_CHECK | SCF_RECORD | SCF_FLIP
 int scf_lanes(polar_ctx *c, const polar::ScfParams &P, int mode, bool r32, bool in32);
 int scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, const uint32_t *d_idx, size_t n, int T,

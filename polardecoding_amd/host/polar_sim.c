@@ -209,13 +209,15 @@ static int construct_order(int N, int dtype, long long frames, double sigma, uin
 
 static void usage(void)
 {
-    fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf|scan --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
+    fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf|scan|bpl --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
                     "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32|q8 [--quant scale,qc,qi]] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
                     "                 [--quant s,qc,qi]   (--dtype q8, fixed-point min-sum sc|scl|cascl: LLR scale, channel and internal bits; default 2,8,8)\n"
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
                     "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n"
                     "                 [--iters I]   (scan: soft-output SCAN with I iterations, 1..64; default 4)\n"
+                    "                 [--graphs P]   (bpl: BP list decoding on the first P cyclic shifts of the stage order, 1..32; default min(n, 8);\n"
+                    "                                  --bp-iters per attempt; --crc 24c|6: CRC-aided, without it no CRC)\n"
                     "                 [--construct frames --design-snr db [--q-out file]]   (Monte-Carlo construction of the order on the device first;\n"
                     "                                  --q-out: write it in the format --q reads)\n"
                     "                 [--sys-polar]   (--fast only: systematic polar code, polar_set_systematic; errors are counted on the codeword's information positions)\n"
@@ -230,6 +232,7 @@ int main(int argc, char **argv)
     int stages[6], nstages = 0;   /* --stages: polar_cascl_set_stages */
     int flips = -1;               /* --flips: polar_scf_set_flips (-1: the library's default) */
     int scan_iters = -1;          /* --iters: polar_scan_set_iters (-1: the library's default) */
+    int graphs = -1;              /* --graphs: polar_bpl_set_graphs with P cyclic shifts (-1: the library's default list) */
     int rm_E = 0, rm_ibil = 0;    /* --E / --ibil: polar_create_rm (0: no rate matching) */
     int sys_polar = 0;            /* --sys-polar: polar_set_systematic */
     double q8_scale = 0;          /* --quant: polar_q8_set_quant (0: the library's default) */
@@ -250,7 +253,8 @@ int main(int argc, char **argv)
             if (!strcmp(v, "bpr")) { bpr = 1; v = "bp"; bp_iters = 90; }   /* BPr_128.c: iterMax 90 (:16) */
             algo = !strcmp(v, "sc") ? POLAR_ALGO_SC : !strcmp(v, "bp") ? POLAR_ALGO_BP
                  : !strcmp(v, "scl") ? POLAR_ALGO_SCL : !strcmp(v, "cascl") ? POLAR_ALGO_CASCL
-                 : !strcmp(v, "scf") ? POLAR_ALGO_SCF : !strcmp(v, "scan") ? POLAR_ALGO_SCAN : -1;
+                 : !strcmp(v, "scf") ? POLAR_ALGO_SCF : !strcmp(v, "scan") ? POLAR_ALGO_SCAN
+                 : !strcmp(v, "bpl") ? POLAR_ALGO_BPL : -1;
             if (algo < 0) usage();
             i++;
         } else if (!strcmp(a, "--N") && v) { N = atoi(v); i++; }
@@ -302,6 +306,12 @@ int main(int argc, char **argv)
             if (end == v || *end || scan_iters < 0) usage();
             i++;
         }
+        else if (!strcmp(a, "--graphs") && v) {
+            char *end;
+            graphs = (int)strtol(v, &end, 10);
+            if (end == v || *end || graphs < 0) usage();
+            i++;
+        }
         else if (!strcmp(a, "--dtype") && v) { dtype = !strcmp(v, "f32") ? POLAR_F32 : !strcmp(v, "q8") ? POLAR_Q8 : POLAR_F64; i++; }
         else if (!strcmp(a, "--quant") && v) {   /* polar_q8_set_quant */
             if (sscanf(v, "%lf,%d,%d", &q8_scale, &q8_qc, &q8_qi) != 3 || !(q8_scale > 0)) usage();
@@ -329,7 +339,9 @@ int main(int argc, char **argv)
     c.N = N; c.K = K;
     polar_crc_matrix gcm;
     memset(&gcm, 0, sizeof gcm);
-    const int with_crc = algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF;
+    /* BP list decoding: a CRC only when --crc names one */
+    const int with_crc = algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF || (algo == POLAR_ALGO_BPL && crc);
+    if (algo == POLAR_ALGO_BPL && crcfile) { fprintf(stderr, "--crc-file: not with --algo bpl\n"); return 1; }
     if (with_crc && crcfile) {
         /* g(D) and r come from the generator-matrix file (the reference's CRC_6.dat, or Gc of CASCL_1024_sys.c:48-561 as
            a file); the library has checked that every row is D^(r+i) mod g */
@@ -448,6 +460,17 @@ int main(int argc, char **argv)
         if (fast && gpus > 1) { fprintf(stderr, "--iters: not with --gpus > 1\n"); return 1; }
         if ((rc = polar_scan_set_iters(ctx, scan_iters)) != 0) { fprintf(stderr, "--iters: %s\n", polar_strerror(rc)); return 1; }
     }
+    if (graphs >= 0) {
+        /* a polar_group builds its contexts from cfg and runs the default list */
+        if (algo != POLAR_ALGO_BPL) { fprintf(stderr, "--graphs: only with --algo bpl\n"); return 1; }
+        if (fast && gpus > 1) { fprintf(stderr, "--graphs: not with --gpus > 1\n"); return 1; }
+        int nlog = 0, perms[32 * 12];
+        while ((1 << nlog) < N) nlog++;
+        if ((rc = polar_bpl_cyclic_graphs(nlog, graphs, perms)) != 0 || (rc = polar_bpl_set_graphs(ctx, perms, graphs)) != 0) {
+            fprintf(stderr, "--graphs: %s\n", polar_strerror(rc));
+            return 1;
+        }
+    }
     /* the library built the frozen set from the 5G sequence like the reference (I[i] = Q[N-(K+r)+i]);
        the encoder needs the same I[] */
     c.I = (int *)malloc(sizeof(int) * (size_t)c.A);
@@ -555,7 +578,8 @@ int main(int argc, char **argv)
             }
             printf("BLER = %lfe-2\tBER = %lfe-2\tK * BER = %lf\n", (double)errblock * 100 / run,
                    (double)errbit * 100 / K / run, (double)errbit / run);
-        } else if (algo == POLAR_ALGO_SC || algo == POLAR_ALGO_BP || algo == POLAR_ALGO_SCAN || (algo == POLAR_ALGO_SCF && !c.sys)) {
+        } else if (algo == POLAR_ALGO_SC || algo == POLAR_ALGO_BP || algo == POLAR_ALGO_SCAN ||
+                   ((algo == POLAR_ALGO_SCF || algo == POLAR_ALGO_BPL) && !c.sys)) {
             printf("bSNR = %.2lf\terror block = %d\trun = %ld\tBLER = %lf\n", db, errblock, run, (double)errblock / run);
             printf("Error bit = %ld\tBER = %lf\n", errbit, (double)errbit / K / run);
         } else if (c.sys) { /* CASCL_1024_sys.c:832-835 */
