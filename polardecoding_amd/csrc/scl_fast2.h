@@ -383,25 +383,28 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     // levels >= 5 (words in LDS); cur = the 32 level-5 partial sums that end at leaf j, j = 31 mod 32
     __device__ __forceinline__ void set_bit_lds(int j, uint32_t cur)
     {
+        // the slot's row offset is recomputed here (one instruction) rather than kept across the frame loop: as a
+        // loop invariant it was spilled and re-loaded from the stack at every carry step
+        const int row = (int)fresh((unsigned)(p * NW));
         lds_fence();
-        if (pos == 0) curw[p * NW] = cur;
+        if (pos == 0) curw[row] = cur;
         lds_fence();
         int t = 5;
         while (t < 10 && ((j >> t) & 1)) {
             const int nw = 1 << (t - 5);
             const int sb = pb(t);
             for (int w = pos; w < nw; w += 4) {
-                const uint32_t cc = curw[p * NW + w];
+                const uint32_t cc = curw[row + w];
                 const uint32_t l = blw[sb * NW + nw + w];
-                curw[p * NW + w] = l ^ cc;
-                curw[p * NW + w + nw] = cc;
+                curw[row + w] = l ^ cc;
+                curw[row + w + nw] = cc;
             }
             lds_fence();
             ++t;
         }
         if (t < 10) {
             const int nw = 1 << (t - 5);
-            for (int w = pos; w < nw; w += 4) blw[p * NW + nw + w] = curw[p * NW + w];
+            for (int w = pos; w < nw; w += 4) blw[row + nw + w] = curw[row + w];
             set_pb(t, p);
             lds_fence();
         }
@@ -483,74 +486,87 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     static __device__ __forceinline__ uint32_t sign_bit(float x) { return (uint32_t)__float_as_int(x) >> 31; }
 
     // ---- decision at leaf j = 8o + K; lambda valid at pos 0 ----
-    template <int K>
-    __device__ __forceinline__ void decide(int o, bool frozen, R lam) { decide_t<K>(o, frozen, lam, lut.tabv(lam)); }
+    // FULL: the list is full (logact == 3: at and behind the third information leaf), known at compile time -- the code
+    // that fills the list, its metric select and its merge with the full-list paths do not exist in those instantiations
+    template <int K, bool FULL>
+    __device__ __forceinline__ void decide(int o, bool frozen, R lam) { decide_t<K, FULL>(o, frozen, lam, lut.tabv(lam)); }
     // tt = T(|lambda|) (SCL_1024.c:352-359), looked up by the caller -- or, at the odd leaves, a by-product of the
     // check node that produced the even leaf's lambda (see octet())
-    template <int K>
+    template <int K, bool FULL>
     __device__ __forceinline__ void decide_t(int o, bool frozen, R lam, R tt)
     {
-        const int j = 8 * o + K;
-        uint32_t crcw = 0;
-        if (CRC_ON) crcw = crct[j];   // the table holds 0 for frozen leaves (make_crc_table): no branch around the read
-        uint32_t bit = 0;
+        // The exits of a leaf share no merged state beyond what each of them writes.  A frozen leaf touches PM and bl0
+        // and is done.  At an information leaf the outcome of the trivial prune (bit, metric) is computed in front of
+        // the prune test and the ranked path is an `if` without `else` that overrides it: the values a fork permutes
+        // (ptr, crc, bl0, A[1..3], a1, bp_d, bp_td) have the fork block as their only writer, so where the paths meet
+        // they merge with the unchanged registers and not with copies made on the trivial side.  (With `if (trivial)
+        // ... else ...` the structurised merge took every such value through a second register set: 13-17 moves on
+        // the trivial exit, and as many back where the frozen exit joins; profiles/r15_ab.txt.)
         if (frozen) {
             PM += tt + negmax(lam);  // PHI(.,0)
-        } else {
-            if (logact < 3) {
-                const R ph0 = tt + negmax(lam), ph1 = tt + posmax(lam);  // PHI(.,0), PHI(.,1)
-                bit = (p >> logact) & 1;
-                PM += bit ? ph1 : ph0;
-                ++logact;
-            } else {
-                // PHI of the branch lambda favours is T(|lambda|), of the other one T(|lambda|) + |lambda|
-                // (SCL_1024.c:481-502; T + 0 is T, so these ARE c0 / c1 in the order the sign of lambda says).
-                const uint32_t lneg = sign_bit(lam);   // lambda = +-0: cb == cw, never trivial, c0 == c1 below
-                const R cb = PM + tt, cw = PM + (tt + absr(lam));
-                // Most information leaves (85 % at 1-3 dB) prune trivially: every path keeps its favoured branch.
-                // That is certain when the largest of the eight favoured keys is below the smallest of the eight
-                // others (the 8 favoured candidates are then the 8 smallest of the 16, all strictly below the median
-                // of SCL_1024.c:619-633), and three max/min steps over the path lanes show it -- without the key
-                // exchange through LDS, the rank network and the fork bookkeeping.  Both codewords must qualify.
-                if (trivial_prune(cb, cw)) {
-                    bit = (uint32_t)dpp_i<0x00>((int)lneg);   // quad_perm [0,0,0,0]: pos 0 holds lambda
-                    PM = cb;
-                } else {
-                    const R c0 = lneg ? cw : cb, c1 = lneg ? cb : cw;
-                    const uint32_t mask = survivors(c0, c1);
-                    const uint32_t m0 = mask & 0xFFu, m1 = mask >> 8;
-                    const uint32_t m_both = m0 & m1, m_dead = ~(m0 | m1) & 0xFFu;
-                    if (__popc(mask) < L) fl |= 0x1u;  // median tie in this lane's codeword
-                    const bool s0 = (m0 >> p) & 1, s1 = (m1 >> p) & 1;
-                    if (__ballot(m_dead != 0u) == 0ull) {
-                        bit = (!s0 && s1) ? 1u : 0u;  // no codeword forks: every slot keeps exactly one branch
-                        PM = bit ? c1 : c0;
-                    } else {
-                        // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661), per codeword
-                        const bool dead = !s0 && !s1;
-                        const int myrank = __popc(m_dead & ((1u << p) - 1u));
-                        const bool refilled = dead && (myrank < __popc(m_both));
-                        const int sg = refilled ? (int)kth[m_both * 8 + myrank] : p;
-                        const int sl = sg * 8 + gl;
-                        const R c1s = __shfl(c1, sl);
-                        ptr = __shfl(ptr, sl);
-                        crc = __shfl(crc, sl);
-                        bl0 = __shfl(bl0, sl);
-                        // what the lower-node steps still to come in this octet read: the sum / difference pairs of the
-                        // check nodes above them (octet())
-                        if constexpr ((K & 4) == 0) { A[2] = __shfl(A[2], sl); A[3] = __shfl(A[3], sl); }  // s2, d2: g at level 2 (leaf 4)
-                        if constexpr ((K & 2) == 0) { A[1] = __shfl(A[1], sl); a1 = __shfl(a1, sl); }       // s1, d1: g at level 1
-                        if constexpr ((K & 1) == 0) { bp_d = __shfl(bp_d, sl); bp_td = __shfl(bp_td, sl); } // a forked copy continues with bit 1: -d0, T(|d0|)
-                        if (refilled) { bit = 1; PM = c1s; }
-                        else if (s0) { bit = 0; PM = c0; }
-                        else if (s1) { bit = 1; PM = c1; }
-                        else { bit = 0; PM = c0; }  // tie rule: un-refilled dead slot continues as its 0-branch
-                    }
-                }
-            }
-            if (CRC_ON) crc ^= bit ? crcw : 0u;
+            set_bit_k<K>(o, 0u);
+            return;
         }
+        uint32_t crcw = 0;
+        if (CRC_ON) crcw = crct[8 * o + K];
+        uint32_t bit;
+        R pm;
+        if (!FULL && logact < 3) {
+            const R ph0 = tt + negmax(lam), ph1 = tt + posmax(lam);  // PHI(.,0), PHI(.,1)
+            bit = (p >> logact) & 1;
+            pm = PM + (bit ? ph1 : ph0);
+            ++logact;
+        } else {
+            // PHI of the branch lambda favours is T(|lambda|), of the other one T(|lambda|) + |lambda|
+            // (SCL_1024.c:481-502; T + 0 is T, so these ARE c0 / c1 in the order the sign of lambda says).
+            const uint32_t lneg = sign_bit(lam);   // lambda = +-0: cb == cw, never trivial, c0 == c1 below
+            const R cb = PM + tt, cw = PM + (tt + absr(lam));
+            // Most information leaves (85 % at 1-3 dB) prune trivially: every path keeps its favoured branch.
+            // That is certain when the largest of the eight favoured keys is below the smallest of the eight
+            // others (the 8 favoured candidates are then the 8 smallest of the 16, all strictly below the median
+            // of SCL_1024.c:619-633), and three max/min steps over the path lanes show it -- without the key
+            // exchange through LDS, the rank network and the fork bookkeeping.  Both codewords must qualify.
+            bit = (uint32_t)dpp_i<0x00>((int)lneg);   // quad_perm [0,0,0,0]: pos 0 holds lambda
+            pm = cb;
+            if (!trivial_prune(cb, cw)) ranked<K>(lneg, cb, cw, bit, pm);
+        }
+        PM = pm;
+        if (CRC_ON) crc ^= bit ? crcw : 0u;
         set_bit_k<K>(o, bit);
+    }
+    // the leaf's decision by ranking the 16 candidates; bit / pm come in as the trivial outcome and leave as the ranked one
+    template <int K>
+    __device__ __forceinline__ void ranked(uint32_t lneg, R cb, R cw, uint32_t &bit, R &pm)
+    {
+        const R c0 = lneg ? cw : cb, c1 = lneg ? cb : cw;
+        const uint32_t mask = survivors(c0, c1);
+        const uint32_t m0 = mask & 0xFFu, m1 = mask >> 8;
+        const uint32_t m_both = m0 & m1, m_dead = ~(m0 | m1) & 0xFFu;
+        if (__popc(mask) < L) fl |= 0x1u;  // median tie in this lane's codeword
+        const bool s0 = (m0 >> p) & 1, s1 = (m1 >> p) & 1;
+        // a slot keeps its surviving branch; one with both keeps 0 (its 1-branch moves to a dead slot); tie rule: a dead
+        // slot that is not refilled continues as its 0-branch
+        bit = (!s0 && s1) ? 1u : 0u;
+        pm = bit ? c1 : c0;
+        if (__ballot(m_dead != 0u) == 0ull) return;  // no codeword forks
+        // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661), per codeword
+        const bool dead = !s0 && !s1;
+        const int myrank = __popc(m_dead & ((1u << p) - 1u));
+        const bool refilled = dead && (myrank < __popc(m_both));
+        const int src = (int)kth[m_both * 8 + myrank];   // myrank <= 7: inside the table for every lane
+        const int sg = refilled ? src : p;
+        const int sl = sg * 8 + gl;
+        const R c1s = __shfl(c1, sl);
+        ptr = __shfl(ptr, sl);
+        crc = __shfl(crc, sl);
+        bl0 = __shfl(bl0, sl);
+        // what the lower-node steps still to come in this octet read: the sum / difference pairs of the
+        // check nodes above them (octet())
+        if constexpr ((K & 4) == 0) { A[2] = __shfl(A[2], sl); A[3] = __shfl(A[3], sl); }  // s2, d2: g at level 2 (leaf 4)
+        if constexpr ((K & 2) == 0) { A[1] = __shfl(A[1], sl); a1 = __shfl(a1, sl); }       // s1, d1: g at level 1
+        if constexpr ((K & 1) == 0) { bp_d = __shfl(bp_d, sl); bp_td = __shfl(bp_td, sl); } // a forked copy continues with bit 1: -d0, T(|d0|)
+        bit = refilled ? 1u : bit;
+        pm = refilled ? c1s : pm;
     }
 
     // ---- the leading run of P all-frozen octets (leaves 0 .. 8P-1; 1 <= P <= 15), instead of octets 0 .. P-1 ----
@@ -627,6 +643,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     }
 
     // ---- octets whose first seven leaves are frozen: breadth-first (all partner bits are 0) ----
+    template <bool FULL>
     __device__ __forceinline__ void octet_frozen_prefix(int o, bool last_frozen)
     {
         // level 2: f half (leaves 0..3) and g half (leaves 4..7), element pos each
@@ -659,7 +676,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             PM += quadp<0xFF>(pg);
             set_bit7(o, 0u);   // bits 1..7 of bl0 are 0 (above) and so is this one: c3 = 0
         } else {
-            decide<7>(o, false, quadp<0xFF>(lg));
+            decide<7, FULL>(o, false, quadp<0xFF>(lg));
         }
     }
 
@@ -689,18 +706,19 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)w, sh, 1);
         return Lut<R>::sel_mask(m, -dif, sum);
     }
-    template <int K>   // leaves K (even) and K + 1 from the level-1 pair in a1 (pos 0: x, pos 1: y)
+    template <int K, bool FULL>   // leaves K (even) and K + 1 from the level-1 pair in a1 (pos 0: x, pos 1: y)
     __device__ __forceinline__ void leaf_pair(int o, uint32_t fm, R x1)
     {
         const ChkBp q = chk_bp(x1, quadp<0xB1>(x1));
         bp_d = q.d;
         bp_td = q.td;
-        decide<K>(o, (fm >> K) & 1, q.v);
+        decide<K, FULL>(o, (fm >> K) & 1, q.v);
         // leaf K + 1: g0 with the bit just decided (bit 1 of bl0, set_bit_k<even>); a slot refilled by a fork took
         // bp_d / bp_td of its source and continues with bit 1, every other slot still has its own q.s / q.ts
         const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)bl0, 1, 1);
-        decide_t<K + 1>(o, (fm >> (K + 1)) & 1, Lut<R>::sel_mask(m1, -bp_d, q.s), Lut<R>::sel_mask(m1, bp_td, q.ts));
+        decide_t<K + 1, FULL>(o, (fm >> (K + 1)) & 1, Lut<R>::sel_mask(m1, -bp_d, q.s), Lut<R>::sel_mask(m1, bp_td, q.ts));
     }
+    template <bool FULL>
     __device__ __forceinline__ void octet(int o, uint32_t fm)
     {
         // level 2: f of (A[2], A[3]); its sum / difference stay in A[2], A[3] for the g step at leaf 4
@@ -715,9 +733,9 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             const R v1 = xor_sign(minabs(v2, y2), v2, y2) + (lut.tabv(s1) - lut.tabv(d1));
             A[1] = s1;
             a1 = d1;
-            leaf_pair<0>(o, fm, v1);
+            leaf_pair<0, FULL>(o, fm, v1);
         }
-        leaf_pair<2>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
+        leaf_pair<2, FULL>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
         {
             const R v2 = g_sel(A[2], A[3], bl0, 4 + pos);   // level 2, g
             const R y2 = quadp<0x4E>(v2);
@@ -725,11 +743,28 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             const R v1 = xor_sign(minabs(v2, y2), v2, y2) + (lut.tabv(s1) - lut.tabv(d1));
             A[1] = s1;
             a1 = d1;
-            leaf_pair<4>(o, fm, v1);
+            leaf_pair<4, FULL>(o, fm, v1);
         }
-        leaf_pair<6>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
+        leaf_pair<6, FULL>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
     }
 };
+
+// One group: the octets from o to the next multiple of eight.  Returns that multiple.
+template <typename D, bool FULL>
+__device__ __forceinline__ int octet_group(D &s, const uint32_t *frz, uint32_t &fword, int o)
+{
+    s.octet_head(o);   // the first octet after the frozen run, then octets 8, 16, ...
+    for (;;) {
+        if ((o & 3) == 0) fword = frz[o >> 2];
+        const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
+        if ((fm & 0x7Fu) != 0x7Fu) s.template octet<FULL>(o, fm);
+        else s.template octet_frozen_prefix<FULL>(o, fm == 0xFFu);
+        ++o;
+        if ((o & 7) == 0) break;
+        s.octet_head_reg(o);
+    }
+    return o;
+}
 
 template <typename R, typename IN, bool CRC_ON, bool FROM_Y>
 __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
@@ -834,18 +869,13 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         // loop does not carry the 16 level-6 registers as loop-variant values.  (With one loop over all octets the
         // compiler kept them in one register set at the loop header and another behind the head, and copied all of
         // them twice per octet.)
-        for (int o = o_first; o < N / 8;) {
-            s.octet_head(o);   // the first octet after the frozen run, then octets 8, 16, ...
-            for (;;) {
-                if ((o & 3) == 0) fword = frz[o >> 2];
-                const uint32_t fm = (fword >> (8 * (o & 3))) & 0xFFu;
-                if ((fm & 0x7Fu) == 0x7Fu) s.octet_frozen_prefix(o, fm == 0xFFu);
-                else s.octet(o, fm);
-                ++o;
-                if ((o & 7) == 0) break;
-                s.octet_head_reg(o);
-            }
-        }
+        // The list fills at the third information leaf and stays full.  The groups up to and including that leaf's run
+        // the body that can still fill it (a few groups per frame: compiled once, rolled); every group behind them runs
+        // the full-list body, in which logact is not read at all.
+        int o = o_first;
+#pragma unroll 1
+        while (o < N / 8 && s.logact < 3) o = octet_group<D, false>(s, frz, fword, o);
+        while (o < N / 8) o = octet_group<D, true>(s, frz, fword, o);
 
         // ---- choose the path, per codeword (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) ----
         const bool pass = CRC_ON && (s.crc == 0);
