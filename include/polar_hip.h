@@ -68,7 +68,8 @@ typedef struct polar_cfg {
     int crc_r;             /* CRC length r (0 = none)                                                    */
     const int *crc_taps;   /* exponents of g(D) incl. 0 and r, e.g. {0,5,6} (CASCL_128.c:212-214)        */
     int n_taps;
-    int L;                 /* list size, power of two 1..32 (SC: 1)                                      */
+    int L;                 /* list size, power of two 1..32 (SC: 1); SCL / CA-SCL in F64 / F32 also 64,  *
+                            * 128, 256 while N * L <= 65536 ("Wide lists" below)                          */
     int algo;              /* POLAR_ALGO_*                                                               */
     int bp_iters;          /* BP round trips (reference: iterMax = 100, BP_1024.c:16)                    */
     const int *info_order; /* I[0..K+crc_r): unfrozen positions in reliability order (I[i] = Q[N-(K+r)+i]).
@@ -480,7 +481,8 @@ int polar_construct_order(int N, const uint64_t *counts, const int *base_order, 
  * parity-check bits of TS 38.212 5.3.1.2 (n_PC > 0: the uplink cases 18 <= K <= 25), eBCH-polar subcodes and any
  * lower-triangular precoding.  A dynamic context is the plain decoder of its polar_cfg plus a set Dyn of positions and a set
  * S_j for every j in Dyn:
- *   1. algo is POLAR_ALGO_SC, POLAR_ALGO_SCL or POLAR_ALGO_CASCL; L a power of two in 1..32; both dtypes; 32 <= N <= 1024.
+ *   1. algo is POLAR_ALGO_SC, POLAR_ALGO_SCL or POLAR_ALGO_CASCL; L a power of two in 1..32, or a wide list ("Wide lists"
+ *      below); both dtypes; 32 <= N <= 1024.
  *   2. Dyn is a set of positions that are frozen under the cfg.  S_j is a subset of {0 .. j-1}; a member may be an
  *      information position, a plain frozen one (always 0) or an earlier dynamic one.
  *   3. At leaf j, for every live path, u_hat_0 .. u_hat_{j-1} are that path's decided bits and lambda its leaf LLR.  An
@@ -501,7 +503,7 @@ int polar_construct_order(int N, const uint64_t *counts, const int *base_order, 
  *      noise.  d_u_bits carries the dynamic bits.
  * Honoured by polar_decode, polar_decode_batch(_y) (a frozen_mask override returns POLAR_EINVAL), polar_decode_device,
  * polar_generate_device, polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device, polar_kernel_name
- * ("k_scl_dyn<...>"), polar_ctx_info, polar_info_order and the polar_genie_* calls (which work on any ctx and ignore the
+ * ("k_scl_dyn<...>"; "k_scl_wide<...>" for L > 32), polar_ctx_info, polar_info_order and the polar_genie_* calls (which work on any ctx and ignore the
  * constraints).  polar_cascl_*, polar_bp_*, polar_scf_* and polar_scan_* return POLAR_EINVAL on a dynamic ctx.
  * Out of scope: dynamic bits on polar_create_rm / polar_create_crc_file contexts (so 5G PC-polar is covered at E = N only),
  * polar_group_* and polar_fer_multi_gpu (they build plain contexts from a polar_cfg), a CRC in the v domain for PAC, Fano or
@@ -535,6 +537,29 @@ int polar_pac_unprecode(int N, const int *g_taps, int n_taps, const int *u, size
  * ptr [n_pc+1], idx, and info_order [n_qi - n_pc]: Q_I \ Q_PC in ascending reliability, which is what cfg.info_order takes. */
 int polar_dyn_pc5g(int N, const int *q_i, int n_qi, int n_pc, int n_pc_wm, int *pos, int *ptr, int *idx, int idx_cap,
                    int *nnz, int *info_order);
+
+/* --- Wide lists: L = 64, 128, 256 (no reference counterpart) ------------------------------------------------------------------
+ * Short codes under dynamic frozen bits (PAC(128, 64) is the main example) approach the finite-length bounds only with lists
+ * of 128 to 256.  polar_create, polar_create_dyn, polar_create_crc_file and polar_create_rm accept L = 64, 128 and 256
+ *   - for POLAR_ALGO_SCL and POLAR_ALGO_CASCL,
+ *   - with dtype POLAR_F64 or POLAR_F32,
+ *   - when N * L <= 65536:
+ *         L =  64:  N <= 1024
+ *         L = 128:  N <= 512
+ *         L = 256:  N <= 256
+ * A larger N returns POLAR_ENOKERNEL before any device is touched.  The rule is unchanged: decisions, metric and flags are
+ * what the decoder for L <= 32 is specified to give, for a larger L (phase 1 clones slot k into slot k + act; phase 2 keeps
+ * the candidates c with #{m : c_m <= c} <= L; the m-th both-survivor in ascending slot order forks into the m-th dead slot; an
+ * un-refilled dead slot continues as its 0-branch; POLAR_FLAG_TIE iff fewer than L candidates survive at some leaf; rules
+ * 3-6 of the dynamic frozen bits; the first slot of least metric among the live slots that pass the CRC, among all live slots
+ * if none passes or there is no CRC), with the same arithmetic in the same operation order.  In f64 the results are
+ * bit-identical to the CPU oracle where it reaches (L = 64) on frames without a median tie.
+ * One kernel serves plain and dynamic contexts: polar_kernel_name starts with "k_scl_wide<".  Every entry point works on
+ * such a ctx: polar_decode, polar_decode_batch(_y), polar_decode_device, polar_cascl_decode_device / _batch (d_list = L),
+ * polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device, the generator, the error counters, the encoder side.
+ * POLAR_EINVAL as before: L = 512 and above, L not a power of two, L > 32 with POLAR_Q8, a stage above 32 in
+ * polar_cascl_set_stages (so no adaptive decoder on a wide ctx), L > 32 in polar_decode_llr, and polar_group_create /
+ * polar_fer_multi_gpu with L > 32. */
 
 /* --- Encoder, payload extraction, systematic polar codes (no reference counterpart as functions of their own) ----------------
  * The transmit side for a caller's own bits, and the way back from a decoder's N-wide u_hat to the K payload bits.  All rows

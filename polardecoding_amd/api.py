@@ -1147,7 +1147,8 @@ def BP(N, K, iterMax=100, early_stop=None, **kw):
 
 
 def SCLdecode(N, K, L=8, **kw):
-    """SCL_1024.c:547 -- ``SCLdecode(y, u_hat)``; L is SCL_1024.c:16."""
+    """SCL_1024.c:547 -- ``SCLdecode(y, u_hat)``; L is SCL_1024.c:16.  L: a power of two up to 32, or a wide list of 64, 128
+    or 256 while N * L <= 65536 (include/polar_hip.h, "Wide lists"; not with dtype=Q8)."""
     return Decoder(N, K, ALGO_SCL, L=L, **kw)
 
 
@@ -1157,7 +1158,7 @@ def CASCL(N, K, L=8, crc_taps=CRC24C_TAPS, crc_file=None, stages=None, **kw):
     ``crc_file``: r and g(D) from a generator-matrix file instead (the reference's CRC_6.dat; ``Gc`` of
     CASCL_1024_sys.c:48-561 in the same layout) -- polar_create_crc_file.
     ``stages``: adaptive CA-SCL, e.g. ``CASCL(1024, 512, L=32, stages=(1, 8, 32))`` (Decoder.set_cascl_stages);
-    None: every frame decoded with list size L."""
+    None: every frame decoded with list size L.  L = 64, 128, 256 (N * L <= 65536): a wide list; no ``stages`` then."""
     if crc_file is not None:
         dec = Decoder(N, K, ALGO_CASCL, L=L, crc_taps=None, crc_file=crc_file, **kw)
     else:
@@ -1217,7 +1218,8 @@ def pac_info_order(N, K, profile="rm"):
 def PAC(N, K, g=0o133, L=32, profile="rm", **kw):
     """Polarization-adjusted convolutional code under list decoding (include/polar_hip.h, dynamic frozen bits): SCL (SC for
     L = 1) over the rate profile `profile` (pac_info_order) with every other position a dynamic frozen bit of the precoder g.
-    Decisions are u-domain rows; ``pac_unprecode(u_hat, g)[..., dec.info_order]`` is the payload."""
+    Decisions are u-domain rows; ``pac_unprecode(u_hat, g)[..., dec.info_order]`` is the payload.  L = 64, 128 or 256 (a wide
+    list, N * L <= 65536) is where PAC(128, 64) gains over the default of 32."""
     io = pac_info_order(N, K, profile)
     dec = Decoder(N, K, ALGO_SCL if L > 1 else ALGO_SC, L=L, info_order=io, dyn=dyn_pac(N, io, g), **kw)
     dec.pac_g = pac_taps(g)
@@ -1226,7 +1228,7 @@ def PAC(N, K, g=0o133, L=32, profile="rm", **kw):
 
 def PCCASCL(N, K, n_pc=3, n_pc_wm=0, L=8, crc_taps=CRC6_TAPS, **kw):
     """5G parity-check CRC-aided polar code at E = N (38.212 5.3.1.2): Q_I = the K + r + n_pc most reliable positions, n_pc
-    of them parity-check bits (dyn_pc5g), CA-SCL over the rest."""
+    of them parity-check bits (dyn_pc5g), CA-SCL over the rest.  L up to 32, or a wide list of 64, 128 or 256."""
     r = int(max(crc_taps))
     q = q_sequence(N)
     pos, sets, io = dyn_pc5g(N, q[N - (K + r + n_pc):], n_pc, n_pc_wm)

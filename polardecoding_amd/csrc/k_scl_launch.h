@@ -1,5 +1,6 @@
-// k_scl_launch.h -- launch code of scl_generic_body's two kernels, shared by k_generic.hip (k_scl_generic) and k_dyn.hip
-// (k_scl_dyn), one translation unit each, compiled in parallel.  Each names its kernel in a trait K:
+// k_scl_launch.h -- launch code of scl_generic_body's two kernels and of k_scl_wide, shared by k_generic.hip (k_scl_generic),
+// k_dyn.hip (k_scl_dyn) and k_wide.hip (k_scl_wide: its own ladder over L, launch_scl below it), one translation unit each,
+// compiled in parallel.  Each names its kernel in a trait K:
 //     K::Params                                  the kernel's parameter struct
 //     K::kernel<R, IN, LOGL, GA>()               the instantiation
 //     K::lds_bytes<R, LOGL>(N, ga)               its dynamic LDS
@@ -17,7 +18,8 @@ int launch_scl_v(polar_ctx *c, typename K::Params Q)
     polar::SclParams &S = K::scl(Q);
     const size_t lds = K::template lds_bytes<R, LOGL>(S.N, GA);
     if (lds > 160 * 1024) return POLAR_ENOKERNEL;
-    LaunchShape s{64, lds, S.B, 1};
+    constexpr int threads = LOGL > 6 ? 1 << LOGL : 64;   // one wavefront; k_scl_wide: one thread per path
+    LaunchShape s{threads, lds, S.B, 1};
     if (GA) {   // the levels in global scratch: at most 8 blocks per CU
         s.scratch_per_block = sizeof(R) * (size_t)((1 << LOGL) + 1) * S.N;
         s.occ_cap = 8;
@@ -27,7 +29,7 @@ int launch_scl_v(polar_ctx *c, typename K::Params Q)
     if (rc) return rc;
     if (GA) S.scratch = pl.scratch;
     S.queue = pl.queue;   // the counter hangs off c->scratch with or without scratch bytes
-    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(64), lds, c->stream, Q);
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(threads), lds, c->stream, Q);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
 }

@@ -217,11 +217,12 @@ bool fast_ok(const polar_ctx *c, int in_is_f32)
 // The kernel family the fixed decoder of ctx c runs on a batch of B rows: decode_fixed() launches it, refresh_kernel_name()
 // names it.  scl_big.h for SCL / CA-SCL with N >= 512, L >= 2 (shapes without a tuned kernel); else the generic kernel,
 // LDS-resident when the levels fit (160 KB per CU), global-scratch variant otherwise.
-enum class Family { BP, DYN, SC_LANES, FAST, FAST2, FAST4, BIG, GENERIC };
+enum class Family { BP, WIDE, DYN, SC_LANES, FAST, FAST2, FAST4, BIG, GENERIC };
 Family kernel_family(const polar_ctx *c, int in_is_f32, size_t B)
 {
     const polar_cfg &g = c->cfg;
     if (g.algo == POLAR_ALGO_BP || g.algo == POLAR_ALGO_BPL) return Family::BP;   // BPL: the kernel of every attempt
+    if (c->logL > 5) return Family::WIDE;   // L = 64 / 128 / 256: one kernel, plain or with dynamic frozen bits
     if (c->is_dyn) return Family::DYN;   // dynamic frozen bits: one kernel for every shape
     if (sc_lanes_ok(c, B)) return Family::SC_LANES;
     if (fast_ok(c, in_is_f32)) {
@@ -297,6 +298,7 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     const bool in32 = in_is_f32 != 0;
     const bool crc = g.algo == POLAR_ALGO_CASCL;
     switch (fam) {
+    case Family::WIDE: return polar_tu::scl_wide(c, P, f32, in32);
     case Family::DYN: return polar_tu::scl_dyn(c, P, f32, in32);
     case Family::SC_LANES: return polar_tu::sc_lanes(c, P, f32, in32);
 #ifdef POLAR_TESTING
@@ -626,6 +628,10 @@ void refresh_kernel_name(polar_ctx *c)
     case Family::DYN:   // stands alone: replaces the wrappers below as well
         snprintf(nm, sizeof nm, "k_scl_dyn<%s,L=%d> (D=%d dynamic frozen bits)", ty, g.L, (int)c->dyn_pos.size());
         break;
+    case Family::WIDE:
+        if (c->is_dyn) snprintf(nm, sizeof nm, "k_scl_wide<%s,L=%d> (D=%d dynamic frozen bits)", ty, g.L, (int)c->dyn_pos.size());
+        else snprintf(nm, sizeof nm, "k_scl_wide<%s,L=%d>", ty, g.L);
+        break;
     case Family::SC_LANES: snprintf(nm, sizeof nm, "k_sc_lanes<%s> (batches of 64+; k_scl_generic below)", ty); break;
     case Family::FAST:
     case Family::FAST2:
@@ -658,7 +664,7 @@ void refresh_kernel_name(polar_ctx *c)
         c->kernel_name = a;
     }
     if (c->rm_mode != POLAR_RM_NONE) c->kernel_name = "k_rm_recover, then " + c->kernel_name;
-    if (fam == Family::DYN) c->kernel_name = nm;
+    if (fam == Family::DYN || (fam == Family::WIDE && c->is_dyn)) c->kernel_name = nm;
 }
 
 std::vector<uint32_t> pack_mask(const unsigned char *m, int N, bool invert)
@@ -885,7 +891,8 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     if (cfg->algo == POLAR_ALGO_SC || cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_SCF || cfg->algo == POLAR_ALGO_SCAN ||
         cfg->algo == POLAR_ALGO_BPL)
         L = 1;
-    if (L < 1 || L > 32 || (L & (L - 1))) return POLAR_EINVAL;
+    if (L < 1 || L > 256 || (L & (L - 1))) return POLAR_EINVAL;
+    if (L > 32 && cfg->dtype == POLAR_Q8) return POLAR_EINVAL;   // wide lists (L = 64 / 128 / 256): float and double only
     const bool crc_optional = cfg->algo == POLAR_ALGO_BPL && cfg->crc_r == 0;   // BP list decoding: crc_r = 0 means none
     if (has_crc(cfg->algo) && !crc_optional && (cfg->crc_r < 1 || !cfg->crc_taps || cfg->n_taps < 2)) return POLAR_EINVAL;
     if ((cfg->algo == POLAR_ALGO_BP || cfg->algo == POLAR_ALGO_BPL) && cfg->bp_iters < 1) return POLAR_EINVAL;
@@ -894,6 +901,7 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     // fixed-point min-sum: SC / SCL / CA-SCL up to N = 1024
     if (cfg->dtype == POLAR_Q8 && (N > 1024 || (cfg->algo != POLAR_ALGO_SC && cfg->algo != POLAR_ALGO_SCL && cfg->algo != POLAR_ALGO_CASCL)))
         return POLAR_ENOKERNEL;
+    if (L > 32 && (long long)N * L > 65536) return POLAR_ENOKERNEL;   // k_scl_wide: its pointer table holds log2 L * log2 N <= 64 bits
 
     polar_ctx *c = new (std::nothrow) polar_ctx();
     if (!c) return POLAR_ENOMEM;
@@ -2281,6 +2289,7 @@ int polar_group_create(const polar_cfg *cfg, int ngpus, polar_group **out)
     if (!cfg || !out || ngpus < 1 || ngpus > 64) return POLAR_EINVAL;
     *out = nullptr;
     if (cfg->dtype == POLAR_Q8) return POLAR_EINVAL;   // the groups build float contexts only
+    if ((cfg->algo == POLAR_ALGO_SCL || cfg->algo == POLAR_ALGO_CASCL) && cfg->L > 32) return POLAR_EINVAL;   // no wide lists in a group
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ngpus > ndev) return POLAR_EDEVICE;
     RcclApi &R = rccl();

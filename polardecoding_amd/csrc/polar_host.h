@@ -289,6 +289,8 @@ int scan_lanes(polar_ctx *c, const polar::ScanParams &P, bool r32, bool in32);
 // k_dyn.hip: dynamic frozen bits (scl_dyn.h): SC / SCL / CA-SCL with c->d_dyn_mask / d_dyn_row, the generator with them
 int scl_dyn(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32);
 int dyn_generate(polar_ctx *c, const polar::GenParams &G);
+// k_wide.hip: SCL / CA-SCL with L = 64 / 128 / 256 (scl_wide.h), plain or with c->d_dyn_mask / d_dyn_row (uses c->logL, c->force_spill)
+int scl_wide(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32);
 // k_enc.hip: the encoder side on packed rows (enc_kernel.h)
 int enc_transform(polar_ctx *c, const uint32_t *d_in, const uint32_t *d_in2, bool clear_frozen, size_t B, uint32_t *d_out);
 int enc_place(polar_ctx *c, const uint32_t *d_payload, size_t B, uint32_t *d_z);                      // needs d_enc_inv, d_enc_rtab

@@ -1,0 +1,377 @@
+// scl_wide.h -- SCL / CA-SCL with a wide list, L = 2^LOGL in {64, 128, 256}, plain or with dynamic frozen bits.
+//
+// The rule is scl_generic.h's (and scl_dyn.h's for DYN), word for word: phase 1 clones slot k into slot k + act, phase 2
+// keeps the candidates c with #{m : c_m <= c} <= L, the m-th both-survivor (ascending slot) forks into the m-th dead slot,
+// an un-refilled dead slot continues as its 0-branch, the tie flag is set iff fewer than L candidates survive at some leaf,
+// a dynamic frozen leaf takes the parity of (history AND mask row) and adds PHI(lambda, b), and the output is the first slot
+// of least metric among the live slots that pass the CRC (among all live slots if none passes or there is no CRC).  The
+// arithmetic is chk_lut / lut.tabv / gfun in the same operation order, so the results equal scl_generic_body's bit for bit
+// wherever both exist, and the CPU model's (tests/test_dyn_host.py dscl_model) everywhere.
+//
+// What differs is the mapping.  scl_generic_body gives a path S = 64 / L lanes of one wavefront and moves state between paths
+// with __shfl / __ballot; that stops at 64 lanes.  Here one codeword has a workgroup of L threads (1, 2 or 4 wavefronts),
+// one thread per path, and everything that crosses paths goes through LDS:
+//
+//     ch[N]                    channel LLRs (level n)
+//     alpha[N][L]              level t of slot s: elements (2^t + e) * L + s -- scl_generic.h's alpha[L][N] transposed, so
+//                              that the L threads writing element e of their own slots touch L consecutive words (no LDS
+//                              bank conflicts; coalesced stores in the global-scratch variant)
+//     blw / curw / hist [N/32][L]   bit-packed as in scl_generic.h, transposed the same way; word 0 of blw and hist lives in
+//                              registers (bl0, h0), cur0 is the working word below level 5
+//     cand[2L]                 candidate metrics of a forking leaf: [p] = 0-branch, [L + p] = 1-branch of slot p
+//     xptr / xcrc / xbl0 / xh0 [L]   the state that moves with a path, written by its owner before a fork, indexed by source slot
+//     blist[L], wcnt[4][4]     per wavefront: the slots of its both-survivors in ascending order, and its counts
+//
+// SclParams::sc_mode is not read: SC has L = 1 and never comes here.
+// GA = true: ch and alpha live in the workgroup's slice of the global scratch ((L + 1) * N values), read with ld_bypass.
+//
+// Each thread walks the whole level row of its path: at leaf j it reads level d + 1 (d = ctz j) through its pointer table and
+// rewrites levels d .. 0 of its OWN slot, reading back only what it has just written.  Across threads the only reads are of
+// level d + 1, which nobody writes at this leaf, so the level steps of one leaf need no barrier between them; one workgroup
+// barrier after the LLR phase of every leaf keeps leaf j's reads ahead of leaf j + 1's writes (in the global variant every
+// wavefront first waits for its own stores, wide_level_barrier()).  The partial-sum updates touch the thread's own words only.  A
+// forking leaf adds three barriers: after the candidates and the exchange arrays are written, after the survivor classes
+// are written, and after the refilled slots have copied their words.
+//
+// Every __syncthreads() and every __ballot sits in control flow that is uniform for the workgroup: the conditions around
+// them are functions of j, the frozen mask, the constraint row and act only, never of the path.
+#pragma once
+#include "scl_dyn.h"
+
+namespace polar {
+
+// LDS carve-up, the same arithmetic on the host (launch) and in the kernel
+template <typename R, int LOGL, bool DYN>
+struct WideLds {
+    static constexpr int L = 1 << LOGL;
+    static constexpr int MISC_WORDS = 32;   // wcnt[4][4], the job slot, padding
+    static constexpr size_t r_elems(int N, bool ga) { return (ga ? 0 : (size_t)N * (L + 1)) + 2 * L; }
+    static constexpr size_t bit_words(int N) { return (size_t)(DYN ? 3 : 2) * (N / 32) * L; }
+    static constexpr size_t bytes(int N, bool ga)
+    {
+        return sizeof(R) * r_elems(N, ga) + sizeof(uint64_t) * L + sizeof(uint32_t) * (bit_words(N) + 4 * L + MISC_WORDS) + 16 +
+               Lut<R>::bytes;
+    }
+};
+
+// The barrier behind a step that wrote ch / alpha.  GA: the rows pass from wavefront to wavefront through global memory and
+// are read around the L1 (ld_bypass), so every wavefront first waits until its own stores have completed (vmcnt(0); the
+// fence keeps the compiler from moving a store below the wait).
+template <bool GA>
+__device__ __forceinline__ void wide_level_barrier()
+{
+    if constexpr (GA) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0); expcnt and lgkmcnt left alone
+    }
+    __syncthreads();
+}
+
+template <typename R, typename IN, int LOGL, bool GA, bool DYN>
+__global__ __launch_bounds__(1 << LOGL) void k_scl_wide(DynParams DP)
+{
+    static_assert(LOGL >= 6 && LOGL <= 8, "one thread per path: 1, 2 or 4 wavefronts");
+    constexpr int L = 1 << LOGL;
+    constexpr int NWAVES = L / 64;
+    using Lay = WideLds<R, LOGL, DYN>;
+    const SclParams &P = DP.s;
+    const int N = P.N, n = P.n, NW = N >> 5;
+    const int p = threadIdx.x;
+    const int wave = p >> 6, wlane = p & 63;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    R *ch, *alpha, *cand;
+    if constexpr (GA) {
+        ch = reinterpret_cast<R *>(P.scratch) + (size_t)blockIdx.x * (size_t)(L + 1) * N;
+        alpha = ch + N;
+        cand = reinterpret_cast<R *>(smem);
+    } else {
+        ch = reinterpret_cast<R *>(smem);
+        alpha = ch + N;
+        cand = alpha + (size_t)N * L;
+    }
+    uint64_t *xptr = reinterpret_cast<uint64_t *>(cand + 2 * L);
+    uint32_t *blw = reinterpret_cast<uint32_t *>(xptr + L);
+    uint32_t *curw = blw + (size_t)NW * L;
+    uint32_t *hist = curw + (size_t)NW * L;   // DYN only
+    uint32_t *xcrc = hist + (DYN ? (size_t)NW * L : 0);
+    uint32_t *xbl0 = xcrc + L;
+    uint32_t *xh0 = xbl0 + L;
+    int *blist = reinterpret_cast<int *>(xh0 + L);
+    int *wcnt = blist + L;               // [NWAVES][4]: both-survivors, dead slots, surviving candidates
+    int *job_slot = wcnt + 16;
+    unsigned char *lut_mem = reinterpret_cast<unsigned char *>(wcnt + Lay::MISC_WORDS);
+    lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
+    Lut<R>::build(lut_mem, p, L);
+    Lut<R> lut;
+    lut.bind(lut_mem);
+    __syncthreads();
+    auto ld = [](const R *q) -> R {
+        if constexpr (GA) return ld_bypass(q);
+        else return *q;
+    };
+
+    for (int frame = blockIdx.x; frame < P.B; frame = next_job_block(P.queue, frame, (int)gridDim.x, P.B, job_slot)) {
+        // ---- channel LLRs (SCL_1024.c:574-578) ----
+        {
+            const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
+            for (int i = p; i < N; i += L) {
+                double v = (double)src[i];
+                if (P.sigma > 0) v = llr_from_y(v, P.sigma);
+                ch[i] = (R)v;
+            }
+        }
+        if constexpr (DYN)
+            for (int w = 1; w < NW; ++w) hist[w * L + p] = 0u;
+        wide_level_barrier<GA>();
+
+        R PM = R(0);
+        uint64_t ptrA = 0;
+        uint32_t crc = 0, bl0 = 0, cur0 = 0;
+        uint32_t h0 = 0;
+        uint32_t fl = 0;
+        int act = 1;
+
+        for (int j = 0; j < N; ++j) {
+            // ================= LLR of leaf j for every active path: the path's thread walks every level =================
+            R lam = R(0);
+            if (p < act) {
+                int tf = n - 1;
+                if (j > 0) {
+                    const int d = __builtin_ctz((unsigned)j);
+                    const int h = 1 << d;
+                    const bool top = d + 1 == n;
+                    const R *src = top ? ch : alpha + (size_t)(2 << d) * L + ptr_get<LOGL>(ptrA, top ? 0 : d + 1);
+                    const int st = top ? 1 : L;
+                    R *out = alpha + (size_t)h * L + p;
+                    for (int e = 0; e < h; ++e) {
+                        const int bi = h + e;
+                        const uint32_t wv = (bi < 32) ? bl0 : blw[(bi >> 5) * L + p];
+                        lam = gfun<R>(ld(src + (size_t)e * st), ld(src + (size_t)(e + h) * st), (wv >> (bi & 31)) & 1);
+                        out[(size_t)e * L] = lam;
+                    }
+                    ptrA = ptr_set<LOGL>(ptrA, d, p);
+                    tf = d - 1;
+                }
+                for (int t = tf; t >= 0; --t) {
+                    const int h = 1 << t;
+                    const bool top = t + 1 == n;
+                    const R *src = top ? ch : alpha + (size_t)(2 << t) * L + ptr_get<LOGL>(ptrA, top ? 0 : t + 1);
+                    const int st = top ? 1 : L;
+                    R *out = alpha + (size_t)h * L + p;
+                    for (int e = 0; e < h; ++e) {
+                        lam = chk_lut<R>(ld(src + (size_t)e * st), ld(src + (size_t)(e + h) * st), lut);
+                        out[(size_t)e * L] = lam;
+                    }
+                    ptrA = ptr_set<LOGL>(ptrA, t, p);
+                }
+            }
+            wide_level_barrier<GA>();   // leaf j's reads of other slots' rows before leaf j + 1's writes
+
+            // ================= decision =================
+            const bool frozen = (P.frozen[j >> 5] >> (j & 31)) & 1;
+            int row = -1;   // DYN: row of leaf j in the constraint matrix, -1 = not dynamic (uniform, like j)
+            if constexpr (DYN) row = DP.row[j];
+            int bit = 0;
+            if (row >= 0) {
+                // dynamic frozen leaf: b = parity of (history AND mask row) over the words 0 .. j >> 5; no fork, no ranking
+                if constexpr (DYN) {
+                    const uint32_t *mrow = DP.mask + (size_t)row * NW;
+                    uint32_t par = 0;
+                    for (int w = 0; w <= (j >> 5); ++w) {
+                        const uint32_t hw = (w == 0) ? h0 : hist[w * L + p];
+                        par ^= (uint32_t)__popc(hw & mrow[w]);
+                    }
+                    bit = (int)(par & 1u);
+                    if (p < act) PM = PM + (lut.tabv(lam) + (bit ? posmax(lam) : negmax(lam)));
+                }
+            } else if (frozen) {
+                if (p < act) PM += lut.tabv(lam) + negmax(lam);  // PHI(.,0), SCL_1024.c:601-604, :662-665
+            } else {
+                // an information leaf: every path offers its two branches
+                const R tt = lut.tabv(lam);
+                const R c0 = PM + (tt + negmax(lam));
+                const R c1 = PM + (tt + posmax(lam));
+                cand[p] = c0;
+                cand[p + L] = c1;
+                xptr[p] = ptrA;
+                xcrc[p] = crc;
+                xbl0[p] = bl0;
+                if constexpr (DYN) xh0[p] = h0;
+                __syncthreads();
+                int sg = p;           // the slot this thread's path comes from
+                bool moved = false;   // it takes the 1-branch of slot sg
+                if (act < L) {
+                    // phase 1: every path forks, clone k -> k + act (SCL_1024.c:586-600)
+                    moved = (p >= act) && (p < 2 * act);
+                    if (moved) sg = p - act;
+                    if (p < act) PM = c0;
+                    act *= 2;
+                } else {
+                    // phase 2: keep the L best of 2L candidates (SCL_1024.c:610-661)
+                    // strict "< med" with med = (L+1)-th smallest  <=>  #{m : c_m <= c} <= L
+                    int n0 = 0, n1 = 0;
+                    for (int m = 0; m < 2 * L; ++m) {
+                        const R v = cand[m];
+                        n0 += (v <= c0);
+                        n1 += (v <= c1);
+                    }
+                    const bool s0 = n0 <= L, s1 = n1 <= L;
+                    const bool both = s0 && s1, dead = !s0 && !s1;
+                    const uint64_t m_s0 = __ballot(s0), m_s1 = __ballot(s1);
+                    const uint64_t m_both = m_s0 & m_s1, m_dead = ~(m_s0 | m_s1);
+                    const uint64_t below = (1ull << wlane) - 1ull;
+                    if (both) blist[wave * 64 + __popcll(m_both & below)] = p;   // this wavefront's both-survivors, ascending
+                    if (wlane == 0) {
+                        wcnt[wave * 4 + 0] = __popcll(m_both);
+                        wcnt[wave * 4 + 1] = __popcll(m_dead);
+                        wcnt[wave * 4 + 2] = __popcll(m_s0) + __popcll(m_s1);
+                    }
+                    __syncthreads();
+                    int n_both = 0, n_surv = 0, rank = __popcll(m_dead & below);   // rank: this slot among the dead ones
+                    for (int w = 0; w < NWAVES; ++w) {
+                        n_both += wcnt[w * 4 + 0];
+                        n_surv += wcnt[w * 4 + 2];
+                        if (w < wave) rank += wcnt[w * 4 + 1];
+                    }
+                    if (n_surv < L) fl |= 0x1u;  // median tie ("Oops!", :621-622)
+                    // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661)
+                    if (dead && rank < n_both) {
+                        int r = rank;
+                        for (int w = 0; w < NWAVES; ++w) {
+                            const int c = wcnt[w * 4 + 0];
+                            if (r >= 0 && r < c) sg = blist[w * 64 + r];
+                            r -= c;   // negative once found
+                        }
+                        moved = true;
+                    } else if (s0) {
+                        PM = c0;  // class 0 or the staying half of class 2
+                    } else if (s1) {
+                        bit = 1;
+                        PM = c1;
+                    } else {
+                        PM = c0;  // tie rule: an un-refilled dead slot continues as its 0-branch
+                    }
+                }
+                if (moved) {
+                    bit = 1;
+                    PM = cand[sg + L];
+                    ptrA = xptr[sg];
+                    crc = xcrc[sg];
+                    bl0 = xbl0[sg];
+                    if constexpr (DYN) h0 = xh0[sg];
+                    for (int w = 1; w < NW; ++w) {
+                        blw[w * L + p] = blw[w * L + sg];
+                        if constexpr (DYN) hist[w * L + p] = hist[w * L + sg];
+                    }
+                }
+                __syncthreads();   // the copies read their sources before the owners go on
+            }
+
+            // ================= DYN: bit j of the path's history (the thread's own words) =================
+            if constexpr (DYN) {
+                if (j < 32) h0 |= (uint32_t)bit << j;
+                else if (p < act && bit) hist[(j >> 5) * L + p] |= 1u << (j & 31);
+            }
+
+            // ================= partial sums (updateBit, SCL_1024.c:424-448), the thread's own words =================
+            if (P.crc_tab && bit) crc ^= P.crc_tab[j];
+            cur0 = (uint32_t)bit;
+            int t = 0;
+            while (t < n && ((j >> t) & 1)) {
+                if (t < 5) {
+                    const int h = 1 << t;
+                    const uint32_t mask = (1u << h) - 1u;
+                    const uint32_t l = (bl0 >> h) & mask;
+                    const uint32_t c = cur0 & mask;
+                    cur0 = (l ^ c) | (c << h);
+                } else if (p < act) {
+                    const int nw = 1 << (t - 5);
+                    if (t == 5) curw[p] = cur0;
+                    for (int w = 0; w < nw; ++w) {
+                        const uint32_t c = curw[w * L + p];
+                        const uint32_t l = blw[(nw + w) * L + p];
+                        curw[w * L + p] = l ^ c;
+                        curw[(w + nw) * L + p] = c;
+                    }
+                }
+                ++t;
+            }
+            if (t < n) {
+                if (t < 5) {
+                    const int h = 1 << t;
+                    const uint32_t mask = (1u << h) - 1u;
+                    bl0 = (bl0 & ~(mask << h)) | ((cur0 & mask) << h);
+                } else if (p < act) {
+                    const int nw = 1 << (t - 5);
+                    if (t == 5) blw[L + p] = cur0;
+                    else
+                        for (int w = 0; w < nw; ++w) blw[(nw + w) * L + p] = curw[w * L + p];
+                }
+            }
+        }
+
+        // ================= choose the path (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) =================
+        // the first slot of least metric among the live slots that pass the CRC; among all live slots if none does
+        cand[p] = PM;
+        xcrc[p] = (P.crc_tab != nullptr && crc == 0) ? 1u : 0u;
+        xbl0[p] = cur0;
+        if constexpr (DYN) xh0[p] = h0;
+        __syncthreads();
+        int best = -1, best_ok = -1;
+        R best_pm = R(0), best_ok_pm = R(0);
+        for (int q = 0; q < act; ++q) {
+            const R pq = cand[q];
+            if (best < 0 || pq < best_pm) {
+                best = q;
+                best_pm = pq;
+            }
+            if (xcrc[q] && (best_ok < 0 || pq < best_ok_pm)) {
+                best_ok = q;
+                best_ok_pm = pq;
+            }
+        }
+        if (best_ok >= 0) {
+            best = best_ok;
+            best_pm = best_ok_pm;
+            fl |= 0x2u;
+        }
+        // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
+        if constexpr (DYN) {
+            if (p < NW) P.out_bits[(size_t)frame * NW + p] = (p == 0) ? xh0[best] : hist[p * L + best];
+        } else if (n <= 5) {
+            uint32_t x = xbl0[best];
+            for (int s = 0; s < n; ++s) {
+                const uint32_t msk = (s == 0) ? 0x55555555u : (s == 1) ? 0x33333333u : (s == 2) ? 0x0F0F0F0Fu
+                                   : (s == 3) ? 0x00FF00FFu : 0x0000FFFFu;
+                x ^= (x >> (1 << s)) & msk;
+            }
+            if (p == 0) P.out_bits[(size_t)frame * NW] = x;
+        } else {
+            uint32_t *xw = curw + best;   // word w at xw[w * L]
+            if (p < NW) {
+                uint32_t x = xw[p * L];
+                x ^= (x >> 1) & 0x55555555u;
+                x ^= (x >> 2) & 0x33333333u;
+                x ^= (x >> 4) & 0x0F0F0F0Fu;
+                x ^= (x >> 8) & 0x00FF00FFu;
+                x ^= (x >> 16) & 0x0000FFFFu;
+                xw[p * L] = x;
+            }
+            __syncthreads();
+            for (int s = 5; s < n; ++s) {
+                const int hw = 1 << (s - 5);
+                if (p < NW && !(p & hw)) xw[p * L] ^= xw[(p + hw) * L];
+                __syncthreads();
+            }
+            if (p < NW) P.out_bits[(size_t)frame * NW + p] = xw[p * L];
+        }
+        if (p == 0) {
+            if (P.pm) P.pm[frame] = (double)best_pm;
+            if (P.flags) P.flags[frame] = fl;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace polar

@@ -211,6 +211,7 @@ static void usage(void)
 {
     fprintf(stderr, "usage: polar_sim --algo sc|bp|bpr|scl|cascl|scf|scan|bpl --N n --K k [--L l] [--crc 24c|6 | --crc-file m.dat] [--sys] [--seed s] [--ble b]\n"
                     "                 [--snr lo:hi:step | --snr-list a,b,..] [--batch b] [--dtype f64|f32|q8 [--quant scale,qc,qi]] [--bp-iters i] [--q file] [--fn file] [--min-run m] [--fast [--gpus g]]\n"
+                    "                 [--L l]   (scl|cascl: a power of two up to 32; 64, 128, 256 with f64|f32 while N * l <= 65536: wide lists)\n"
                     "                 [--quant s,qc,qi]   (--dtype q8, fixed-point min-sum sc|scl|cascl: LLR scale, channel and internal bits; default 2,8,8)\n"
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
