@@ -271,6 +271,60 @@ int polar_scf_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, dou
 int polar_scf_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *flags,
                            unsigned *attempts);
 
+/* --- Dynamic SC-Flip: flip sets ranked by a metric (Chandesris, Savin and Declercq, 2018; the multiplier-free metric of
+ * Ercan, Tonnellier, Doan and Gross, 2020) -----------------------------------------------------------------------------
+ * Opt-in on a POLAR_ALGO_SCF context (polar_scf_set_dynamic).  An attempt inverts a SET of up to omega decisions, and the
+ * sets are ranked by a metric that charges an early, fairly reliable decision less than |lambda| alone would.
+ * A declared departure from the paper: the paper's decoder is serial (one attempt, its extensions into a priority list,
+ * pop, repeat: T SC latencies back to back).  Here the rule is layered: all sets of size k of a frame run at once, their
+ * extensions are ranked together and give the sets of size k + 1, omega + 1 SC latencies in all.  The sets tried are
+ * therefore not the paper's, and neither is the metric's log-sum form (the multiplier-free one is used, reproducible
+ * bit for bit).
+ * Setting: order omega in {1, 2, 3}, budgets T_1 .. T_omega (each 1 .. 32, T_1 <= A), a penalty c >= 0 and a threshold
+ * tau >= 0, finite doubles rounded once to R.  Rules 1-3 and 7 of the section above stay (attempt 0, the CRC test, the
+ * untouched passing frames, the metric 0.0, the flags).
+ *   1. run(E), E a set of information positions: SC with the decision inverted at every leaf of E (rule 5 above at each
+ *      member; later leaves see the inverted bits).  lambda^E_j is the leaf LLR at information leaf j in that run.
+ *      run(empty) is attempt 0.
+ *   2. counter: cnt^E_i = #{ j in I[0..A) : j <= i and |lambda^E_j| <= tau }, an integer; it covers flipped leaves and i
+ *      itself; the comparison is done in R, fabs as in rule 4 above.
+ *   3. metric of extending E by an information position i > max(E) (max(empty) = -1):
+ *        M(E, i) = (F_E + |lambda^E_i|) + S,  S = c * (R)cnt^E_i,
+ *      F_empty absent (M(empty, i) = |lambda_i| + S), F_E the sum of |lambda^E_j| over j in E in ascending j starting
+ *      from the first term; every + and the one * rounded once in R, no contraction.  With c = 0, M(empty, i) = |lambda_i|.
+ *   4. level-1 list: the T_1 positions i of I[0..A) with the smallest (M(empty, i), i), ascending (c = 0: rule 4 above).
+ *   5. level-(k+1) list (k < omega), built only for frames where no attempt of levels <= k passed: with E_0 .. E_{T_k - 1}
+ *      the frame's level-k sets in list order, the candidates are all (q, i), i in I[0..A), i > max(E_q); the key is
+ *      (M(E_q, i), q, i), lexicographic, lambda taken from run(E_q); the list is the T_{k+1} candidates of smallest key,
+ *      ascending; candidate (q, i) stands for the set E_q + {i} (distinct by construction).  Fewer candidates: a shorter list.
+ *   6. attempts are numbered globally: rank q (0-based) of level k is attempt T_1 + .. + T_{k-1} + q + 1.
+ *   7. the output is the passing attempt of smallest number (attempts = that number, POLAR_FLAG_CRC_PASS, the reported set
+ *      is its E); if none passes, attempt 0 with attempts = T_1 + .. + T_omega, the flag clear and an empty set.  A frame
+ *      that passes at some level is not run at a later level.
+ *   8. identities: omega = 1 with c = 0 is the static decoder above bit for bit, attempts included; with c, tau and T_1
+ *      fixed, a frame decoded at level 1 has the same output for every omega, so the wrong frames of (T_1, T_2) are a
+ *      subset of those of (T_1).
+ *   9. the Python convenience constructor alone defaults to c = 1.5, tau = 5.0 (the constants Ercan et al. give; a choice,
+ *      see DESIGN.md 4.6 for what this library measured).  A fresh context runs the static rule.
+ * Honoured by everything that honours SCF: polar_decode, polar_decode_batch(_y), polar_decode_device, polar_scf_decode_*,
+ * polar_fer_batch, polar_stop_rule_batch_y, polar_time_decode_device, polar_kernel_name, CRC-file, systematic and
+ * rate-matched contexts.  polar_group_* and polar_fer_multi_gpu keep running the static default.  The host reads one count
+ * per level (a 4-byte copy and a stream sync each); a decode during stream capture stays POLAR_EINVAL. */
+#define POLAR_SCF_MAX_ORDER 3
+/* budgets[0..omega) = T_1 .. T_omega; budgets[0] becomes T (a later polar_scf_set_flips changes T_1 only).  omega = 0
+ * clears the rule and leaves T as it is (budgets, c, tau ignored).  POLAR_EINVAL (ctx unchanged): not an SCF ctx, omega
+ * outside 0 .. 3, a budget out of range, c or tau negative or not finite. */
+int polar_scf_set_dynamic(polar_ctx *ctx, const int *budgets, int omega, double c, double tau);
+/* Every output is nullable.  budgets [3]: T_1 (the ctx's T), T_2, T_3, 0 beyond omega; omega = 0, c = tau = 0: the static rule. */
+int polar_scf_get_dynamic(const polar_ctx *ctx, int *omega, int *budgets, double *c, double *tau);
+/* polar_scf_decode_device plus d_sets (nullable) [B][3]: the reported set in ascending order, -1 padded (all -1: attempt 0
+ * is the output).  On a static ctx it holds at most one entry, the flipped position. */
+int polar_scf_decode_sets_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
+                                 uint32_t *d_uhat_bits, uint32_t *d_flags, uint32_t *d_attempts, int32_t *d_sets);
+/* Host-buffer form: sets (nullable) [B][3]. */
+int polar_scf_decode_sets_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u_hat, unsigned *flags,
+                                unsigned *attempts, int *sets);
+
 /* --- Soft-output SCAN (soft cancellation; Fayyaz and Barry, IEEE JSAC 2014) ----------------------------------------------
  * SCAN is BP's message arithmetic driven by SC's schedule: a serial walk over the tree that carries LLRs upwards instead of
  * hard partial sums, and returns an LLR for every u bit and every code bit.  A POLAR_ALGO_SCAN context takes the cfg of a BP

@@ -100,6 +100,10 @@ def load_library(testing=False):
     L.polar_scf_set_flips.argtypes = [vp, C.c_int]
     L.polar_scf_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
     L.polar_scf_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
+    L.polar_scf_set_dynamic.argtypes = [vp, ip, C.c_int, C.c_double, C.c_double]
+    L.polar_scf_get_dynamic.argtypes = [vp, ip, ip, dp, dp]
+    L.polar_scf_decode_sets_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp, vp]
+    L.polar_scf_decode_sets_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up, ip]
     L.polar_bpl_set_graphs.argtypes = [vp, ip, C.c_int]
     L.polar_bpl_get_graphs.argtypes = [vp, ip, ip]
     L.polar_bpl_cyclic_graphs.argtypes = [C.c_int, C.c_int, ip]
@@ -412,6 +416,7 @@ class Decoder:
         self.bp_stop = BP_STOP_NONE
         self.cascl_stages = ()
         self.scf_flips = None   # None: the library's default (min(8, K + r))
+        self.scf_dynamic = None   # None: the static rule; else (budgets, c, tau) of set_scf_dynamic
         self.scan_iters = None  # None: the library's default (4)
         self._bpl_graphs = None # None: the library's default list (min(n, 8) cyclic shifts)
         self._rm = (int(E), 1 if ibil else 0) if E is not None else None
@@ -469,6 +474,8 @@ class Decoder:
             self.set_cascl_stages(self.cascl_stages)
         if self.scf_flips is not None:
             self.set_scf_flips(self.scf_flips)
+        if self.scf_dynamic is not None:
+            self.set_scf_dynamic(*self.scf_dynamic)
         if self.scan_iters is not None:
             self.set_scan_iters(self.scan_iters)
         if self._bpl_graphs is not None:
@@ -536,6 +543,31 @@ class Decoder:
         min(32, K + r); T = 0 is SC plus the CRC flag."""
         self._check(self._lib.polar_scf_set_flips(self._h, int(T)), "polar_scf_set_flips")
         self.scf_flips = int(T)
+        if self.scf_dynamic is not None:   # T_1 of the dynamic rule
+            b, c, tau = self.scf_dynamic
+            self.scf_dynamic = ((int(T),) + tuple(b[1:]), c, tau)
+
+    def set_scf_dynamic(self, budgets, c=0.0, tau=0.0):
+        """Dynamic SC-Flip (polar_scf_set_dynamic): flip sets of up to len(budgets) <= 3 positions, budgets[k] sets of size
+        k + 1 per CRC-failing frame (each 1 .. 32), ranked by M = |lambda| sums + c * (count of |lambda| <= tau).  budgets[0]
+        becomes the flip budget T.  None or () restores the static rule and keeps T."""
+        b = np.asarray(list(budgets) if budgets is not None else [], dtype=np.int32)
+        self._check(self._lib.polar_scf_set_dynamic(self._h, _ptr(b, C.c_int) if b.size else None, int(b.size), float(c),
+                                                    float(tau)), "polar_scf_set_dynamic")
+        if b.size:
+            self.scf_dynamic = (tuple(int(x) for x in b), float(c), float(tau))
+            self.scf_flips = int(b[0])
+        else:
+            self.scf_dynamic = None
+
+    def get_scf_dynamic(self):
+        """polar_scf_get_dynamic: (budgets, c, tau) with budgets a tuple of omega entries; ((), 0.0, 0.0) on the static rule."""
+        om = C.c_int()
+        b = np.zeros(3, dtype=np.int32)
+        c, tau = C.c_double(), C.c_double()
+        self._check(self._lib.polar_scf_get_dynamic(self._h, C.byref(om), _ptr(b, C.c_int), C.byref(c), C.byref(tau)),
+                    "polar_scf_get_dynamic")
+        return tuple(int(x) for x in b[:om.value]), c.value, tau.value
 
     def set_scan_iters(self, iters):
         """SCAN iteration count (polar_scan_set_iters): 1 <= iters <= 64, default 4."""
@@ -802,6 +834,40 @@ class Decoder:
         self._check(self._lib.polar_scf_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
                                                      _ptr(fl, C.c_uint), _ptr(at, C.c_uint)), "polar_scf_decode_batch")
         return uh, fl, at
+
+    def decode_scf_sets_device(self, d_in, sigma=0.0, out_bits=None, flags=None, attempts=None, sets=None):
+        """polar_scf_decode_sets_device: decode_scf_device plus `sets` (optional int32 tensor [B][3]): the positions the
+        reported attempt inverted, ascending, -1 padded.  Returns out_bits."""
+        import torch
+        B = self._dev_rows(d_in)
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        for t, m in ((flags, 1), (attempts, 1), (sets, 3)):
+            if t is not None and (t.numel() < m * B or t.element_size() != 4 or not t.is_contiguous()):
+                raise ValueError("flags / attempts / sets must be contiguous 32-bit tensors of at least B (sets: 3 B) elements")
+        self._check(self._lib.polar_scf_decode_sets_device(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B, C.c_void_p(out_bits.data_ptr()),
+            C.c_void_p(flags.data_ptr()) if flags is not None else None,
+            C.c_void_p(attempts.data_ptr()) if attempts is not None else None,
+            C.c_void_p(sets.data_ptr()) if sets is not None else None), "polar_scf_decode_sets_device")
+        return out_bits
+
+    def decode_scf_sets_batch(self, llr):
+        """polar_scf_decode_sets_batch: llr [B][N] -> (u_hat [B][N] int32, flags [B] uint32, attempts [B] uint32,
+        sets [B][3] int32)."""
+        llr = self._rows(llr)
+        B = llr.shape[0]
+        uh = np.empty((B, self.N), dtype=np.int32)
+        fl = np.zeros(B, dtype=np.uint32)
+        at = np.zeros(B, dtype=np.uint32)
+        st = np.full((B, 3), -1, dtype=np.int32)
+        self._check(self._lib.polar_scf_decode_sets_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
+                                                          _ptr(fl, C.c_uint), _ptr(at, C.c_uint), _ptr(st, C.c_int)),
+                    "polar_scf_decode_sets_batch")
+        return uh, fl, at, st
 
     def decode_bpl_device(self, d_in, sigma=0.0, out_bits=None, iters=None, flags=None, graph=None, total_iters=None):
         """polar_bpl_decode_device: like decode_device, plus per frame (optional int32 tensors [B]) the round trips of the
@@ -1178,6 +1244,15 @@ def SCFlip(N, K, T=8, crc_taps=CRC24C_TAPS, crc_file=None, **kw):
         dec = Decoder(N, K, ALGO_SCF, L=1, crc_taps=crc_taps, **kw)
     if T != 8:
         dec.set_scf_flips(T)
+    return dec
+
+
+def DSCFlip(N, K, budgets=(8, 16), c=1.5, tau=5.0, crc_taps=CRC24C_TAPS, crc_file=None, **kw):
+    """Dynamic SC-Flip (include/polar_hip.h, polar_scf_set_dynamic): SCFlip whose attempts invert sets of up to len(budgets)
+    decisions, budgets[k] sets of size k + 1, ranked by the multiplier-free metric with penalty ``c`` and threshold ``tau``
+    (defaults: the constants of Ercan et al., 2020; DESIGN.md 4.6 has what they measured here)."""
+    dec = SCFlip(N, K, T=8, crc_taps=crc_taps, crc_file=crc_file, **kw)
+    dec.set_scf_dynamic(budgets, c, tau)
     return dec
 
 

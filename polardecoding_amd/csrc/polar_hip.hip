@@ -394,8 +394,14 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
 // reliable information decisions, and pass B runs all T single-flip attempts of every failing frame at once, one lane per
 // (frame, attempt), in chunks of at most 256 MiB of decisions; k_scf_resolve keeps the first attempt that passes.  One
 // 4-byte copy and a stream sync: the failing count.
+//
+// With the dynamic rule (polar_scf_set_dynamic) the steps are: check, compact, record (SCF_RECORD_M: each failing frame's
+// T_1 best M(0, i), which k_scf_merge turns into the level-1 sets), then per level k: run the frame's T_k sets at once
+// (SCF_FLIPREC below omega, keeping each pair's T_{k+1} best extensions; SCF_FLIPSET at omega) in chunks of at most 256 MiB
+// of decisions, k_scf_resolve_sets, and below omega: compact the frames that still fail (4-byte copy and sync) and merge
+// their pairs' lists into the sets of level k + 1.  d_sets (nullable) [B][3]: the reported set; a static ctx fills it too.
 int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
-               uint32_t *d_flags, uint32_t *d_attempts)
+               uint32_t *d_flags, uint32_t *d_attempts, int32_t *d_sets = nullptr)
 {
     if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
@@ -403,17 +409,22 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
     if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the host reads the failing count
     const int T = c->scf_T, NW = c->NW;
+    const int omega = T > 0 ? c->scf_omega : 0;
+    int Tk[polar::SCF_MAX_ORDER + 1] = {T, 0, 0, 0}, Ttot = T;
+    for (int k = 1; k < omega; ++k) Ttot += (Tk[k] = c->scf_Tk[k]);
     const bool r32 = c->cfg.dtype == POLAR_F32, in32 = in_is_f32 != 0;
     int rc;
     if (!d_flags) {
         if ((rc = ensure(c, c->ad_flags, B * sizeof(uint32_t)))) return rc;
         d_flags = (uint32_t *)c->ad_flags.p;
     }
+    if (d_sets) HIP_TRY(c, hipMemsetAsync(d_sets, 0xFF, B * polar::SCF_MAX_ORDER * sizeof(int32_t), c->stream));   // -1
     polar::ScfParams P{};
     P.in = d_in; P.sigma = sigma; P.out_bits = d_bits; P.pm = d_pm; P.flags = d_flags; P.attempts = d_attempts;
     P.frozen = c->d_frozen; P.crc_tab = c->d_crc_tab;
-    P.N = c->cfg.N; P.n = c->n; P.B = (int)B; P.T = T;
+    P.N = c->cfg.N; P.n = c->n; P.B = (int)B; P.T = Ttot;   // pass A writes attempts = 0 / P.T
     if ((rc = polar_tu::scf_lanes(c, P, polar::SCF_CHECK, r32, in32))) return rc;
+    P.T = T;
     if (T == 0) return POLAR_OK;
     if ((rc = ensure(c, c->ad_idx[0], B * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
@@ -424,8 +435,71 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     uint32_t h = 0;
     HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t n = h;
+    size_t n = h;
     if (n == 0) return POLAR_OK;
+    if (omega > 0) {
+        const size_t rsz = r32 ? 4 : 8, pair_bytes = (size_t)NW * sizeof(uint32_t);
+        size_t pairs = 0, ents = 0, chmax = 0;   // per level: pairs n T_k, list entries n T_k T_{k+1}; pairs per chunk
+        for (int k = 0; k < omega; ++k) {
+            pairs = std::max(pairs, n * (size_t)Tk[k]);
+            ents = std::max(ents, n * (size_t)(k ? Tk[k - 1] : 1) * (size_t)Tk[k]);
+            chmax = std::max(chmax, chunk_rows(n, pair_bytes * (size_t)Tk[k], 1) * (size_t)Tk[k]);
+        }
+        // every buffer of the call, before the first launch of the rule
+        for (Buf *b : {&c->scf_sets[0], &c->scf_sets[1]})
+            if ((rc = ensure(c, *b, pairs * polar::SCF_MAX_ORDER * sizeof(uint16_t)))) return rc;
+        if ((rc = ensure(c, c->scf_lkey, ents * rsz)) || (rc = ensure(c, c->scf_lpos, ents * sizeof(uint16_t))) ||
+            (rc = ensure(c, c->scf_lcnt, pairs * sizeof(uint32_t))) || (rc = ensure(c, c->scf_spass, n * sizeof(uint32_t))) ||
+            (rc = ensure(c, c->scf_surv, n * sizeof(uint32_t))) || (rc = ensure(c, c->ad_idx[1], n * sizeof(uint32_t))) ||
+            (rc = ensure(c, c->scf_bits, chmax * pair_bytes)) || (rc = ensure(c, c->scf_pass, chmax * sizeof(uint32_t))))
+            return rc;
+        uint16_t *lpos = (uint16_t *)c->scf_lpos.p;
+        uint32_t *lcnt = (uint32_t *)c->scf_lcnt.p, *spass = (uint32_t *)c->scf_spass.p, *surv = (uint32_t *)c->scf_surv.p;
+        polar::ScfParams R = P;
+        R.out_bits = nullptr; R.pm = nullptr; R.flags = nullptr; R.attempts = nullptr;
+        R.mc = c->scf_c; R.tau = c->scf_tau; R.lkey = c->scf_lkey.p; R.lpos = lpos; R.lcnt = lcnt;
+        // record: attempt 0 again, each failing frame's T_1 smallest (M(0, i), i); the level-1 sets are these positions
+        R.idx = idx; R.B = (int)n; R.T = 1; R.Tn = Tk[0];
+        if ((rc = polar_tu::scf_lanes(c, R, polar::SCF_RECORD_M, r32, in32))) return rc;
+        int cur = 0, base = 0;
+        if ((rc = polar_tu::scf_merge(c, r32, c->scf_lkey.p, lpos, lcnt, nullptr, nullptr, nullptr, n, 1, Tk[0],
+                                      (uint16_t *)c->scf_sets[cur].p, nullptr)))
+            return rc;
+        for (int k = 0; k < omega; ++k) {   // level k + 1
+            const bool last = k + 1 == omega;
+            const size_t Tl = (size_t)Tk[k], Tnx = (size_t)Tk[k + 1];
+            uint16_t *sets = (uint16_t *)c->scf_sets[cur].p;
+            const size_t CH = chunk_rows(n, pair_bytes * Tl, 1);
+            for (size_t off = 0; off < n; off += CH) {
+                const size_t nc = std::min(CH, n - off);
+                polar::ScfParams F = R;
+                F.idx = idx + off; F.flips = sets + off * Tl * polar::SCF_MAX_ORDER; F.B = (int)(nc * Tl); F.T = (int)Tl;
+                F.Tn = (int)Tnx;
+                F.lkey = (char *)c->scf_lkey.p + off * Tl * Tnx * rsz; F.lpos = lpos + off * Tl * Tnx; F.lcnt = lcnt + off * Tl;
+                F.out_bits = (uint32_t *)c->scf_bits.p; F.flags = (uint32_t *)c->scf_pass.p;
+                if ((rc = polar_tu::scf_lanes(c, F, last ? polar::SCF_FLIPSET : polar::SCF_FLIPREC, r32, in32))) return rc;
+                if ((rc = polar_tu::scf_resolve_sets(c, (uint32_t *)c->scf_pass.p, (uint32_t *)c->scf_bits.p, idx + off, nc,
+                                                     (int)Tl, F.flips, polar::SCF_MAX_ORDER, k + 1, base, d_bits, d_flags,
+                                                     d_attempts, d_sets, last ? nullptr : spass + off)))
+                    return rc;
+            }
+            if (last) break;
+            base += (int)Tl;
+            if ((rc = polar_tu::ad_compact(c, spass, nullptr, n, 1u, (uint32_t *)c->ad_blk.p, surv, (uint32_t *)c->ad_cnt.p)))
+                return rc;
+            HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (h == 0) break;
+            uint32_t *nidx = (uint32_t *)c->ad_idx[idx == (uint32_t *)c->ad_idx[0].p ? 1 : 0].p;
+            if ((rc = polar_tu::scf_merge(c, r32, c->scf_lkey.p, lpos, lcnt, sets, surv, idx, h, (int)Tl, (int)Tnx,
+                                          (uint16_t *)c->scf_sets[cur ^ 1].p, nidx)))
+                return rc;
+            idx = nidx;
+            n = h;
+            cur ^= 1;
+        }
+        return POLAR_OK;
+    }
     // the flip list of every failing frame: attempt 0 again, its T smallest |lambda_j|
     if ((rc = ensure(c, c->scf_flips, n * (size_t)T * sizeof(uint16_t)))) return rc;
     uint16_t *flips = (uint16_t *)c->scf_flips.p;
@@ -444,9 +518,13 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
         F.idx = idx + off; F.flips = flips + off * (size_t)T; F.B = (int)(nc * (size_t)T);
         F.out_bits = (uint32_t *)c->scf_bits.p; F.flags = (uint32_t *)c->scf_pass.p;
         if ((rc = polar_tu::scf_lanes(c, F, polar::SCF_FLIP, r32, in32))) return rc;
-        if ((rc = polar_tu::scf_resolve(c, (uint32_t *)c->scf_pass.p, (uint32_t *)c->scf_bits.p, idx + off, nc, T, d_bits,
-                                        d_flags, d_attempts)))
-            return rc;
+        if (d_sets)
+            rc = polar_tu::scf_resolve_sets(c, (uint32_t *)c->scf_pass.p, (uint32_t *)c->scf_bits.p, idx + off, nc, T, F.flips,
+                                            1, 1, 0, d_bits, d_flags, d_attempts, d_sets, nullptr);
+        else
+            rc = polar_tu::scf_resolve(c, (uint32_t *)c->scf_pass.p, (uint32_t *)c->scf_bits.p, idx + off, nc, T, d_bits,
+                                       d_flags, d_attempts);
+        if (rc) return rc;
     }
     return POLAR_OK;
 }
@@ -561,11 +639,12 @@ int scan_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, siz
 // d_graph, d_total: BP list decoding only.
 int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                         double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters, void *d_llr_u = nullptr,
-                        void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr)
+                        void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr,
+                        int32_t *d_sets = nullptr)
 {
     if (c && c->cfg.algo == POLAR_ALGO_BPL) return bpl_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters, d_graph, d_total);
     if (c && c->cfg.algo == POLAR_ALGO_SCAN) return scan_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_llr_u, d_ext_x);
-    if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
+    if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters, d_sets);
     if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
         if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
         if (B == 0) return POLAR_OK;
@@ -581,11 +660,12 @@ int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double si
 // (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (it is part of the lane, polar_host.h).
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr,
-                       void *d_llr_u = nullptr, void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr)
+                       void *d_llr_u = nullptr, void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr,
+                       int32_t *d_sets = nullptr)
 {
     if (!c || c->rm_mode == POLAR_RM_NONE)
         return decode_device_plain(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters, d_llr_u, d_ext_x,
-                                   d_graph, d_total);
+                                   d_graph, d_total, d_sets);
     const size_t esz = in_is_f32 ? 4 : 8;
     const bool scan = c->cfg.algo == POLAR_ALGO_SCAN;   // its three outputs are nullable
     const size_t soft_row = (size_t)c->cfg.N * (c->cfg.dtype == POLAR_F32 ? 4 : 8);
@@ -604,7 +684,7 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
                                       d_pm ? d_pm + off : nullptr, d_flags ? d_flags + off : nullptr, d_frozen,
                                       d_iters ? d_iters + off : nullptr, d_llr_u ? (char *)d_llr_u + off * soft_row : nullptr,
                                       d_ext_x ? (char *)d_ext_x + off * soft_row : nullptr, d_graph ? d_graph + off : nullptr,
-                                      d_total ? d_total + off : nullptr)))
+                                      d_total ? d_total + off : nullptr, d_sets ? d_sets + off * polar::SCF_MAX_ORDER : nullptr)))
             return rc;
     }
     return POLAR_OK;
@@ -644,6 +724,12 @@ void refresh_kernel_name(polar_ctx *c)
     if (g.algo == POLAR_ALGO_SCF)
         snprintf(nm, sizeof nm, "k_scf_lanes<%s> (SC-Flip, T=%d; pass A, k_ad_fail_count/scan/write, record, pass B, k_scf_resolve)",
                  ty, c->scf_T);
+    if (g.algo == POLAR_ALGO_SCF && c->scf_omega > 0) {
+        std::string b = std::to_string(c->scf_T);
+        for (int k = 1; k < c->scf_omega; ++k) b += "," + std::to_string(c->scf_Tk[k]);
+        snprintf(nm, sizeof nm, "k_scf_lanes<%s> (dynamic SC-Flip, omega=%d, T=%s, c=%g, tau=%g; k_scf_merge, k_scf_resolve_sets)", ty,
+                 c->scf_omega, b.c_str(), c->scf_c, c->scf_tau);
+    }
     if (g.algo == POLAR_ALGO_SCAN) snprintf(nm, sizeof nm, "k_scan_lanes<%s> (SCAN, I=%d)", ty, c->scan_I);
     if (g.algo == POLAR_ALGO_BPL) {
         const std::string bp = nm;
@@ -698,7 +784,7 @@ void unpack_words(const uint32_t *w, int NW, int *out)
 constexpr unsigned HOST_THREADS = 6;   // 4 -> 6: end_to_end 4.4 -> 4.6-4.7 M frames/s; 8 and 12 no more (run 35)
 int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char *frozen_mask, size_t B,
                int *u_hat, double *pm_out, unsigned *flags, unsigned *iters = nullptr, unsigned *graph = nullptr,
-               unsigned *total = nullptr)
+               unsigned *total = nullptr, int *sets = nullptr)
 {
     if (!c || !in || !u_hat) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
@@ -721,6 +807,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     if (iters && (rc = ensure(c, c->bp_iters, B * sizeof(uint32_t)))) return rc;
     if (graph && (rc = ensure(c, c->bpl_graph, B * sizeof(uint32_t)))) return rc;
     if (total && (rc = ensure(c, c->bpl_total, B * sizeof(uint32_t)))) return rc;
+    if (sets && (rc = ensure(c, c->scf_hsets, B * polar::SCF_MAX_ORDER * sizeof(int32_t)))) return rc;
     // Chunked pipeline: while chunk k is decoded, chunk k+1 crosses PCIe on a second stream and the decisions of
     // chunk k-1 are unpacked to the caller's int array by helper threads.  The input is pageable caller memory: a
     // hipMemcpyAsync from it is a single-threaded staging copy inside the runtime (about 18 GB/s) that blocks this thread.
@@ -824,7 +911,8 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
         rc = decode_device_impl(c, c->in2[s].p, 0, sigma, nf, (uint32_t *)c->bits2[s].p, (double *)c->pm.p + f0,
                                 (uint32_t *)c->flags.p + f0, d_frozen, iters ? (uint32_t *)c->bp_iters.p + f0 : nullptr, nullptr,
                                 nullptr, graph ? (uint32_t *)c->bpl_graph.p + f0 : nullptr,
-                                total ? (uint32_t *)c->bpl_total.p + f0 : nullptr);
+                                total ? (uint32_t *)c->bpl_total.p + f0 : nullptr,
+                                sets ? (int32_t *)c->scf_hsets.p + f0 * polar::SCF_MAX_ORDER : nullptr);
         if (rc) return fail_join(rc);
         if (hipEventRecord(c->ev_free[s], c->stream) != hipSuccess) return fail_join(POLAR_EDEVICE);
         if (hipMemcpyAsync(c->h_bits[s], c->bits2[s].p, nf * NW * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) !=
@@ -844,6 +932,8 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
     if (iters) HIP_TRY(c, hipMemcpyAsync(iters, c->bp_iters.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (graph) HIP_TRY(c, hipMemcpyAsync(graph, c->bpl_graph.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (total) HIP_TRY(c, hipMemcpyAsync(total, c->bpl_total.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (sets)
+        HIP_TRY(c, hipMemcpyAsync(sets, c->scf_hsets.p, B * polar::SCF_MAX_ORDER * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return POLAR_OK;
 }
@@ -1408,6 +1498,53 @@ int polar_scf_set_flips(polar_ctx *c, int T)
     c->scf_T = T;
     refresh_kernel_name(c);
     return POLAR_OK;
+}
+
+int polar_scf_set_dynamic(polar_ctx *c, const int *budgets, int omega, double cc, double tau)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF || omega < 0 || omega > POLAR_SCF_MAX_ORDER) return POLAR_EINVAL;
+    if (omega == 0) {   // back to the static rule; T stays
+        c->scf_omega = 0;
+        refresh_kernel_name(c);
+        return POLAR_OK;
+    }
+    if (!budgets || !std::isfinite(cc) || !std::isfinite(tau) || cc < 0 || tau < 0) return POLAR_EINVAL;
+    for (int k = 0; k < omega; ++k)
+        if (budgets[k] < 1 || budgets[k] > polar::SCF_MAX_T || (k == 0 && budgets[k] > c->A)) return POLAR_EINVAL;
+    c->scf_omega = omega;
+    c->scf_T = budgets[0];
+    for (int k = 0; k < POLAR_SCF_MAX_ORDER; ++k) c->scf_Tk[k] = k < omega ? budgets[k] : 0;
+    c->scf_c = cc;
+    c->scf_tau = tau;
+    refresh_kernel_name(c);
+    return POLAR_OK;
+}
+
+int polar_scf_get_dynamic(const polar_ctx *c, int *omega, int *budgets, double *cc, double *tau)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
+    if (omega) *omega = c->scf_omega;
+    if (budgets)
+        for (int k = 0; k < POLAR_SCF_MAX_ORDER; ++k) budgets[k] = k == 0 ? c->scf_T : k < c->scf_omega ? c->scf_Tk[k] : 0;
+    if (cc) *cc = c->scf_omega ? c->scf_c : 0.0;
+    if (tau) *tau = c->scf_omega ? c->scf_tau : 0.0;
+    return POLAR_OK;
+}
+
+int polar_scf_decode_sets_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
+                                 uint32_t *d_flags, uint32_t *d_attempts, int32_t *d_sets)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
+    DeviceGuard guard(c->cfg.device);
+    return decode_device_impl(c, d_in, in_is_f32, sigma, B, d_uhat_bits, nullptr, d_flags, c->d_frozen, d_attempts, nullptr,
+                              nullptr, nullptr, nullptr, d_sets);
+}
+
+int polar_scf_decode_sets_batch(polar_ctx *c, const double *llr_in, size_t B, int *u_hat, unsigned *flags, unsigned *attempts,
+                                int *sets)
+{
+    if (!c || c->cfg.algo != POLAR_ALGO_SCF) return POLAR_EINVAL;
+    return host_batch(c, llr_in, 0.0, nullptr, B, u_hat, nullptr, flags, attempts, nullptr, nullptr, sets);
 }
 
 int polar_scf_decode_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,

@@ -68,6 +68,13 @@ struct polar_ctx : Lane {
     // SC-Flip (POLAR_ALGO_SCF): flip budget T (polar_scf_set_flips), the failing frames' flip positions, pass B's pairs
     int scf_T = 8;
     Buf scf_flips, scf_pass, scf_bits;
+    // its dynamic rule (polar_scf_set_dynamic): order (0: the static rule), budgets T_2, T_3 (T_1 is scf_T), c and tau; the
+    // flip sets of the level that runs and of the next one, the pairs' lists (keys, leaves, lengths), per failing frame
+    // whether a pair passed, and the slots of the frames that go on to the next level
+    int scf_omega = 0, scf_Tk[3] = {0, 0, 0};
+    double scf_c = 0.0, scf_tau = 0.0;
+    Buf scf_sets[2], scf_lkey, scf_lpos, scf_lcnt, scf_spass, scf_surv;
+    Buf scf_hsets;                        // polar_scf_decode_sets_batch: staging of the reported sets
     // BP list decoding (POLAR_ALGO_BPL): the graphs pi_p[b] (polar_bpl_set_graphs), per graph whether it is the identity,
     // and on the device sigma_p, its inverse, the permuted frozen masks and (with a CRC) the permuted CRC tables; the
     // attempts' round trips per open frame, and graph / total_iters of the host-pointer entry points.  The open-frame lists
@@ -273,10 +280,17 @@ int bpl_gather(polar_ctx *c, const void *d_src, bool in32, void *d_dst, const ui
 int bpl_scatter(polar_ctx *c, const uint32_t *s_bits, const uint32_t *s_iters, const uint32_t *s_flags, const uint32_t *d_idx,
                 size_t base, size_t n, const uint16_t *d_sinv, uint32_t need, int p, int P, bool all, uint32_t *d_bits,
                 uint32_t *d_iters, uint32_t *d_flags, uint32_t *d_graph, uint32_t *d_total);
-// k_scf.hip: SC-Flip (scf_lanes.h); mode = polar::SCF_CHECK | SCF_RECORD | SCF_FLIP
+// k_scf.hip: SC-Flip (scf_lanes.h); mode = polar::SCF_CHECK | SCF_RECORD | SCF_FLIP, and SCF_RECORD_M | SCF_FLIPSET |
+// SCF_FLIPREC of the dynamic rule
 int scf_lanes(polar_ctx *c, const polar::ScfParams &P, int mode, bool r32, bool in32);
 int scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, const uint32_t *d_idx, size_t n, int T,
                 uint32_t *d_bits, uint32_t *d_flags, uint32_t *d_attempts);
+int scf_resolve_sets(polar_ctx *c, const uint32_t *d_pass, const uint32_t *d_pbits, const uint32_t *d_idx, size_t n, int T,
+                     const uint16_t *d_sets_in, int stride, int width, int base, uint32_t *d_bits, uint32_t *d_flags,
+                     uint32_t *d_attempts, int32_t *d_sets, uint32_t *d_slot_pass);
+int scf_merge(polar_ctx *c, bool r32, const void *d_lkey, const uint16_t *d_lpos, const uint32_t *d_lcnt,
+              const uint16_t *d_psets, const uint32_t *d_surv, const uint32_t *d_idx_in, size_t n, int Tk, int Tn,
+              uint16_t *d_out_sets, uint32_t *d_idx_out);
 // k_rm.hip: 5G rate matching (rm_kernel.h): recovery [B][E] -> [B][N] of the input type, generator [B][E]
 int rm_recover(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t B, void *d_out);
 int rm_generate(polar_ctx *c, const polar::GenParams &G);

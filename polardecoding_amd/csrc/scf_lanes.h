@@ -11,6 +11,13 @@
 //               Writes the T flip positions, ascending |lambda|, ties to the smaller j.
 //   SCF_FLIP    (pass B, one lane per (failing frame, attempt t)) SC with the decision at leaf p_t inverted; the inverted bit
 //               enters the partial sums of every later leaf.  Writes the decisions and the CRC pass bit of the pair.
+// The dynamic rule (polar_scf_set_dynamic, include/polar_hip.h) adds three policies; a static context launches none of them:
+//   SCF_RECORD_M  SCF_RECORD on the key M(0, j) = |lambda_j| + c * cnt_j, cnt_j the running count of information leaves with
+//               |lambda| <= tau.  Writes the list itself (keys, leaves, length) for k_scf_merge.
+//   SCF_FLIPSET (one lane per (failing frame, flip set E)) run(E): up to three ascending flip leaves per lane.  The next one
+//               sits in a cursor that advances at each hit, so a leaf costs one compare.  Writes what SCF_FLIP writes.
+//   SCF_FLIPREC run(E) as SCF_FLIPSET, and in the same run the lane's Tn smallest (M(E, j), j) over j > max(E): F_E
+//               accumulates as the flipped leaves are reached, cnt counts from leaf 0.  Writes decisions, pass bit and list.
 // Why the list is not kept in pass A: T = 32 at N = 2048 in f64 needs 24 KiB of LDS per wavefront on top of k_sc_lanes's
 // 24 KiB, which halves the resident wavefronts of a pass that runs on every frame; re-decoding only the failing frames costs
 // 1/T of pass B instead.
@@ -24,14 +31,17 @@ namespace polar {
 
 template <typename R>
 struct ScfCfg {
-    static constexpr int WAVES = 4;   // at most; fewer when the SCF_RECORD list does not fit 160 KiB (N = 2048, f64, T > 16)
+    static constexpr int WAVES = 4;   // at most; fewer when the list of a recording policy does not fit 160 KiB (N = 2048, f64, T > 16)
+    static constexpr bool keeps_list(int mode) { return mode == SCF_RECORD || mode == SCF_RECORD_M || mode == SCF_FLIPREC; }
     static constexpr size_t list_bytes(int T) { return (size_t)T * 64 * (sizeof(R) + sizeof(uint32_t)); }
     static constexpr size_t wave_bytes(int N, int T, int mode)
     {
-        return ScLanesCfg<R>::wave_bytes(N) + (mode == SCF_RECORD ? list_bytes(T) : 0);
+        return ScLanesCfg<R>::wave_bytes(N) + (keeps_list(mode) ? list_bytes(T) : 0);
     }
     static constexpr size_t lds_bytes(int N, int T, int mode, int waves) { return wave_bytes(N, T, mode) * waves + Lut<R>::bytes; }
 };
+
+constexpr int SCF_NO_LEAF = 0x7fffffff;   // above every leaf index
 
 template <typename R, int MODE>
 struct ScfLanes {
@@ -46,6 +56,10 @@ struct ScfLanes {
     uint32_t *pos;            // SCF_RECORD: its leaf
     int nT, cnt;              // SCF_RECORD: list length, entries filled
     R thr;                    // SCF_RECORD: key[(nT - 1) * 64] once the list is full
+    int nf, f1, f2;           // SCF_FLIPSET, SCF_FLIPREC: the next leaf to invert and the two after it (SCF_NO_LEAF: none)
+    int maxE;                 // SCF_RECORD_M, SCF_FLIPREC: leaves above it are recorded (-1: all; SCF_NO_LEAF: none)
+    int tcnt;                 // SCF_RECORD_M, SCF_FLIPREC: information leaves so far with |lambda| <= tau
+    R F, mc, tau;             // SCF_FLIPREC: sum of |lambda| over the flipped leaves so far; the rule's c and tau in R
 
     __device__ __forceinline__ void record(R v, int j)
     {
@@ -74,9 +88,26 @@ struct ScfLanes {
         if constexpr (T == 0) {
             uint32_t bit = (a[0] < R(0)) ? 1u : 0u;
             if constexpr (MODE == SCF_FLIP) bit ^= (j0 + K0 == flip) ? 1u : 0u;
+            if constexpr (MODE >= SCF_RECORD_M) {
+                const int j = j0 + K0;
+                const R v = absr(a[0]);
+                if constexpr (MODE != SCF_FLIPSET) tcnt += (v <= tau) ? 1 : 0;
+                if constexpr (MODE != SCF_RECORD_M) {
+                    if (j == nf) {
+                        bit ^= 1u;
+                        if constexpr (MODE == SCF_FLIPREC) F = F + v;
+                        nf = f1;
+                        f1 = f2;
+                        f2 = SCF_NO_LEAF;
+                    }
+                }
+                if constexpr (MODE != SCF_FLIPSET) {
+                    if (j > maxE) record((F + v) + mc * (R)tcnt, j);   // rule 3: each operation rounded once (-ffp-contract=off)
+                }
+            }
             if constexpr (MODE == SCF_RECORD) {
                 record(absr(a[0]), j0 + K0);
-            } else {
+            } else if constexpr (MODE != SCF_RECORD_M) {
                 const uint32_t t = ctab[K0];
                 crc ^= bit ? t : 0u;
             }
@@ -113,13 +144,14 @@ __global__ __launch_bounds__(256, (ScLanesCfg<R>::MIN_WAVES_PER_SIMD)) void k_sc
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int waves = (int)(blockDim.x >> 6);
     const int nT = P.T;
+    const int nL = (MODE >= SCF_RECORD_M) ? P.Tn : nT;   // length of the list in LDS
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *mine = smem + (size_t)wave * Cfg::wave_bytes(N, nT, MODE);
+    unsigned char *mine = smem + (size_t)wave * Cfg::wave_bytes(N, nL, MODE);
     uint32_t *blw = reinterpret_cast<uint32_t *>(mine);          // [NW][64]: saved left partial sums
     uint32_t *curw = blw + (size_t)NW * 64;                      // [NW/2][64] working partial sums
     R *lkey = reinterpret_cast<R *>(mine + ScLanesCfg<R>::wave_bytes(N)) + lane;    // SCF_RECORD: [T][64]
-    uint32_t *lpos = reinterpret_cast<uint32_t *>(lkey - lane + (size_t)nT * 64) + lane;
-    unsigned char *lut_mem = smem + (size_t)waves * Cfg::wave_bytes(N, nT, MODE);
+    uint32_t *lpos = reinterpret_cast<uint32_t *>(lkey - lane + (size_t)nL * 64) + lane;
+    unsigned char *lut_mem = smem + (size_t)waves * Cfg::wave_bytes(N, nL, MODE);
     Lut<R>::build(lut_mem, threadIdx.x, blockDim.x);
     Lut<R> lut;
     lut.bind(lut_mem);
@@ -139,12 +171,26 @@ __global__ __launch_bounds__(256, (ScLanesCfg<R>::MIN_WAVES_PER_SIMD)) void k_sc
         int flip = -1;
         if (have) {
             if constexpr (MODE == SCF_CHECK) frame = (size_t)item;
-            else if constexpr (MODE == SCF_RECORD) frame = P.idx[item];
+            else if constexpr (MODE == SCF_RECORD || MODE == SCF_RECORD_M) frame = P.idx[item];
             else {
                 frame = P.idx[item / nT];
-                flip = (int)P.flips[item];
+                if constexpr (MODE == SCF_FLIP) flip = (int)P.flips[item];
             }
         }
+        int nf = SCF_NO_LEAF, f1 = SCF_NO_LEAF, f2 = SCF_NO_LEAF, maxE = SCF_NO_LEAF;
+        if constexpr (MODE == SCF_RECORD_M) maxE = -1;
+        if constexpr (MODE == SCF_FLIPSET || MODE == SCF_FLIPREC) {
+            if (have) {   // an absent set (a level's list was shorter than its budget) inverts nothing and never passes
+                const uint16_t *e = P.flips + (size_t)item * SCF_MAX_ORDER;
+                if (e[0] != SCF_NO_POS) nf = maxE = (int)e[0];
+                if (e[1] != SCF_NO_POS) f1 = maxE = (int)e[1];
+                if (e[2] != SCF_NO_POS) f2 = maxE = (int)e[2];
+            }
+        }
+        const bool valid = nf != SCF_NO_LEAF;
+        int tcnt = 0;
+        R F = R(0);
+        const R mc = (R)P.mc, tau = (R)P.tau;
         const IN *row = reinterpret_cast<const IN *>(P.in) + frame * N;
         const bool al16 = ((reinterpret_cast<uintptr_t>(P.in) | ((size_t)N * sizeof(IN))) & 15u) == 0;   // uniform
         auto chan16 = [&](int e0, R *dst) {
@@ -295,7 +341,8 @@ __global__ __launch_bounds__(256, (ScLanesCfg<R>::MIN_WAVES_PER_SIMD)) void k_sc
             uint32_t beta = 0, dec = 0;
             const uint32_t fz = (uint32_t)__builtin_amdgcn_readlane((int)fwv, b & 63);
             if (live && fz != 0xFFFFFFFFu) {
-                ScfLanes<R, MODE> S{lut, fz, 0u, b << 5, P.crc_tab + (b << 5), crc, flip, lkey, lpos, nT, cnt, thr};
+                ScfLanes<R, MODE> S{lut, fz, 0u, b << 5, P.crc_tab + (b << 5), crc, flip, lkey, lpos, nL, cnt, thr,
+                                    nf, f1, f2, maxE, tcnt, F, mc, tau};
                 uint32_t bl = 0, br = 0;
                 if (n == 5) {
                     chan16(0, x5);
@@ -321,13 +368,24 @@ __global__ __launch_bounds__(256, (ScLanesCfg<R>::MIN_WAVES_PER_SIMD)) void k_sc
                 crc = S.crc;
                 cnt = S.cnt;
                 thr = S.thr;
+                if constexpr (MODE >= SCF_RECORD_M) {
+                    nf = S.nf;
+                    f1 = S.f1;
+                    f2 = S.f2;
+                    tcnt = S.tcnt;
+                    F = S.F;
+                }
             }
-            if constexpr (MODE != SCF_RECORD) {
+            if constexpr (MODE != SCF_RECORD && MODE != SCF_RECORD_M) {
                 if (have) P.out_bits[(size_t)item * NW + b] = dec;
             }
             // ---- partial sums upwards (k_sc_lanes) ----
             int t = 5;
-            curw[lane] = beta;
+            if constexpr (MODE >= SCF_RECORD_M) {
+                if (n > 5) curw[lane] = beta;   // N = 32 has no curw ([NW/2][64]): the word after blw is the list's first key
+            } else {
+                curw[lane] = beta;
+            }
             while (t < n - 1 && ((b >> (t - 5)) & 1)) {
                 const int nw = 1 << (t - 5);
                 for (int w = 0; w < nw; ++w) {
@@ -351,8 +409,19 @@ __global__ __launch_bounds__(256, (ScLanesCfg<R>::MIN_WAVES_PER_SIMD)) void k_sc
                 if (P.attempts) P.attempts[item] = pass ? 0u : (uint32_t)nT;
             } else if constexpr (MODE == SCF_FLIP) {
                 P.flags[item] = pass ? 1u : 0u;
-            } else {
+            } else if constexpr (MODE == SCF_RECORD) {
                 for (int i = 0; i < nT; ++i) P.flips[(size_t)item * nT + i] = (uint16_t)lpos[i * 64];
+            } else {
+                if constexpr (MODE != SCF_RECORD_M) P.flags[item] = (pass && valid) ? 1u : 0u;
+                if constexpr (MODE != SCF_FLIPSET) {
+                    R *ok = reinterpret_cast<R *>(P.lkey) + (size_t)item * nL;
+                    uint16_t *op = P.lpos + (size_t)item * nL;
+                    for (int i = 0; i < cnt; ++i) {
+                        ok[i] = lkey[i * 64];
+                        op[i] = (uint16_t)lpos[i * 64];
+                    }
+                    P.lcnt[item] = (uint32_t)cnt;
+                }
             }
         }
     }
@@ -378,6 +447,86 @@ __global__ __launch_bounds__(256) void k_scf_resolve(const uint32_t *__restrict_
         if (w == 0) {
             if (flags) flags[f] |= SCF_CRC_PASS;
             if (attempts) attempts[f] = (uint32_t)(t + 1);
+        }
+    }
+}
+
+// k_scf_resolve for flip sets.  Pair k * T + t - 1 of failing frame k ran the set sets[(k * T + t - 1) * stride ..+ width)
+// (a static context's flip list: stride = width = 1).  The smallest passing t is global attempt base + t; d_sets
+// (nullable, [frames][3]) gets its set, -1 padded.  slot_pass (nullable, [n]) gets 1 where a pair of the frame passed and
+// 0 elsewhere: the flags the next level's compaction reads.
+__global__ __launch_bounds__(256) void k_scf_resolve_sets(const uint32_t *__restrict__ pass, const uint32_t *__restrict__ pbits,
+                                                          const uint32_t *__restrict__ idx, long long n, int T, int logNW,
+                                                          const uint16_t *__restrict__ sets, int stride, int width, int base,
+                                                          uint32_t *__restrict__ bits, uint32_t *__restrict__ flags,
+                                                          uint32_t *__restrict__ attempts, int32_t *__restrict__ d_sets,
+                                                          uint32_t *__restrict__ slot_pass)
+{
+    const long long total = n << logNW;
+    const long long wmask = (1ll << logNW) - 1;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long long)gridDim.x * 256) {
+        const long long k = q >> logNW, w = q & wmask;
+        int t = 0;
+        while (t < T && !pass[k * T + t]) ++t;
+        if (w == 0 && slot_pass) slot_pass[k] = t < T ? 1u : 0u;
+        if (t == T) continue;
+        const long long f = idx[k];
+        bits[(f << logNW) + w] = pbits[((k * T + t) << logNW) + w];
+        if (w == 0) {
+            if (flags) flags[f] |= SCF_CRC_PASS;
+            if (attempts) attempts[f] = (uint32_t)(base + t + 1);
+            if (d_sets) {
+                for (int e = 0; e < SCF_MAX_ORDER; ++e) {
+                    const uint16_t p = e < width ? sets[(k * T + t) * stride + e] : SCF_NO_POS;
+                    d_sets[f * SCF_MAX_ORDER + e] = p == SCF_NO_POS ? -1 : (int32_t)p;
+                }
+            }
+        }
+    }
+}
+
+// Rule 5 of the dynamic rule: the sets of the next level.  One thread per still-failing frame s, which sat in slot
+// o = surv[s] of the level that just ran (surv null: o = s, nothing was compacted).  Its Tk pairs o * Tk + q kept sorted
+// lists (lkey, lpos, lcnt: Tn entries at most, SCF_RECORD_M / SCF_FLIPREC); a Tk-way merge emits the Tn smallest
+// (M, q, i): the heads are scanned in ascending q with a strict compare, so equal M goes to the smaller q, and a list is
+// in (M, i) order already.  Comparisons only.  out_sets[(s * Tn + r) * 3 ..] = E_q with i appended (psets null: E_q is
+// empty), absent sets where the candidates run out; idx_out[s] = idx_in[o] when the frames were compacted.
+template <typename R>
+__global__ __launch_bounds__(256) void k_scf_merge(const R *__restrict__ lkey, const uint16_t *__restrict__ lpos,
+                                                   const uint32_t *__restrict__ lcnt, const uint16_t *__restrict__ psets,
+                                                   const uint32_t *__restrict__ surv, const uint32_t *__restrict__ idx_in,
+                                                   long long n, int Tk, int Tn, uint16_t *__restrict__ out_sets,
+                                                   uint32_t *__restrict__ idx_out)
+{
+    for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < n; s += (long long)gridDim.x * 256) {
+        const long long o = surv ? (long long)surv[s] : s;
+        if (surv) idx_out[s] = idx_in[o];
+        unsigned char head[SCF_MAX_T];
+        for (int q = 0; q < Tk; ++q) head[q] = 0;
+        for (int r = 0; r < Tn; ++r) {
+            int best = -1;
+            R bk = R(0);
+            for (int q = 0; q < Tk; ++q) {
+                const long long it = o * Tk + q;
+                if (head[q] >= lcnt[it]) continue;
+                const R k = lkey[it * Tn + head[q]];
+                if (best < 0 || k < bk) {
+                    best = q;
+                    bk = k;
+                }
+            }
+            uint16_t *e = out_sets + (s * Tn + r) * SCF_MAX_ORDER;
+            if (best < 0) {
+                e[0] = e[1] = e[2] = SCF_NO_POS;
+                continue;
+            }
+            const long long it = o * Tk + best;
+            int m = 0;
+            if (psets)
+                for (; m < SCF_MAX_ORDER - 1 && psets[it * SCF_MAX_ORDER + m] != SCF_NO_POS; ++m) e[m] = psets[it * SCF_MAX_ORDER + m];
+            e[m++] = lpos[it * Tn + head[best]];
+            for (; m < SCF_MAX_ORDER; ++m) e[m] = SCF_NO_POS;
+            ++head[best];
         }
     }
 }

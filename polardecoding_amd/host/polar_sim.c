@@ -216,6 +216,8 @@ static void usage(void)
                     "                 [--bp-stop g]   (bp: stop a frame once u_hat F == x_hat; one stderr line of iteration counts per point)\n"
                     "                 [--stages 1,8,32]   (cascl: adaptive list sizes, re-decode only CRC-failing frames; last = --L)\n"
                     "                 [--flips T]   (scf: CRC-aided SC-Flip with up to T single-flip attempts per failing frame; default 8)\n"
+                    "                 [--flips T1,T2[,T3]] [--scf-metric c,tau]   (scf: dynamic SC-Flip, T_k flip sets of size k ranked by\n"
+                    "                     M = sum of |lambda| + c * #{|lambda| <= tau}; default metric 0,0)\n"
                     "                 [--iters I]   (scan: soft-output SCAN with I iterations, 1..64; default 4)\n"
                     "                 [--graphs P]   (bpl: BP list decoding on the first P cyclic shifts of the stage order, 1..32; default min(n, 8);\n"
                     "                                  --bp-iters per attempt; --crc 24c|6: CRC-aided, without it no CRC)\n"
@@ -232,6 +234,9 @@ int main(int argc, char **argv)
     int fast = 0, sys = 0, bpr = 0, gpus = 1, bp_stop = POLAR_BP_STOP_NONE;
     int stages[6], nstages = 0;   /* --stages: polar_cascl_set_stages */
     int flips = -1;               /* --flips: polar_scf_set_flips (-1: the library's default) */
+    int budgets[POLAR_SCF_MAX_ORDER] = {0, 0, 0}, nbudgets = 0;   /* --flips T1,T2[,T3]: polar_scf_set_dynamic */
+    double scf_c = 0, scf_tau = 0;
+    int have_metric = 0;          /* --scf-metric c,tau */
     int scan_iters = -1;          /* --iters: polar_scan_set_iters (-1: the library's default) */
     int graphs = -1;              /* --graphs: polar_bpl_set_graphs with P cyclic shifts (-1: the library's default list) */
     int rm_E = 0, rm_ibil = 0;    /* --E / --ibil: polar_create_rm (0: no rate matching) */
@@ -298,7 +303,20 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--flips") && v) {
             char *end;
             flips = (int)strtol(v, &end, 10);
-            if (end == v || *end) usage();
+            if (end == v) usage();
+            budgets[0] = flips;
+            nbudgets = 1;
+            while (*end == ',' && nbudgets < POLAR_SCF_MAX_ORDER) {
+                const char *q = end + 1;
+                budgets[nbudgets++] = (int)strtol(q, &end, 10);
+                if (end == q) usage();
+            }
+            if (*end) usage();
+            i++;
+        }
+        else if (!strcmp(a, "--scf-metric") && v) {
+            if (sscanf(v, "%lf,%lf", &scf_c, &scf_tau) != 2) usage();
+            have_metric = 1;
             i++;
         }
         else if (!strcmp(a, "--iters") && v) {
@@ -454,6 +472,19 @@ int main(int argc, char **argv)
         if (algo != POLAR_ALGO_SCF) { fprintf(stderr, "--flips: only with --algo scf\n"); return 1; }
         if (fast && gpus > 1) { fprintf(stderr, "--flips: not with --gpus > 1\n"); return 1; }
         if ((rc = polar_scf_set_flips(ctx, flips)) != 0) { fprintf(stderr, "--flips: %s\n", polar_strerror(rc)); return 1; }
+    }
+    if (nbudgets > 1 || have_metric) {
+        /* a polar_group builds its contexts from cfg and runs the static default */
+        if (algo != POLAR_ALGO_SCF) { fprintf(stderr, "--scf-metric: only with --algo scf\n"); return 1; }
+        if (fast && gpus > 1) { fprintf(stderr, "--flips T1,T2 / --scf-metric: not with --gpus > 1\n"); return 1; }
+        if (nbudgets == 0) {   /* the metric alone: on the context's T */
+            if ((rc = polar_scf_get_dynamic(ctx, NULL, budgets, NULL, NULL)) != 0) { fprintf(stderr, "--scf-metric: %s\n", polar_strerror(rc)); return 1; }
+            nbudgets = 1;
+        }
+        if ((rc = polar_scf_set_dynamic(ctx, budgets, nbudgets, scf_c, scf_tau)) != 0) {
+            fprintf(stderr, "--flips / --scf-metric: %s\n", polar_strerror(rc));
+            return 1;
+        }
     }
     if (scan_iters >= 0) {
         /* a polar_group builds its contexts from cfg and runs the default I */
