@@ -7,6 +7,10 @@
 // of least metric among the live slots that pass the CRC (among all live slots if none passes or there is no CRC).  The
 // arithmetic is chk_lut / lut.tabv / gfun in the same operation order, so the results equal scl_generic_body's bit for bit
 // wherever both exist, and the CPU model's (tests/test_dyn_host.py dscl_model) everywhere.
+// "Everywhere" includes the frames with a median tie: tests/test_gpu_wide.py holds that at L = 64 (one wavefront, N = 32 on
+// a grid), tests/test_gpu_wide_families.py at L = 128 and 256 (2 and 4 wavefronts) on tied and degenerate rows, frozen sets
+// outside the 5G order and dense constraint sets, where dead slots stay un-refilled, refills cross wavefronts and leaves
+// have all 2L candidates equal (tests/test_wide_families_host.py asserts that the cases do).
 //
 // What differs is the mapping.  scl_generic_body gives a path S = 64 / L lanes of one wavefront and moves state between paths
 // with __shfl / __ballot; that stops at 64 lanes.  Here one codeword has a workgroup of L threads (1, 2 or 4 wavefronts),

@@ -16,6 +16,7 @@ of the mask is dynamic unless stated:
   dyn_chain       S_j = the nearest earlier information position and the two nearest earlier dynamic positions
   alternate       every second frozen position dynamic with bern_half sets, the others plain frozen
   pac             polar_dyn_pac with g = 0o133 on the mask's information set
+  none            (a Case's family only, not in FAMILIES) no constraints: dyn = None, a plain context (tests/wide_families.py)
 
 Every set obeys the ABI: i < j, ascending, position frozen under the cfg; a set may hold information, dynamic and plain
 frozen positions.  Everything is a function of (N, mask, seed) alone.
@@ -43,6 +44,7 @@ import test_dyn_host as M  # noqa: E402
 
 G133 = 0o133
 CRC6 = (0, 5, 6)
+NONE = "none"
 FAMILIES = ("all_prev", "bern_half", "prev_only", "word0_only", "own_word_only", "word_edges", "dyn_chain", "alternate", "pac")
 
 
@@ -194,7 +196,7 @@ def materialise(c):
     """Made(mask, info_order, (pos, sets), CRC taps or None, u [B][N], OrderedDict input name -> rows [B][N] of the dtype)"""
     if c not in _MADE:
         mask, order = mask_of(c.N, c.mask)
-        dyn = constraint_families(c.N, mask, 5)[c.fam]
+        dyn = None if c.fam == NONE else constraint_families(c.N, mask, 5)[c.fam]
         taps = CRC6 if c.algo == "CASCL" else None
         u, llr = M.make_frames(c.N, order, dyn, c.B, _seed(c), dbs=c.dbs, crc=taps)
         batches = OrderedDict((k, input_batch(llr, k, _seed(c), np_dtype(c))) for k in c.inputs)

@@ -62,10 +62,14 @@ def _parity32(x):
     return (x & np.uint32(1)).astype(np.uint8)
 
 
-def dscl_model(frozen, dyn, llr, L, crc=None, dtype=np.float64, sc=None, oracle=None):
+def dscl_model(frozen, dyn, llr, L, crc=None, dtype=np.float64, sc=None, oracle=None, trace=None):
     """frozen [N] (1 = frozen under the cfg, dynamic positions included), dyn = (pos, sets) or None, llr [B][N], list size
     L, crc = (info_order, taps) or None, arithmetic dtype.  sc: SC decisions (no metric, no flags); default L == 1 without a
-    CRC.  Returns (u_hat [B][N] int32, pm [B] float64, flags [B] uint32)."""
+    CRC.  Returns (u_hat [B][N] int32, pm [B] float64, flags [B] uint32).
+    trace: a dict that receives four bool arrays [B], each true where some phase-2 leaf of the frame had the property --
+    "tie" (fewer than L candidates survive), "cross" (a refilled slot and its source slot lie in different groups of 64
+    slots), "unrefilled" (a dead slot is not refilled), "all_equal" (the 2L candidates are all equal).  The results do not
+    depend on it."""
     if oracle is None:
         from oracle import oracle_py as oracle
     frozen = np.asarray(frozen)
@@ -95,6 +99,8 @@ def dscl_model(frozen, dyn, llr, L, crc=None, dtype=np.float64, sc=None, oracle=
     PM = np.zeros((B, L), dtype=dtype)
     tie = np.zeros(B, dtype=bool)
     act = 1
+    if trace is not None:
+        trace.update({k: np.zeros(B, dtype=bool) for k in ("tie", "cross", "unrefilled", "all_equal")})
 
     def level(buf, ptr, t):
         if t == n:
@@ -153,6 +159,11 @@ def dscl_model(frozen, dyn, llr, L, crc=None, dtype=np.float64, sc=None, oracle=
             c1_s = np.take_along_axis(c1, sg, axis=1)
             bit = np.where(refill, 1, np.where(s0, 0, np.where(s1, 1, 0))).astype(np.uint8)
             PM = np.where(refill, c1_s, np.where(s0, c0, np.where(s1, c1, c0)))
+            if trace is not None:
+                trace["tie"] |= (s0.sum(1) + s1.sum(1)) < L
+                trace["cross"] |= (refill & ((sg >> 6) != (slot[None, :] >> 6))).any(1)
+                trace["unrefilled"] |= (dead & ~refill).any(1)
+                trace["all_equal"] |= cand.min(1) == cand.max(1)
         if sg is not None:
             pa = np.take_along_axis(pa, sg[:, :, None], axis=1)
             pb = np.take_along_axis(pb, sg[:, :, None], axis=1)

@@ -6,7 +6,10 @@ mechanism first exists: N = 32 (the whole history in registers, one wavefront), 
 ranking, refill and exchange across wavefronts, history words in LDS), L = 256 in f32 (levels in LDS), in f64 and under the
 test library's spill switch (levels in global scratch), the CRC mask on the final choice, the three shapes that fill the
 64-bit pointer table (60, 63 and 64 bits), the work queue, the input forms, the FER gain over L = 32 and the refusal of
-adaptive stages.  Model cost at N = 128 is 12 / 28 / 74 ms per frame for L = 64 / 128 / 256, hence the batch sizes."""
+adaptive stages.  Model cost at N = 128 is 12 / 28 / 74 ms per frame for L = 64 / 128 / 256, hence the batch sizes.
+
+The tied rows here are at N = 32, L = 64 (one wavefront); the rows at L = 128 and 256 are Gaussian and tie in no frame.  Ties,
+un-refilled dead slots and refills across wavefronts at L = 128 and 256 are in tests/test_gpu_wide_families.py."""
 import functools
 import os
 import sys

@@ -3,7 +3,9 @@
 code lengths, rates, CRCs, both arithmetic types, ragged batch sizes.  Developer tool (tests/ holds the fixed cases).
 --patterns: every configuration on a frozen set of tests/frozen_patterns.py (picked by the tool's rng) instead of the 5G set.
 --dyn FAMILY: instead of the sweep above, k_scl_dyn against the numpy model of tests/test_dyn_host.py (bits, metric, flags by
-==, tie frames included) on a constraint family of tests/dyn_families.py, at larger B than tests/test_gpu_dyn_families.py."""
+==, tie frames included) on a constraint family of tests/dyn_families.py, at larger B than tests/test_gpu_dyn_families.py.
+--wide: instead of the sweep above, k_scl_wide at L = 128 / 256 against the same model on the cases of tests/wide_families.py
+(groups w1 .. w7) with the seed given here and --wide-scale times the frames of tests/test_gpu_wide_families.py."""
 import argparse, itertools, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,6 +22,10 @@ ap.add_argument("--patterns", action="store_true",
                 help="a frozen set outside the 5G order (tests/frozen_patterns.py) per configuration, K = its size less the CRC")
 ap.add_argument("--dyn", choices=("pac", "all_prev", "bern_half"), default=None,
                 help="dynamic frozen bits: this constraint family on the PAC rm mask, against the numpy model")
+ap.add_argument("--wide", action="store_true",
+                help="wide lists: the cases of tests/wide_families.py with this seed, against the numpy model")
+ap.add_argument("--wide-scale", type=int, default=4, help="--wide: frames per case, as a multiple of the test's")
+ap.add_argument("--wide-groups", default="w1,w2,w3,w4,w5,w6,w7", help="--wide: the groups to run")
 args = ap.parse_args()
 rng = np.random.default_rng(args.seed)
 bad = 0
@@ -52,6 +58,35 @@ def dyn_sweep(family):
         bad += (not ok)
         dec.close()
 
+
+def wide_sweep(scale):
+    """k_scl_wide == dscl_model on every frame of every case of wide_families.cases() but the work-queue rows"""
+    global bad
+    import wide_families as WF
+    WF.SEED = args.seed
+    for c in WF.cases():
+        if c.group not in args.wide_groups.split(","):
+            continue
+        c = c._replace(B=c.B * scale)
+        made, (ref, tr) = WF.materialise(c), WF.reference(c)
+        K = made.order.size - (max(made.taps) if made.taps else 0)
+        dec = pa.Decoder(c.N, K, pa.ALGO_CASCL if made.taps else pa.ALGO_SCL, L=c.L, crc_taps=made.taps,
+                         dtype=pa.F32 if c.dtype == "f32" else pa.F64, info_order=made.order, dyn=made.dyn)
+        for name, rows in made.batches.items():
+            uh, pm, fl = dec.decode_batch(np.asarray(rows, dtype=np.float64))
+            want = ref[name]
+            ok = np.array_equal(uh, want[0]) and np.array_equal(pm, want[1]) and np.array_equal(np.asarray(fl).view(np.uint32), want[2])
+            t = tr[name]
+            print(f"{'ok ' if ok else 'BAD'} wide {WF.tag(c):52s} {name:16s} {dec.kernel_name[:28]:28s} tie={int(t['tie'].sum())} "
+                  f"unrefilled={int(t['unrefilled'].sum())} cross={int(t['cross'].sum())} all-equal={int(t['all_equal'].sum())}", flush=True)
+            bad += (not ok)
+        dec.close()
+
+
+if args.wide:
+    wide_sweep(args.wide_scale)
+    print(f"{bad} mismatching batches, {time.time() - t0:.0f} s")
+    sys.exit(1 if bad else 0)
 
 if args.dyn:
     dyn_sweep(args.dyn)
