@@ -30,6 +30,14 @@ int polar_testing_select_kernel(polar_ctx *ctx, int variant);
  * 0 = the measured best for the arithmetic type and list size. */
 int polar_testing_big_split(polar_ctx *ctx, int split);
 
+/* Seven host loops cut a batch into passes of at most 256 MiB of rows and offset every input, output and list pointer per
+ * pass (q8 rows, rate-matched rows, the later stages of adaptive CA-SCL, SC-Flip's pass B and the levels of its dynamic
+ * rule, BP list attempts, polar_construct_batch).  At that size a second pass needs batches no model can follow.  This
+ * sets the cap in bytes for ctx (and its stage contexts), so that the tests reach the second and later passes with a few
+ * hundred short frames; each loop's own floor (64 rows, or 1 frame for the SC-Flip loops) still holds.  0 restores
+ * 256 MiB.  The kernels and what they compute per frame do not depend on it. */
+int polar_testing_chunk_bytes(polar_ctx *ctx, size_t bytes);
+
 /* The kernels' scalar arithmetic on caller-chosen operands, one thread per element, through the SAME device
  * functions the decoders inline (csrc/polar_math.h, csrc/polar_lut.h):
  *   op 0  chk(a, b)        compare chain, CHK of SCL_1024.c:343-374

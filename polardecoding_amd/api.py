@@ -419,6 +419,7 @@ class Decoder:
         self.scf_dynamic = None   # None: the static rule; else (budgets, c, tau) of set_scf_dynamic
         self.scan_iters = None  # None: the library's default (4)
         self._bpl_graphs = None # None: the library's default list (min(n, 8) cyclic shifts)
+        self._chunk_bytes = 0   # test-only cap of the chunked passes (testing.chunk_bytes); 0: the library's 256 MiB
         self._rm = (int(E), 1 if ibil else 0) if E is not None else None
         self._dyn = None
         if dyn is not None:
@@ -485,6 +486,9 @@ class Decoder:
             self.set_systematic(True)
         if self._quant is not None:
             self.set_quant(*self._quant)
+        if self._chunk_bytes:   # only a test library has the setter
+            lib.polar_testing_chunk_bytes.argtypes = [C.c_void_p, C.c_size_t]
+            self._check(lib.polar_testing_chunk_bytes(self._h, self._chunk_bytes), "polar_testing_chunk_bytes")
 
     @property
     def info_order(self):

@@ -73,11 +73,11 @@ std::vector<uint32_t> make_crc_table(int N, int r, const std::vector<int> &taps,
     return tab;
 }
 
-// Rows per pass where a batch goes through ctx scratch in chunks: at most 256 MiB of rows, at least `floor` of them, never
-// more than the batch.
-size_t chunk_rows(size_t B, size_t row_bytes, size_t floor = 64)
+// Rows per pass where a batch goes through ctx scratch in chunks: at most c->chunk_bytes (256 MiB) of rows, at least `floor`
+// of them, never more than the batch.
+size_t chunk_rows(const polar_ctx *c, size_t B, size_t row_bytes, size_t floor = 64)
 {
-    return std::min(B, std::max(floor, ((size_t)256 << 20) / row_bytes));
+    return std::min(B, std::max(floor, c->chunk_bytes / row_bytes));
 }
 
 // contexts whose code carries a CRC: r, crc_tab, the generator's CRC multiply, the systematic K-bit error metric
@@ -245,7 +245,7 @@ int q8_decode_rows(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
     const size_t esz = in_is_f32 ? 4 : 8;
     if (reinterpret_cast<uintptr_t>(d_in) % esz) return POLAR_EINVAL;
     const size_t N = (size_t)c->cfg.N;
-    const size_t CH = chunk_rows(B, N);
+    const size_t CH = chunk_rows(c, B, N);
     int rc;
     if ((rc = ensure(c, c->q8_rows, CH * N))) return rc;
     if (d_pm && (rc = ensure(c, c->q8_pm, CH * sizeof(int32_t)))) return rc;
@@ -323,6 +323,7 @@ void sync_stage_ctx(polar_ctx *c)
         s->use_fast2 = c->use_fast2;
         s->use_fast4 = c->use_fast4;
         s->big_split = c->big_split;
+        s->chunk_bytes = c->chunk_bytes;
     }
 }
 
@@ -340,7 +341,7 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
     const int m = (int)st.size(), N = c->cfg.N, NW = c->NW;
     const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
     // later stages run in chunks of at most 256 MiB of gathered input
-    const size_t CH = chunk_rows(B, row);
+    const size_t CH = chunk_rows(c, B, row);
     int rc;
     // every buffer of the call, before its first launch
     if (!d_flags) {
@@ -443,7 +444,7 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
         for (int k = 0; k < omega; ++k) {
             pairs = std::max(pairs, n * (size_t)Tk[k]);
             ents = std::max(ents, n * (size_t)(k ? Tk[k - 1] : 1) * (size_t)Tk[k]);
-            chmax = std::max(chmax, chunk_rows(n, pair_bytes * (size_t)Tk[k], 1) * (size_t)Tk[k]);
+            chmax = std::max(chmax, chunk_rows(c, n, pair_bytes * (size_t)Tk[k], 1) * (size_t)Tk[k]);
         }
         // every buffer of the call, before the first launch of the rule
         for (Buf *b : {&c->scf_sets[0], &c->scf_sets[1]})
@@ -469,7 +470,7 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
             const bool last = k + 1 == omega;
             const size_t Tl = (size_t)Tk[k], Tnx = (size_t)Tk[k + 1];
             uint16_t *sets = (uint16_t *)c->scf_sets[cur].p;
-            const size_t CH = chunk_rows(n, pair_bytes * Tl, 1);
+            const size_t CH = chunk_rows(c, n, pair_bytes * Tl, 1);
             for (size_t off = 0; off < n; off += CH) {
                 const size_t nc = std::min(CH, n - off);
                 polar::ScfParams F = R;
@@ -509,7 +510,7 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     if ((rc = polar_tu::scf_lanes(c, R, polar::SCF_RECORD, r32, in32))) return rc;
     // pass B: frames [off, off + nc) of the list, T pairs each
     const size_t pair_bytes = (size_t)NW * sizeof(uint32_t);
-    const size_t CH = chunk_rows(n, pair_bytes * (size_t)T, 1);
+    const size_t CH = chunk_rows(c, n, pair_bytes * (size_t)T, 1);
     if ((rc = ensure(c, c->scf_bits, CH * (size_t)T * pair_bytes))) return rc;
     if ((rc = ensure(c, c->scf_pass, CH * (size_t)T * sizeof(uint32_t)))) return rc;
     for (size_t off = 0; off < n; off += CH) {
@@ -546,7 +547,7 @@ int bpl_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     const bool crc = c->cfg.crc_r > 0, direct = c->bpl_ident[0] != 0;
     const uint32_t need = POLAR_FLAG_BP_CONVERGED | (crc ? POLAR_FLAG_CRC_PASS : 0u);
     const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
-    const size_t CH = chunk_rows(B, row);
+    const size_t CH = chunk_rows(c, B, row);
     int rc;
     // every buffer of the call, before its first launch
     if ((rc = ensure(c, c->bpl_siters, B * sizeof(uint32_t)))) return rc;
@@ -672,7 +673,7 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
     if (!d_in || (!d_bits && !scan) || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     const size_t row = (size_t)c->cfg.N * esz;
-    const size_t CH = chunk_rows(B, row);
+    const size_t CH = chunk_rows(c, B, row);
     int rc;
     if ((rc = ensure(c, c->rm_rows, CH * row))) return rc;
     for (size_t off = 0; off < B; off += CH) {
@@ -1865,7 +1866,7 @@ int polar_construct_batch(polar_ctx *c, unsigned long long seed, unsigned long l
     DeviceGuard guard(c->cfg.device);
     const bool f32 = c->cfg.dtype == POLAR_F32;
     const size_t row = (size_t)c->cfg.N * (f32 ? 4 : 8);
-    const size_t CH = chunk_rows(B, row);
+    const size_t CH = chunk_rows(c, B, row);
     int rc;
     if ((rc = ensure(c, c->genie_rows, CH * row))) return rc;
     for (size_t off = 0; off < B; off += CH) {
@@ -2624,6 +2625,13 @@ int polar_testing_big_split(polar_ctx *c, int split)
     if (!c || (split != 0 && split != 35 && split != 46 && split != 57 && split != 351 && split != 371))
         return POLAR_EINVAL;
     c->big_split = split;
+    return POLAR_OK;
+}
+
+int polar_testing_chunk_bytes(polar_ctx *c, size_t bytes)
+{
+    if (!c) return POLAR_EINVAL;
+    c->chunk_bytes = bytes ? bytes : kChunkBytes;
     return POLAR_OK;
 }
 #endif  // POLAR_TESTING

@@ -34,6 +34,8 @@ struct Lane {
     Buf q8_rows;      // POLAR_Q8: the quantised rows of the float entry points, one chunk
 };
 
+constexpr size_t kChunkBytes = (size_t)256 << 20;   // a chunked pass takes at most this many bytes of rows
+
 // Every device resource of a ctx is a member of an owning type (dev_owned.h): polar_destroy only synchronises and deletes.
 // The streams are declared before the buffers, so that the buffers are released first.
 struct polar_ctx : Lane {
@@ -123,6 +125,7 @@ struct polar_ctx : Lane {
     bool use_fast4 = false;     // four codewords per wavefront (k_scl_fast4) at N = 1024
     bool force_spill = false;   // no tuned L = 8 kernel; with force_generic: the global-scratch variant of k_scl_generic
     int big_split = 0;          // 35 | 46 | 57: LDS / scratch split of k_scl_big; 0 = the measured best
+    size_t chunk_bytes = kChunkBytes;   // bytes of rows per pass of the chunked loops (chunk_rows, polar_hip.hip)
 };
 
 // c's lane <-> c->lane_b: work enqueued through c afterwards runs on the other stream with the other stream's buffers

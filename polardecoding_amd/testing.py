@@ -33,6 +33,19 @@ def big_split(dec, split):
     return dec
 
 
+def chunk_bytes(dec, nbytes):
+    """The byte cap of the chunked host loops (polar_testing_chunk_bytes): a pass takes at most nbytes of rows, so a few
+    hundred frames cross pass boundaries.  0 restores 256 MiB.  The decoder keeps the cap across a later rebind."""
+    lib = load_library(testing=True)
+    dec._rebind(lib)
+    lib.polar_testing_chunk_bytes.argtypes = [C.c_void_p, C.c_size_t]
+    rc = lib.polar_testing_chunk_bytes(dec._h, int(nbytes))
+    if rc != 0:
+        raise PolarError(f"polar_testing_chunk_bytes rc={rc}")
+    dec._chunk_bytes = int(nbytes)
+    return dec
+
+
 def math(op, a, b, dtype=np.float64, device=0):
     """The device functions of csrc/polar_math.h / polar_lut.h applied element-wise on the GPU."""
     lib = load_library(testing=True)
