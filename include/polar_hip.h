@@ -670,6 +670,15 @@ int polar_get_systematic(const polar_ctx *ctx);
 /* host only, touches no device: 1 if the two-pass encoder is systematic on info_order[0..A), 0 if not; POLAR_EINVAL for N not a
  * power of two in 32..4096, A outside 1..N, or positions that are out of range or repeated */
 int polar_systematic_check(int N, const int *info_order, int A);
+/* host only, touches no device: the two forms of the CRC test of a code with information positions info_order[0..A) (A = K +
+ * crc_r, ascending reliability) and the CRC crc_taps (as in polar_cfg).  crc_tab [N] (nullable) is the table the list decoders
+ * apply leaf by leaf, crc_tab[I[i]] = D^i mod g(D) (systematic != 0: tab_sys above).  masks [32][N/32] is the same test on
+ * the root partial sums x_hat = u_hat F^{(x)n}, which the two-codewords-per-wavefront CA-SCL kernel (N = 1024, L = 8) applies
+ * once per frame: bit i of XOR over {j : u_hat_j = 1} of crc_tab[j] is the parity of x_hat AND masks[i] (bit k & 31 of word
+ * k >> 5 = position k); masks crc_r .. 31 are zero.  POLAR_EINVAL for N not a power of two in 32..4096, A outside 1..N,
+ * crc_r outside 1..32, positions out of range, fewer than two taps or masks NULL. */
+int polar_crc_masks(int N, const int *info_order, int A, int crc_r, const int *crc_taps, int n_taps, int systematic,
+                    uint32_t *crc_tab, uint32_t *masks);
 
 /* --- Fixed-point min-sum decoding: int8 SC / SCL / CA-SCL (dtype POLAR_Q8; no reference counterpart) ----------------------
  * The decoder of hardware papers and 5G receivers: quantised LLRs, a check node that is a sign and a minimum, integer path

@@ -73,6 +73,33 @@ std::vector<uint32_t> make_crc_table(int N, int r, const std::vector<int> &taps,
     return tab;
 }
 
+// The same test read off the root partial sums x_hat = u_hat F^{(x)n} at the end of a frame (the pair kernel, scl_fast2.h):
+// u_j = XOR over {k : j a subset of k} of x_hat_k, so XOR over {j : u_j = 1} of tab[j] = XOR over {k : x_hat_k = 1} of t[k]
+// with t[k] = XOR over {j : j a subset of k} of tab[j] -- the table pushed through the transpose of the transform.  Bit i
+// of that remainder is the parity of x_hat AND mask i, mask i = bit i of every t[k]: CRC_MASK_ROWS masks of N bits,
+// m[i * N/32 + w] = positions 32w .. 32w+31 of mask i, all-zero masks from r up.
+std::vector<uint32_t> make_crc_masks(int N, const std::vector<uint32_t> &tab)
+{
+    std::vector<uint32_t> t = tab;
+    for (int s = 1; s < N; s <<= 1)
+        for (int k = 0; k < N; ++k)
+            if (k & s) t[(size_t)k] ^= t[(size_t)(k ^ s)];
+    const int NW = N / 32;
+    std::vector<uint32_t> m((size_t)polar::CRC_MASK_ROWS * NW, 0u);
+    for (int k = 0; k < N; ++k)
+        for (int i = 0; i < polar::CRC_MASK_ROWS; ++i)
+            if ((t[(size_t)k] >> i) & 1u) m[(size_t)i * NW + (k >> 5)] |= 1u << (k & 31);
+    return m;
+}
+
+// the CRC table t of a ctx and its masks to the device, synchronously (d_crc_tab and d_crc_mask always hold the same table)
+int upload_crc_tables(polar_ctx *c, const std::vector<uint32_t> &t)
+{
+    const std::vector<uint32_t> m = make_crc_masks(c->cfg.N, t);
+    if (int rc = c->d_crc_tab.upload(t.data(), t.size())) return rc;
+    return c->d_crc_mask.upload(m.data(), m.size());
+}
+
 // Rows per pass where a batch goes through ctx scratch in chunks: at most c->chunk_bytes (256 MiB) of rows, at least `floor`
 // of them, never more than the batch.
 size_t chunk_rows(const polar_ctx *c, size_t B, size_t row_bytes, size_t floor = 64)
@@ -290,6 +317,8 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     P.in = d_in; P.sigma = sigma; P.out_bits = d_bits; P.pm = d_pm; P.flags = d_flags;
     P.frozen = d_frozen;
     P.crc_tab = (g.algo == POLAR_ALGO_CASCL) ? c->d_crc_tab : nullptr;
+    P.crc_mask = (g.algo == POLAR_ALGO_CASCL) ? c->d_crc_mask : nullptr;
+    P.crc_r = (g.algo == POLAR_ALGO_CASCL) ? g.crc_r : 0;
     P.N = g.N; P.n = c->n; P.B = (int)B;
     P.sc_mode = (g.algo == POLAR_ALGO_SC) ? 1 : 0;
     P.dbg = nullptr;
@@ -1078,7 +1107,7 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     if (int rc = c->d_frozen.upload(fw.data(), (size_t)c->NW)) return cleanup(rc);
     if (int rc = c->d_info.upload(iw.data(), (size_t)c->NW)) return cleanup(rc);
     if (r > 0)
-        if (int rc = c->d_crc_tab.upload(c->h_crc_tab.data(), (size_t)N)) return cleanup(rc);
+        if (int rc = upload_crc_tables(c, c->h_crc_tab)) return cleanup(rc);
     if (cfg->algo == POLAR_ALGO_BPL) {   // every attempt stops by rule G; the default list: min(n, 8) cyclic shifts
         c->bp_stop = POLAR_BP_STOP_G;
         const int P = std::min(c->n, 8);
@@ -1476,9 +1505,8 @@ int polar_cascl_set_stages(polar_ctx *c, const int *stages, int n)
             }
             int rc = polar_create(&g, &subs[(size_t)i]);
             if (!rc) rc = polar_set_stream(subs[(size_t)i], c->stream.get());
-            if (!rc && c->sys_polar && subs[(size_t)i]->d_crc_tab &&   // the stage reads the table of the mode that is on
-                hipMemcpy(subs[(size_t)i]->d_crc_tab, c->h_crc_tab_sys.data(), (size_t)c->cfg.N * 4, hipMemcpyHostToDevice) != hipSuccess)
-                rc = POLAR_EDEVICE;
+            if (!rc && c->sys_polar && subs[(size_t)i]->d_crc_tab)   // the stage reads the table of the mode that is on
+                rc = upload_crc_tables(subs[(size_t)i], c->h_crc_tab_sys);
             if (rc) {
                 for (polar_ctx *s : subs) polar_destroy(s);
                 return rc;
@@ -2147,6 +2175,28 @@ int polar_systematic_check(int N, const int *info_order, int A)
     return 1;
 }
 
+int polar_crc_masks(int N, const int *info_order, int A, int crc_r, const int *crc_taps, int n_taps, int systematic,
+                    uint32_t *crc_tab, uint32_t *masks)
+{
+    if (N < 32 || N > 4096 || (N & (N - 1)) || !info_order || A < 1 || A > N || crc_r < 1 || crc_r > 32 || !crc_taps ||
+        n_taps < 2 || !masks)
+        return POLAR_EINVAL;
+    polar_ctx c;   // host members only: what make_crc_table_sys reads
+    c.cfg.N = N;
+    c.frozen.assign((size_t)N, 1);
+    for (int i = 0; i < A; ++i) {
+        if (info_order[i] < 0 || info_order[i] >= N) return POLAR_EINVAL;
+        c.frozen[(size_t)info_order[i]] = 0;
+    }
+    c.h_crc_tab = make_crc_table(N, crc_r, std::vector<int>(crc_taps, crc_taps + n_taps), std::vector<int>(info_order, info_order + A));
+    std::vector<uint32_t> t = c.h_crc_tab;
+    if (systematic) make_crc_table_sys(&c, t);
+    if (crc_tab) std::copy(t.begin(), t.end(), crc_tab);
+    const std::vector<uint32_t> m = make_crc_masks(N, t);
+    std::copy(m.begin(), m.end(), masks);
+    return POLAR_OK;
+}
+
 int polar_get_systematic(const polar_ctx *c) { return c && c->sys_polar ? 1 : 0; }
 
 int polar_set_systematic(polar_ctx *c, int on)
@@ -2163,9 +2213,10 @@ int polar_set_systematic(polar_ctx *c, int on)
         if (c->h_crc_tab_sys.empty()) make_crc_table_sys(c, c->h_crc_tab_sys);
         const std::vector<uint32_t> &t = on ? c->h_crc_tab_sys : c->h_crc_tab;
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // no queued decode still reads the old table
-        HIP_TRY(c, hipMemcpy(c->d_crc_tab, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+        if (int rc = upload_crc_tables(c, t)) return rc;
         for (polar_ctx *s : c->stage_ctx)
-            if (s && s->d_crc_tab) HIP_TRY(c, hipMemcpy(s->d_crc_tab, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+            if (s && s->d_crc_tab)
+                if (int rc = upload_crc_tables(s, t)) return rc;
     }
     c->sys_polar = on != 0;
     return POLAR_OK;

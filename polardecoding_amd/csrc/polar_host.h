@@ -53,6 +53,7 @@ struct polar_ctx : Lane {
     DevMem<uint32_t> d_frozen;            // [NW] bit = frozen
     DevMem<uint32_t> d_info;              // [NW] bit = unfrozen
     DevMem<uint32_t> d_crc_tab;           // [N] or empty
+    DevMem<uint32_t> d_crc_mask;          // [CRC_MASK_ROWS][NW] the same table as masks over x_hat (make_crc_masks), or empty
     DevMem<uint32_t> d_gc_rows;           // [K] systematic CRC generator rows (D^(r+k) mod g), or empty
     DevMem<uint32_t> d_frozen_override;
     DevMem<int> d_info_order;             // [A] for the device-side generator and the encoder (info_order_table)

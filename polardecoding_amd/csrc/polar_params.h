@@ -4,6 +4,8 @@
 
 namespace polar {
 
+constexpr int CRC_MASK_ROWS = 32;   // masks in SclParams::crc_mask: one per remainder bit, for the longest CRC a ctx accepts
+
 struct SclParams {
     const void *in;            // [B][N] double or float: LLRs, or y when sigma > 0
     double sigma;              // > 0: input is y, llr = 2*y/sigma/sigma
@@ -18,6 +20,8 @@ struct SclParams {
     void *scratch;             // k_scl_fast, N = 1024: per-wave global scratch (FastCfg::scratch_elems each)
     unsigned long long *dbg;   // read by nothing; kept so that the fields after it keep their offsets
     unsigned *queue;           // persistent kernels: job counter (polar_host.h work_queue()); null = jobs by a fixed stride
+    const uint32_t *crc_mask;  // [CRC_MASK_ROWS][N/32] crc_tab as masks over the root partial sums (k_scl_fast2); null = no CRC
+    int crc_r;                 // CRC bits: the masks from crc_r up are zero
 };
 
 struct BpParams {

@@ -36,8 +36,8 @@ struct Fast2Cfg {
     // block-shared LDS
     static constexpr size_t off_lut = 0;
     static constexpr size_t off_frz = off_lut + ((Lut<R>::bytes + 15) / 16) * 16;
-    static constexpr size_t off_crc = off_frz + 4 * NW;
-    static constexpr size_t off_kth = off_crc + 4 * N;      // kth[mask][k] = index of the k-th set bit of mask (u8)
+    static constexpr size_t off_msk = off_frz + 4 * NW;     // CRC masks over x_hat [CRC_MASK_ROWS][pos][8]: mask i, words pos + 4j
+    static constexpr size_t off_kth = off_msk + 4 * CRC_MASK_ROWS * NW;   // kth[mask][k] = index of the k-th set bit of mask (u8)
     static constexpr size_t off_stair = off_kth + 256 * 8;  // room for a Stair<R> (chk_idx): not used
     static constexpr size_t shared_bytes = off_stair + ((Stair<R>::bytes + 15) / 16) * 16;
     // per-wave LDS
@@ -72,7 +72,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     R a1;            // level 1 (pos 0, 1)
     R bp_s, bp_d, bp_ts, bp_td;   // by-products of the last level-0 check node: x + y, x - y, T(|x + y|), T(|x - y|)
     R PM;            // valid at pos 0
-    uint32_t ptr, crc, bl0, fl;
+    uint32_t ptr, bl0, fl;
     int logact;
     int p, c, pos, lane, gl;   // gl = c*4 + pos: lane offset inside a path group
     int own_addr, oth_addr;    // rank network: byte addresses into keys[]
@@ -81,7 +81,6 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     Lut<R> lut;
     R *cand, *stg;
     uint32_t *blw, *curw, *keys;   // this lane's codeword slice of the per-wave arrays
-    const uint32_t *crct;
     const unsigned char *kth;
     // Scratch and input rows are read and written through buffer instructions: a wave-uniform resource descriptor
     // (4 SGPRs) plus a 32-bit per-lane byte offset.  The two codewords of a wavefront differ by a constant offset, so no
@@ -498,7 +497,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         // The exits of a leaf share no merged state beyond what each of them writes.  A frozen leaf touches PM and bl0
         // and is done.  At an information leaf the outcome of the trivial prune (bit, metric) is computed in front of
         // the prune test and the ranked path is an `if` without `else` that overrides it: the values a fork permutes
-        // (ptr, crc, bl0, A[1..3], a1, bp_d, bp_td) have the fork block as their only writer, so where the paths meet
+        // (ptr, bl0, A[1..3], a1, bp_d, bp_td) have the fork block as their only writer, so where the paths meet
         // they merge with the unchanged registers and not with copies made on the trivial side.  (With `if (trivial)
         // ... else ...` the structurised merge took every such value through a second register set: 13-17 moves on
         // the trivial exit, and as many back where the frozen exit joins; profiles/r15_ab.txt.)
@@ -507,8 +506,6 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             set_bit_k<K>(o, 0u);
             return;
         }
-        uint32_t crcw = 0;
-        if (CRC_ON) crcw = crct[8 * o + K];
         uint32_t bit;
         R pm;
         if (!FULL && logact < 3) {
@@ -531,7 +528,6 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             if (!trivial_prune(cb, cw)) ranked<K>(lneg, cb, cw, bit, pm);
         }
         PM = pm;
-        if (CRC_ON) crc ^= bit ? crcw : 0u;
         set_bit_k<K>(o, bit);
     }
     // the leaf's decision by ranking the 16 candidates; bit / pm come in as the trivial outcome and leave as the ranked one
@@ -558,7 +554,6 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         const int sl = sg * 8 + gl;
         const R c1s = __shfl(c1, sl);
         ptr = __shfl(ptr, sl);
-        crc = __shfl(crc, sl);
         bl0 = __shfl(bl0, sl);
         // what the lower-node steps still to come in this octet read: the sum / difference pairs of the
         // check nodes above them (octet())
@@ -776,13 +771,14 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the per-wave LDS base is scalar
     unsigned char *base = smem + C::shared_bytes + (size_t)wave * C::per_wave;
     uint32_t *frz = reinterpret_cast<uint32_t *>(smem + C::off_frz);
-    uint32_t *crct = reinterpret_cast<uint32_t *>(smem + C::off_crc);
+    uint32_t *msk = reinterpret_cast<uint32_t *>(smem + C::off_msk);
     unsigned char *kth = smem + C::off_kth;
 
     Lut<R>::build(smem + C::off_lut, threadIdx.x, blockDim.x);
     for (int i = threadIdx.x; i < NW; i += blockDim.x) frz[i] = P.frozen[i];
-    if (CRC_ON)
-        for (int i = threadIdx.x; i < N; i += blockDim.x) crct[i] = P.crc_tab[i];
+    if (CRC_ON)   // mask i, word pos + 4j at [i][pos][j]: a lane's eight words of a mask are two 16-byte reads
+        for (int i = threadIdx.x; i < CRC_MASK_ROWS * NW; i += blockDim.x)
+            msk[i] = P.crc_mask[(i & ~(NW - 1)) + ((i >> 3) & 3) + 4 * (i & 7)];
     for (int i = threadIdx.x; i < 256 * 8; i += blockDim.x) {
         int m = i >> 3, k = i & 7, idx = 0, seen = 0;
         for (int b = 0; b < 8; ++b)
@@ -802,7 +798,6 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
     s.pos0_mask = s.pos == 0 ? 0xFFFFFFFFu : 0u;
     s.gl = s.lane & 7;
     s.lut.bind(smem + C::off_lut);
-    s.crct = crct;
     s.kth = kth;
     s.blw = reinterpret_cast<uint32_t *>(base + C::off_bl) + s.c * 8 * NW;
     s.curw = reinterpret_cast<uint32_t *>(base + C::off_cw) + s.c * 8 * NW;
@@ -850,7 +845,6 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         s.ptr = 0;
         for (int t = 4; t <= 8; ++t) s.set_pa(t, p);
         for (int t = 5; t <= 9; ++t) s.set_pb(t, p);
-        s.crc = 0;
         s.bl0 = 0;
         s.a1 = R(0);
 #pragma unroll
@@ -878,7 +872,34 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         while (o < N / 8) o = octet_group<D, true>(s, frz, fword, o);
 
         // ---- choose the path, per codeword (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) ----
-        const bool pass = CRC_ON && (s.crc == 0);
+        // The CRC remainder is read once, here, so it is computed once, here: it is linear in u_hat = x_hat F^{(x)n}, and
+        // every slot's x_hat is in curw since leaf 1023 carried to the root.  Bit i of the remainder is the parity of
+        // x_hat AND mask i (polar_hip.hip make_crc_masks); a lane takes its eight words pos + 4j of the slot's row, and the
+        // four lanes of the slot add their parities.  Masks come four at a time (the ones from crc_r up are zero).
+        bool pass = false;
+        if constexpr (CRC_ON) {
+            lds_fence();
+            uint32_t x[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = s.curw[p * NW + pos + 4 * j];
+            typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
+            const u4_t *mk = reinterpret_cast<const u4_t *>(msk + 8 * pos);
+            const int rows = (P.crc_r + 3) & ~3;
+            uint32_t rem = 0;
+#pragma unroll 1
+            for (int i = 0; i < rows; i += 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const u4_t a = mk[(i + k) * (NW / 4)], b = mk[(i + k) * (NW / 4) + 1];
+                    const uint32_t acc = (x[0] & a.x) ^ (x[1] & a.y) ^ (x[2] & a.z) ^ (x[3] & a.w) ^ (x[4] & b.x) ^
+                                         (x[5] & b.y) ^ (x[6] & b.z) ^ (x[7] & b.w);
+                    rem |= (uint32_t)(__popc(acc) & 1) << (i + k);
+                }
+            }
+            rem ^= (uint32_t)dpp_i<0xB1>((int)rem);   // quad_perm [1,0,3,2]
+            rem ^= (uint32_t)dpp_i<0x4E>((int)rem);   // quad_perm [2,3,0,1]
+            pass = rem == 0u;
+        }
         const uint64_t bp_ = __ballot(pass && pos == 0);
         // lanes of codeword c at pos 0 are lanes p*8 + 4c: bits 4c, 8+4c, ...
         const uint64_t cwmask = 0x0101010101010101ull << (4 * c);

@@ -1,0 +1,135 @@
+"""CPU: the CRC masks of the pair kernel (k_scl_fast2) against the table the other list kernels apply leaf by leaf.
+
+The pair kernel reads the CRC remainder of a path off the root partial sums x_hat = u_hat F^{(x)n} once per frame: bit i of
+the remainder is parity(x_hat AND M'_i).  polar_crc_masks (include/polar_hip.h) returns the table crc_tab
+(crc_tab[I[i]] = D^i mod g(D)) and the masks M' that the library builds from it for a code; no device is touched.  Here,
+with numpy only: for u with the frozen positions zero, x_hat = u F^{(x)n}, and every parity must equal the bit of
+XOR over {j : u_j = 1} of crc_tab[j].  u = 0, every single-bit u on an information position (each column once) and 200
+random u per code; the table itself is checked against its definition.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import polardecoding_amd as pa
+from oracle import oracle_py as O
+
+MASK_ROWS = 32
+
+# (name, N, K, taps): taps as in polar_cfg (exponents of g(D), 0 and r included)
+CODES = [
+    ("crc24c", 1024, 512, list(O.CRC24C_TAPS)),
+    ("crc6", 1024, 512, list(O.CRC6_TAPS)),
+    ("crc6_n128", 128, 64, list(O.CRC6_TAPS)),
+    ("r1", 1024, 512, [0, 1]),                      # g = D + 1: one parity bit
+    ("r11", 1024, 512, [0, 5, 9, 10, 11]),           # CRC-11 of 5G NR: D^11 + D^10 + D^9 + D^5 + 1
+    ("crc24c_k128", 1024, 128, list(O.CRC24C_TAPS)),
+    ("crc24c_k896", 1024, 896, list(O.CRC24C_TAPS)),
+]
+
+
+def transform(u):
+    """x = u F^{(x)n} over GF(2) on the last axis: the lower element of a pair absorbs the upper one."""
+    x = u.copy()
+    N = x.shape[-1]
+    s = 1
+    while s < N:
+        v = x.reshape(x.shape[:-1] + (N // (2 * s), 2, s))
+        v[..., 0, :] ^= v[..., 1, :]
+        s <<= 1
+    return x
+
+
+def crc_table(N, info, taps):
+    """crc_tab[I[i]] = D^i mod g(D), bit t = coefficient of D^t; 0 at the frozen positions."""
+    r = max(taps)
+    glow = sum(1 << t for t in taps if t < r)
+    tab = np.zeros(N, dtype=np.uint32)
+    rem = 1
+    for j in info:
+        tab[j] = rem
+        rem <<= 1
+        if rem >> r:
+            rem = (rem ^ (1 << r)) ^ glow
+    return tab
+
+
+def lib_tables(N, info, taps, systematic=0):
+    lib = pa.load_library()
+    f = lib.polar_crc_masks
+    f.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    io = np.ascontiguousarray(info, dtype=np.int32)
+    tp = np.ascontiguousarray(taps, dtype=np.int32)
+    tab = np.zeros(N, dtype=np.uint32)
+    masks = np.full(MASK_ROWS * N // 32, 0xFFFFFFFF, dtype=np.uint32)
+    rc = f(N, io.ctypes.data, len(io), max(taps), tp.ctypes.data, len(tp), systematic, tab.ctypes.data, masks.ctypes.data)
+    assert rc == 0
+    bits = ((masks.reshape(MASK_ROWS, N // 32, 1) >> np.arange(32, dtype=np.uint32)) & 1).reshape(MASK_ROWS, N)
+    return tab, bits.astype(np.uint8)
+
+
+def syndrome(tab, u):
+    """XOR over the set bits of every row of u of tab[j]."""
+    return np.bitwise_xor.reduce(np.where(u.astype(bool), tab[None, :], np.uint32(0)), axis=1)
+
+
+def words(N, info):
+    """u = 0, the unit vectors of the information positions, 200 random words; frozen positions zero."""
+    rng = np.random.default_rng(20261019 + N + len(info))
+    rnd = np.zeros((200, N), dtype=np.uint8)
+    rnd[:, info] = rng.integers(0, 2, size=(200, len(info)), dtype=np.uint8)
+    unit = np.zeros((len(info), N), dtype=np.uint8)
+    unit[np.arange(len(info)), info] = 1
+    return np.concatenate([np.zeros((1, N), dtype=np.uint8), unit, rnd])
+
+
+@pytest.mark.parametrize("name,N,K,taps", CODES, ids=[c[0] for c in CODES])
+def test_mask_parities_are_the_table_syndrome(name, N, K, taps):
+    r = max(taps)
+    info = [int(j) for j in O.Code(N, K, taps).info_order]
+    assert len(info) == K + r
+    tab, M = lib_tables(N, info, taps)
+    assert np.array_equal(tab, crc_table(N, info, taps))
+    assert not M[r:].any()                      # the masks from r up are zero
+    u = words(N, info)
+    x = transform(u)
+    assert np.array_equal(transform(x), u)      # F^{(x)n} is its own inverse
+    want = syndrome(tab, u)
+    got = (x.astype(np.int64) @ M.T.astype(np.int64)) & 1      # parity(x AND M'_i), [words][32]
+    for i in range(MASK_ROWS):
+        assert np.array_equal(got[:, i], (want >> np.uint32(i)) & 1), f"{name}: remainder bit {i}"
+    assert want[0] == 0 and want[1:K + r + 1].all()            # the unit vectors reach every column with a non-zero entry
+
+
+def test_masks_of_systematic_mode_follow_its_table():
+    """polar_set_systematic switches the table; the masks are built from the table that is live."""
+    N, K, taps = 1024, 512, list(O.CRC24C_TAPS)
+    info = [int(j) for j in O.Code(N, K, taps).info_order]
+    tab, M = lib_tables(N, info, taps, systematic=1)
+    plain = crc_table(N, info, taps)
+    assert not np.array_equal(tab, plain)
+    u = words(N, info)
+    x = transform(u)
+    # the systematic-mode table applied to u is the plain one applied to x[I] (include/polar_hip.h)
+    frozen = np.ones(N, dtype=bool)
+    frozen[info] = False
+    assert np.array_equal(syndrome(tab, u), syndrome(plain, np.where(frozen, 0, x)))
+    want = syndrome(tab, u)
+    got = (x.astype(np.int64) @ M.T.astype(np.int64)) & 1
+    for i in range(MASK_ROWS):
+        assert np.array_equal(got[:, i], (want >> np.uint32(i)) & 1)
+
+
+def test_bad_arguments():
+    lib = pa.load_library()
+    f = lib.polar_crc_masks
+    f.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    io = np.arange(8, dtype=np.int32)
+    tp = np.array([0, 1], dtype=np.int32)
+    out = np.zeros(MASK_ROWS * 2, dtype=np.uint32)
+    assert f(48, io.ctypes.data, 8, 1, tp.ctypes.data, 2, 0, None, out.ctypes.data) == -1     # N not a power of two
+    assert f(64, io.ctypes.data, 8, 33, tp.ctypes.data, 2, 0, None, out.ctypes.data) == -1    # r > 32
+    assert f(64, io.ctypes.data, 8, 1, tp.ctypes.data, 2, 0, None, None) == -1                # no output
+    assert f(64, io.ctypes.data, 8, 1, tp.ctypes.data, 2, 0, None, out.ctypes.data) == 0
