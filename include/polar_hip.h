@@ -679,6 +679,13 @@ int polar_systematic_check(int N, const int *info_order, int A);
  * crc_r outside 1..32, positions out of range, fewer than two taps or masks NULL. */
 int polar_crc_masks(int N, const int *info_order, int A, int crc_r, const int *crc_taps, int n_taps, int systematic,
                     uint32_t *crc_tab, uint32_t *masks);
+/* host only, touches no device: where the list-filling phase of the two-codewords-per-wavefront SCL / CA-SCL kernel (N = 1024,
+ * L = 8) ends for the code with information positions info_order[0..A): 128, 192 or 256 when the leaves below it are decoded
+ * breadth-first (at most three information leaves below it, each one of the last two leaves of its 64-leaf block and none
+ * below leaf 126; for 192 and 256 exactly one of them below leaf 128 and no other in front of the last 64-leaf block), 0
+ * when the kernel decodes every leaf in order, which includes every N other than 1024.  The outputs are the same either
+ * way.  POLAR_EINVAL as polar_systematic_check. */
+int polar_fill_phase_end(int N, const int *info_order, int A);
 
 /* --- Fixed-point min-sum decoding: int8 SC / SCL / CA-SCL (dtype POLAR_Q8; no reference counterpart) ----------------------
  * The decoder of hardware papers and 5G receivers: quantised LLRs, a check node that is a sign and a minimum, integer path

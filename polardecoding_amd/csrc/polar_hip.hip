@@ -92,6 +92,41 @@ std::vector<uint32_t> make_crc_masks(int N, const std::vector<uint32_t> &tab)
     return m;
 }
 
+// Where the list-filling phase of the pair kernel ends (scl_fast2.h fill_phase(); N = 1024): the leaves below E are decoded
+// breadth-first on at most two paths per 64-leaf block.  E is the largest of 256, 192, 128 for which
+//   (a) at most three information leaves lie below E,
+//   (b) every one of them is one of the last two leaves of its 64-leaf block, and none lies below leaf 126 (the first 128
+//       leaves are one butterfly: leaves 62 / 63 may not fork),
+//   (c) for E > 128, exactly one of them lies below leaf 128 and no other one below E - 64: exactly two paths enter every
+//       block behind leaf 128 (the phase decodes such a block for two paths),
+// and 0 (the frozen run and the octets behind it, as without the phase) if there is none or E <= 8 * lead, lead = the
+// leading all-frozen octets the kernel counts (at most 15).  frozen: [N] bytes, non-zero = frozen.
+int fill_phase_end(int N, const unsigned char *frozen)
+{
+    if (N != 1024) return 0;
+    int lead = 0;
+    while (lead < 15) {
+        bool all = true;
+        for (int k = 0; k < 8; ++k) all = all && frozen[8 * lead + k] != 0;
+        if (!all) break;
+        ++lead;
+    }
+    for (int E = 256; E >= 128; E -= 64) {
+        int count = 0, early = 0, first = 0;   // information leaves below E / in front of the last block / below leaf 128
+        bool ok = true;
+        for (int j = 0; j < E; ++j) {
+            if (frozen[j]) continue;
+            if ((j & 63) < 62 || j < 126) ok = false;   // (b)
+            ++count;
+            if (j < E - 64) ++early;
+            if (j < 128) ++first;
+        }
+        if (E > 128 && !(first == 1 && early == 1)) ok = false;   // (c)
+        if (ok && count <= 3 && E > 8 * lead) return E;
+    }
+    return 0;
+}
+
 // the CRC table t of a ctx and its masks to the device, synchronously (d_crc_tab and d_crc_mask always hold the same table)
 int upload_crc_tables(polar_ctx *c, const std::vector<uint32_t> &t)
 {
@@ -319,6 +354,8 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
     P.crc_tab = (g.algo == POLAR_ALGO_CASCL) ? c->d_crc_tab : nullptr;
     P.crc_mask = (g.algo == POLAR_ALGO_CASCL) ? c->d_crc_mask : nullptr;
     P.crc_r = (g.algo == POLAR_ALGO_CASCL) ? g.crc_r : 0;
+    // the mask in use is the ctx's own or the per-call one of host_batch(): each has its phase end, any other mask has none
+    P.fill_end = d_frozen == c->d_frozen ? c->fill_end : d_frozen == c->d_frozen_override ? c->fill_end_override : 0;
     P.N = g.N; P.n = c->n; P.B = (int)B;
     P.sc_mode = (g.algo == POLAR_ALGO_SC) ? 1 : 0;
     P.dbg = nullptr;
@@ -830,6 +867,7 @@ int host_batch(polar_ctx *c, const double *in, double sigma, const unsigned char
                                   c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // w goes out of scope
         d_frozen = c->d_frozen_override;
+        c->fill_end_override = fill_phase_end(N, frozen_mask);
     }
     int rc;
     if ((rc = ensure(c, c->pm, B * sizeof(double)))) return rc;
@@ -1105,6 +1143,7 @@ int polar_create(const polar_cfg *cfg, polar_ctx **out)
     // both allocations before either copy: out of memory is reported before a failed copy
     if (c->d_frozen.alloc((size_t)c->NW) != hipSuccess || c->d_info.alloc((size_t)c->NW) != hipSuccess) return cleanup(POLAR_ENOMEM);
     if (int rc = c->d_frozen.upload(fw.data(), (size_t)c->NW)) return cleanup(rc);
+    c->fill_end = fill_phase_end(N, c->frozen.data());
     if (int rc = c->d_info.upload(iw.data(), (size_t)c->NW)) return cleanup(rc);
     if (r > 0)
         if (int rc = upload_crc_tables(c, c->h_crc_tab)) return cleanup(rc);
@@ -2195,6 +2234,17 @@ int polar_crc_masks(int N, const int *info_order, int A, int crc_r, const int *c
     const std::vector<uint32_t> m = make_crc_masks(N, t);
     std::copy(m.begin(), m.end(), masks);
     return POLAR_OK;
+}
+
+int polar_fill_phase_end(int N, const int *info_order, int A)
+{
+    if (N < 32 || N > 4096 || (N & (N - 1)) || !info_order || A < 1 || A > N) return POLAR_EINVAL;
+    std::vector<unsigned char> frozen((size_t)N, 1);
+    for (int i = 0; i < A; ++i) {
+        if (info_order[i] < 0 || info_order[i] >= N) return POLAR_EINVAL;
+        frozen[(size_t)info_order[i]] = 0;
+    }
+    return fill_phase_end(N, frozen.data());
 }
 
 int polar_get_systematic(const polar_ctx *c) { return c && c->sys_polar ? 1 : 0; }

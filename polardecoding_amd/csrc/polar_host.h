@@ -56,6 +56,7 @@ struct polar_ctx : Lane {
     DevMem<uint32_t> d_crc_mask;          // [CRC_MASK_ROWS][NW] the same table as masks over x_hat (make_crc_masks), or empty
     DevMem<uint32_t> d_gc_rows;           // [K] systematic CRC generator rows (D^(r+k) mod g), or empty
     DevMem<uint32_t> d_frozen_override;
+    int fill_end = 0, fill_end_override = 0;   // fill_phase_end() of the mask in d_frozen / d_frozen_override (pair kernel)
     DevMem<int> d_info_order;             // [A] for the device-side generator and the encoder (info_order_table)
     int num_cu = 0;
     Buf in, bits, pm, flags;              // staging for the host-pointer entry points

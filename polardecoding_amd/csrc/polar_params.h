@@ -22,6 +22,7 @@ struct SclParams {
     unsigned *queue;           // persistent kernels: job counter (polar_host.h work_queue()); null = jobs by a fixed stride
     const uint32_t *crc_mask;  // [CRC_MASK_ROWS][N/32] crc_tab as masks over the root partial sums (k_scl_fast2); null = no CRC
     int crc_r;                 // CRC bits: the masks from crc_r up are zero
+    int fill_end;              // k_scl_fast2: leaves below it are decoded by fill_phase() (fill_phase_end() of the mask), 0 = none
 };
 
 struct BpParams {

@@ -573,7 +573,10 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     // (SCL_1024.c:601-604).  Afterwards the registers hold the nodes that contain leaf 8P at levels 4..6.
     // Levels 8 and 7 above it are computed once, by the codeword's 32 lanes together, into slot 0's scratch rows,
     // and every slot points there (the eight slots are replicas of one path until the first information leaf).
-    __device__ __forceinline__ void frozen_prefix(int P)
+    // fill_phase() runs the same tree for all 128 leaves: it asks for the metric of the first nphi leaves only
+    // (nphi = 8P otherwise), takes no registers (regs = false: the head at octet E/8 rebuilds them) and wants the
+    // level-1 pair above leaves 126 / 127 (xl, yl), which the last stage overwrites.
+    __device__ __forceinline__ void frozen_prefix(int P, int nphi, bool regs, R &xl, R &yl)
     {
         const int w32 = p * 4 + pos, j0 = 8 * P;
         vm_drain();   // the top-left level written by the root step
@@ -610,6 +613,10 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
                 x[i] = stg[idx[i]];
                 y[i] = stg[idx[i] + h];
             }
+            if (t == 0) {
+                xl = stg[126];
+                yl = stg[127];
+            }
             lds_fence();
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -617,7 +624,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
                 stg[idx[i] + h] = y[i] + x[i];
             }
             lds_fence();
-            if (t >= 4) {   // node of level t that holds leaf j0: elements pos + 4r
+            if (t >= 4 && regs) {   // node of level t that holds leaf j0: elements pos + 4r
                 const R *node = stg + ((j0 >> t) << t) + pos;
 #pragma unroll
                 for (int r = 0; r < h / 4; ++r) A[h / 4 + r] = node[4 * r];
@@ -632,9 +639,129 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         lds_fence();
         R pm = PM;
 #pragma unroll 8
-        for (int j = 0; j < j0; ++j) pm += stg[128 + j];
+        for (int j = 0; j < nphi; ++j) pm += stg[128 + j];
         PM = pm;
         lds_fence();
+    }
+
+    // ---- the list-filling phase: leaves 0 .. E-1, E in {128, 192, 256} (the host's choice, polar_fill_phase_end) ----
+    // Below E every information leaf is one of the last two leaves of its 64-leaf block, and for E > 128 exactly one of
+    // them lies in front of the last block, below leaf 128.  Inside a block all partner bits are therefore 0 up to its
+    // last pair, two distinct paths enter it (slot s continues path s & 1: the forks go by slot bits, decide()), and
+    // the block is two 64-element butterflies per codeword instead of eight octets on eight slots.  The last two leaves are frozen
+    // (PHI(., 0)) or fork without ranking, exactly as decide() does while logact < 3.  Every slot keeps its own metric
+    // and writes its own partial-sum rows, so pb() stays as the frame set it; the level-7 rows of the two paths go to
+    // the scratch rows of slots 0 and 1.  The head at octet E/8 (from_l8 / from_l7 / from_top) rebuilds every register.
+    // bit0 / bit1 of f2: leaf frozen.  lam0: the even leaf's lambda; (xl, yl): the level-1 pair above the two leaves.
+    // Returns the block's partial sums, which are the same in every 32-bit word: u = bit at the last-but-one leaf gives
+    // the even positions, u = bit at the last leaf gives all of them.
+    __device__ __forceinline__ uint32_t fill_tail(uint32_t f2, R lam0, R xl, R yl)
+    {
+        uint32_t b0 = 0, b1 = 0;
+        if (!(f2 & 1u)) {
+            b0 = (p >> logact) & 1;
+            ++logact;
+        }
+        PM += lut.tabv(lam0) + (b0 ? posmax(lam0) : negmax(lam0));   // PHI(lambda, bit)
+        const R lam1 = b0 ? -(xl - yl) : yl + xl;   // g with the bit just decided: the single rounding of leaf_pair()
+        if (!(f2 & 2u)) {
+            b1 = (p >> logact) & 1;
+            ++logact;
+        }
+        PM += lut.tabv(lam1) + (b1 ? posmax(lam1) : negmax(lam1));
+        return (b0 ? 0x55555555u : 0u) ^ (b1 ? 0xFFFFFFFFu : 0u);
+    }
+    __device__ __forceinline__ void fill_phase(int E, const uint32_t *frz, R xl, R yl)
+    {
+        const int w32 = (int)fresh((unsigned)(p * 4 + pos));
+        const int qb = (p & 1) * 64;   // the slot's path inside the staging buffer
+        const uint32_t wv0 = fill_tail(frz[3] >> 30, stg[126], xl, yl);
+        uint32_t wv1 = 0;
+        lds_fence();
+        blw[p * NW + 4 + pos] = wv0;   // beta_7
+        lds_fence();
+#pragma unroll 1
+        for (int S = 128; S < E; S += 64) {
+            // the block's level-6 node for paths 0 and 1, elements w32 and w32 + 32, at stg[64 q + .]
+            vm_drain();
+            const uint32_t wsel = S == 128 ? wv0 : wv1;   // beta_7 (S = 128) / beta_6 (S = 192) of the slot ...
+            uint32_t wq[2];                               // ... and of slots 0 and 1 at bit w32 & 31 = e & 31
+            wq[0] = (uint32_t)__shfl((int)wsel, gl) >> w32;
+            wq[1] = (uint32_t)__shfl((int)wsel, 8 + gl) >> w32;
+            if (S == 128) {   // g at level 7 from slot 0's level-8 row (the prefix's), f to level 6
+                const SPtr s8 = l8(0) + w32;
+                R v8[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v8[k] = ld_sc(s8 + 32 * k);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const SPtr o7 = l7(q) + w32;
+                    R v7[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        v7[k] = g_bit<R>(v8[k], v8[k + 4], wq[q], 0);
+                        o7[32 * k] = v7[k];
+                    }
+                    stg[64 * q + w32] = chk(v7[0], v7[2]);
+                    stg[64 * q + w32 + 32] = chk(v7[1], v7[3]);
+                }
+                set_pa(7, p & 1);
+            } else {          // g at level 6 from the path's level-7 row
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const SPtr s7 = l7(q) + w32;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        stg[64 * q + w32 + 32 * i] = g_bit<R>(ld_sc(s7 + 32 * i), ld_sc(s7 + 32 * i + 64), wq[q], 0);
+                }
+            }
+            lds_fence();
+#pragma unroll
+            for (int t = 5; t >= 0; --t) {   // six stages, both paths: 64 butterflies, two per lane
+                const int h = 1 << t;
+                int idx[2];
+                R x[2], y[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int b = w32 + 32 * i;
+                    idx[i] = ((b >> t) << (t + 1)) | (b & (h - 1));
+                    x[i] = stg[idx[i]];
+                    y[i] = stg[idx[i] + h];
+                }
+                if (t == 0) {
+                    xl = stg[qb + 62];
+                    yl = stg[qb + 63];
+                }
+                lds_fence();
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    stg[idx[i]] = chk(x[i], y[i]);
+                    stg[idx[i] + h] = y[i] + x[i];
+                }
+                lds_fence();
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const R lam = stg[w32 + 32 * k];
+                stg[128 + w32 + 32 * k] = lut.tabv(lam) + negmax(lam);
+            }
+            lds_fence();
+            R pm = PM;
+#pragma unroll 2
+            for (int j = 0; j < 62; ++j) pm += stg[128 + qb + j];
+            PM = pm;
+            const uint32_t wv = fill_tail(frz[(S + 62) >> 5] >> 30, stg[qb + 62], xl, yl);
+            lds_fence();
+            if (S == 128) {
+                wv1 = wv;
+                if (pos < 2) blw[p * NW + 2 + pos] = wv;   // beta_6
+            } else {          // beta_8 = (beta_7 ^ b, b), b = the partial sums of leaves 128 .. 255 = (wv1 ^ wv, wv)
+                const uint32_t b = pos < 2 ? wv1 ^ wv : wv;
+                blw[p * NW + 8 + pos] = wv0 ^ b;
+                blw[p * NW + 12 + pos] = b;
+            }
+            lds_fence();
+        }
     }
 
     // ---- octets whose first seven leaves are frozen: breadth-first (all partner bits are 0) ----
@@ -824,6 +951,7 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
     int lead = 0;
     while (lead < 15 && ((frz[lead >> 2] >> (8 * (lead & 3))) & 0xFFu) == 0xFFu) ++lead;
     lead = __builtin_amdgcn_readfirstlane(lead);
+    const int E = P.fill_end;   // 0: the frozen run and the octets from `lead`; else fill_phase() and the octets from E / 8
 
     // jobs (pairs of frames): the first one by the wavefront's index, the others from the launch's work queue
     for (int pair = wave_global; 2 * pair < P.B;) {
@@ -854,9 +982,14 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         uint32_t fword = 0;
 
         int o_first = 0;
-        if (lead > 0) {
-            s.frozen_prefix(lead);
+        if (E > 0 || lead > 0) {
+            R xl, yl;
+            s.frozen_prefix(E > 0 ? 15 : lead, E > 0 ? 126 : 8 * lead, E == 0, xl, yl);
             o_first = lead;
+            if (E > 0) {
+                s.fill_phase(E, frz, xl, yl);
+                o_first = E >> 3;
+            }
             fword = frz[o_first >> 2];
         }
         // Groups of eight octets: level 6 (and the scratch levels) change only at the head of a group, so the inner
