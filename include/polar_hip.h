@@ -747,7 +747,19 @@ int polar_q8_decode_batch(polar_ctx *ctx, const int8_t *q, size_t B, int *u_hat,
  * when out_is_f32; channel LLRs 2y/sigma/sigma, or y when out_is_y) and d_u_bits[B][N/32] (nullable).
  * Counter-based generator: frame (first_frame + f) depends only on (seed, frame index), so batches can be cut
  * and sharded over GPUs freely.  This is NOT the reference's sequential Ranq1 stream (that one stays on the
- * host: polar_sim.c); use it for throughput / FER runs, not for reproducing published run counts. */
+ * host: polar_sim.c); use it for throughput / FER runs, not for reproducing published run counts.
+ * The generator, by value (tests/gen_model.py restates it; tests/test_gpu_generator_values.py holds the kernels to it):
+ *   Philox4x32-10 with counter (frame lo, frame hi, block, stream), frame = first_frame + f, and key (seed lo, seed hi).
+ *   payload: word w of the K payload bits (bit b of the word = payload bit 32 w + b; the last word masked when K & 31) is
+ *     output word 0 of (block w, stream 0).
+ *   uniforms: u0 = (k0 + 0.5) 2^-53, u1 = (k1 + 0.5) 2^-53 in binary64, k0 / k1 the top 53 bits of output words 0:1 / 2:3;
+ *     they lie in (0, 1] (k + 0.5 rounds to even from 2^52 on; u0 = 1 gives a normal of 0).
+ *   normals: one block gives two, r cos(2 pi u1) (normal 0) and r sin(2 pi u1) (normal 1), r = sqrt(-2 log u0); |z| < 8.66.
+ *   noise on a plain or dynamic context: element j of a row takes normal (j >> 6) & 1 of block (j & 63) + 64 (j >> 7),
+ *     stream 1 (N = 64: normal 0 of block j; the second normal is not used).  Rate-matched rows and design rows take
+ *     stream 2 (see there).
+ *   y = (1 - 2 x) + sigma z and the LLR is 2 * y / sigma / sigma, evaluated in that order in binary64; a float output is
+ *     that binary64 value rounded once.  N >= 64 (POLAR_EINVAL below). */
 int polar_generate_device(polar_ctx *ctx, unsigned long long seed, unsigned long long first_frame, double snr_db,
                           size_t B, void *d_out, int out_is_f32, int out_is_y, uint32_t *d_u_bits);
 

@@ -43,7 +43,8 @@ struct Philox {
             k1 += 0xBB67AE85u;
         }
     }
-    // two uniforms in (0,1) with 53 random bits each
+    // two uniforms in (0,1] with 53 random bits each: k + 0.5 rounds to even for k >= 2^52, so 1.0 is reached (k = 2^53 - 1,
+    // the normal is then 0) and 0 is not
     __device__ __forceinline__ double u0() const { return ((double)((((uint64_t)c[0] << 32) | c[1]) >> 11) + 0.5) * 0x1.0p-53; }
     __device__ __forceinline__ double u1() const { return ((double)((((uint64_t)c[2] << 32) | c[3]) >> 11) + 0.5) * 0x1.0p-53; }
 };
