@@ -14,6 +14,7 @@
 // the leaf schedule (frozen pattern) is the same for both codewords, so control flow stays uniform.
 // Arithmetic is the same as k_scl_fast / the reference, operation for operation.
 #pragma once
+#include "octet_bits.h"
 #include "scl_fast.h"
 
 namespace polar {
@@ -345,22 +346,18 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     }
 
     // ---- partial sums (identical per path to k_scl_fast) ----
+    // Bits 0..7 of bl0: the decided bits u_0 .. u_7 of the current octet as they are, 0 at the head of every octet; a frozen
+    // leaf writes nothing.  The sums over them are formed where they are read (octet(), octet_bits.h); leaf 7 turns the
+    // byte into the octet's eight level-3 sums, clears it and carries on.  Bits 8..15: level 3, bits 16..31: level 4.
     template <int K>
     __device__ __forceinline__ void set_bit_k(int o, uint32_t bit)
     {
-        if constexpr ((K & 1) == 0) {
-            bl0 = (bl0 & ~2u) | (bit << 1);
-        } else if constexpr ((K & 3) == 1) {
-            const uint32_t c1 = (((bl0 >> 1) & 1u) ^ bit) | (bit << 1);
-            bl0 = (bl0 & ~0xCu) | (c1 << 2);
-        } else if constexpr (K == 3) {
-            const uint32_t c1 = (((bl0 >> 1) & 1u) ^ bit) | (bit << 1);
-            const uint32_t c2 = (((bl0 >> 2) & 3u) ^ c1) | (c1 << 2);
-            bl0 = (bl0 & ~0xF0u) | (c2 << 4);
+        if constexpr (K < 7) {
+            bl0 |= bit << K;
         } else {
-            const uint32_t c1 = (((bl0 >> 1) & 1u) ^ bit) | (bit << 1);
-            const uint32_t c2 = (((bl0 >> 2) & 3u) ^ c1) | (c1 << 2);
-            set_bit7(o, (((bl0 >> 4) & 15u) ^ c2) | (c2 << 4));
+            const uint32_t c3 = octet_bits::level3((bl0 & 0x7Fu) | (bit << 7));
+            bl0 &= ~0xFFu;
+            set_bit7(o, c3);
         }
     }
     // Leaf 7 of octet o closes the octet: j = 8o + 7, so the combine steps at levels 0..2 are the same at every octet
@@ -793,10 +790,9 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         PM += pg;
         PM += quadp<0x55>(pg);
         PM += quadp<0xAA>(pg);
-        bl0 &= ~0xFEu;
         if (last_frozen) {
             PM += quadp<0xFF>(pg);
-            set_bit7(o, 0u);   // bits 1..7 of bl0 are 0 (above) and so is this one: c3 = 0
+            set_bit7(o, 0u);   // bits 0..7 of bl0 are 0 as at the head of every octet (set_bit_k): c3 = 0
         } else {
             decide<7, FULL>(o, false, quadp<0xFF>(lg));
         }
@@ -835,9 +831,9 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         bp_d = q.d;
         bp_td = q.td;
         decide<K, FULL>(o, (fm >> K) & 1, q.v);
-        // leaf K + 1: g0 with the bit just decided (bit 1 of bl0, set_bit_k<even>); a slot refilled by a fork took
+        // leaf K + 1: g0 with the bit just decided (bit K of bl0, set_bit_k<K>); a slot refilled by a fork took
         // bp_d / bp_td of its source and continues with bit 1, every other slot still has its own q.s / q.ts
-        const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)bl0, 1, 1);
+        const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)bl0, K, 1);
         decide_t<K + 1, FULL>(o, (fm >> (K + 1)) & 1, Lut<R>::sel_mask(m1, -bp_d, q.s), Lut<R>::sel_mask(m1, bp_td, q.ts));
     }
     template <bool FULL>
@@ -857,9 +853,10 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             a1 = d1;
             leaf_pair<0, FULL>(o, fm, v1);
         }
-        leaf_pair<2, FULL>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
+        // the partner sums of the g steps come from the octet's raw bits (bits 0..7 of bl0) where they are read
+        leaf_pair<2, FULL>(o, fm, g_sel(A[1], a1, octet_bits::level1_lo(bl0), pos));
         {
-            const R v2 = g_sel(A[2], A[3], bl0, 4 + pos);   // level 2, g
+            const R v2 = g_sel(A[2], A[3], octet_bits::level2(bl0), pos);   // level 2, g
             const R y2 = quadp<0x4E>(v2);
             const R s1 = v2 + y2, d1 = v2 - y2;
             const R v1 = xor_sign(minabs(v2, y2), v2, y2) + (lut.tabv(s1) - lut.tabv(d1));
@@ -867,7 +864,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             a1 = d1;
             leaf_pair<4, FULL>(o, fm, v1);
         }
-        leaf_pair<6, FULL>(o, fm, g_sel(A[1], a1, bl0, 2 + pos));
+        leaf_pair<6, FULL>(o, fm, g_sel(A[1], a1, octet_bits::level1_hi(bl0), pos));
     }
 };
 
