@@ -318,7 +318,8 @@ int polar_scf_set_dynamic(polar_ctx *ctx, const int *budgets, int omega, double 
 /* Every output is nullable.  budgets [3]: T_1 (the ctx's T), T_2, T_3, 0 beyond omega; omega = 0, c = tau = 0: the static rule. */
 int polar_scf_get_dynamic(const polar_ctx *ctx, int *omega, int *budgets, double *c, double *tau);
 /* polar_scf_decode_device plus d_sets (nullable) [B][3]: the reported set in ascending order, -1 padded (all -1: attempt 0
- * is the output).  On a static ctx it holds at most one entry, the flipped position. */
+ * is the output).  On a static ctx it holds at most one entry, the flipped position.  d_flags, d_attempts and d_sets are
+ * nullable. */
 int polar_scf_decode_sets_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                                  uint32_t *d_uhat_bits, uint32_t *d_flags, uint32_t *d_attempts, int32_t *d_sets);
 /* Host-buffer form: sets (nullable) [B][3]. */
@@ -425,8 +426,8 @@ int polar_bpl_set_graphs(polar_ctx *ctx, const int *perms, int P);
 int polar_bpl_get_graphs(const polar_ctx *ctx, int *P, int *perms);
 /* the cyclic shifts out[s][b] = (b + s) mod n, s = 0 .. P-1; 5 <= n <= 12, 1 <= P <= 32.  Host only. */
 int polar_bpl_cyclic_graphs(int n, int P, int *out);
-/* polar_decode_device for a BPL ctx, plus per frame (each nullable, [B] uint32): d_iters and d_flags of rule 6, d_graph of
- * rule 5 and d_total_iters of rule 6. */
+/* polar_decode_device for a BPL ctx, plus per frame ([B] uint32 each): d_iters and d_flags of rule 6, d_graph of rule 5
+ * and d_total_iters of rule 6.  d_iters, d_flags, d_graph and d_total_iters are nullable. */
 int polar_bpl_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
                             uint32_t *d_iters, uint32_t *d_flags, uint32_t *d_graph, uint32_t *d_total_iters);
 /* Host-buffer form: llr_in [B][N] LLRs (E per row on a rate-matched ctx), u_hat [B][N]; iters, flags, graph, total_iters

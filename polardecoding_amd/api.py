@@ -94,6 +94,7 @@ def load_library(testing=False):
     L.polar_bp_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp]
     L.polar_bp_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, up, up]
     L.polar_bp_readout_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, ip, C.c_int, vp, vp]
+    L.polar_bp_readout_batch.argtypes = [vp, dp, C.c_double, C.c_size_t, ip, ip, C.c_int, C.POINTER(C.c_ulonglong), ip]
     L.polar_cascl_set_stages.argtypes = [vp, ip, C.c_int]
     L.polar_cascl_decode_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp, vp]
     L.polar_cascl_decode_batch.argtypes = [vp, dp, C.c_size_t, ip, dp, up, up]

@@ -5,10 +5,16 @@ wavefront decodes which frame then depends on timing.  Nothing about a frame's r
 frame for frame, what the same frames return in launches small enough to be assigned statically (the path the oracle and
 golden-vector tests cover), again and again on the same context: the wavefront that takes the last number puts the counter
 back to zero, so every launch -- and a replay of a captured one -- starts from the same state without a memset in between."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import extents as X  # noqa: E402
 
 CRC24C = (0, 1, 2, 4, 8, 12, 13, 15, 17, 20, 21, 23, 24)
 CRC6 = (0, 1, 6)
@@ -50,18 +56,29 @@ def test_one_big_launch_equals_statically_assigned_small_launches(algo, N, K, kw
     llr, _ = make_batch(B, N, K, taps, 1.5, info, "cuda", gen)   # 1.5 dB: frames differ a lot in work (ranked steps, forks)
     lists = algo in ("CASCL", "SCL")
 
-    def run(x):
+    def run(x, arena=None):
+        """arena: the outputs are views into it (tests/extents.py), guarded by 64 rows on both sides: the only place where
+        more jobs than resident wavefronts meet a ragged last job"""
         nb = x.shape[0]
-        bits = torch.full((nb, N // 32), -1, dtype=torch.int32, device="cuda")
-        pm = torch.full((nb,), -1.0, dtype=torch.float64, device="cuda") if lists else None
-        fl = torch.full((nb,), -1, dtype=torch.int32, device="cuda") if lists else None
+        if arena is None:
+            bits = torch.full((nb, N // 32), -1, dtype=torch.int32, device="cuda")
+            pm = torch.full((nb,), -1.0, dtype=torch.float64, device="cuda") if lists else None
+            fl = torch.full((nb,), -1, dtype=torch.int32, device="cuda") if lists else None
+        else:
+            bits = arena.carve("bits", "int32", nb * (N // 32), 64, N // 32).view(nb, N // 32).fill_(-1)
+            pm = arena.carve("pm", "float64", nb, 64, 1).fill_(-1.0) if lists else None
+            fl = arena.carve("flags", "int32", nb, 64, 1).fill_(-1) if lists else None
         dec.decode_device(x, out_bits=bits, pm=pm, flags=fl)
         return bits, pm, fl
+
+    specs = [("int32", B * (N // 32), 64, N // 32)] + ([("float64", B, 64, 1), ("int32", B, 64, 1)] if lists else [])
 
     parts = [run(llr[i:i + chunk]) for i in range(0, B, chunk)]
     ref_bits = torch.cat([p[0] for p in parts])
     for rep in range(3):   # every launch must leave the counter at zero for the next one
-        bits, pm, fl = run(llr)
+        arena = X.Arena("torch", X.Arena.need(specs))
+        bits, pm, fl = run(llr, arena)
+        assert arena.check() == [], f"a store outside the outputs in launch {rep}"
         assert torch.equal(bits, ref_bits), f"decisions differ in launch {rep}"
         assert not bool((bits == -1).all(dim=1).any()), "a frame was not decoded"   # frozen positions are 0 in u_hat
         if lists:
