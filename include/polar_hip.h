@@ -688,6 +688,78 @@ int polar_crc_masks(int N, const int *info_order, int A, int crc_r, const int *c
  * way.  POLAR_EINVAL as polar_systematic_check. */
 int polar_fill_phase_end(int N, const int *info_order, int A);
 
+/* --- List output: all L paths, masked-CRC selection, list soft output (no reference counterpart) ---------------------------
+ * Every list decoder ends a frame with its live paths, their metrics and their CRC remainders, and the decodes above return
+ * one of them.  polar_list_decode returns them all; k_list_select, k_list_gather and k_list_soft work on what it wrote.
+ * tests/list_model.py restates the rules below in numpy; tests/test_gpu_list.py holds the kernels to it with ==.
+ *   1. which decoder: the context's own SCL or CA-SCL rule -- for L <= 32 the rule the oracle states, for larger L the rule of
+ *      "Wide lists", on a dynamic context with rules 3-6 of "Dynamic frozen bits".  Leaf by leaf the list is the one the
+ *      ordinary decode of the same context has.
+ *   2. the live list: after leaf N - 1 there are `act` live slots (act = min(L, 2^#information leaves)).  Each has its decided
+ *      bits u_hat (frozen = 0, dynamic = b), its metric PM in the context's arithmetic type R, and its remainder
+ *      rem = XOR over {j : u_hat_j = 1} of the context's CRC table (crc_tab[I[i]] = D^i mod g(D); tab_sys in systematic mode;
+ *      rem = 0 for POLAR_ALGO_SCL, which has no CRC).
+ *   3. output order: rank k = 0, 1, ... lists the live slots in ascending (PM, slot), compared in R.  d_count[f] = act.  The
+ *      entries k >= act are padding: bits 0, pm = +inf, rem = 0.  d_pm holds the R value widened to double (exact).
+ *   4. flags: d_flags is the flags word of the ordinary decode: POLAR_FLAG_TIE and POLAR_FLAG_CRC_PASS.
+ *   5. identity: let k* be the smallest k < count with rem[k] = 0 if the context has a CRC and such a k exists, else k* = 0.
+ *      Then paths[k*], pm[k*] and flags equal what polar_decode_device on the same context returns for the same row, bit for
+ *      bit (POLAR_FLAG_RERANK excluded: it is a diagnostic of other kernels), also where the ordinary decode runs a tuned
+ *      kernel (k_scl_fast2, k_scl_fast, k_scl_big).
+ *   6. where it works: POLAR_ALGO_SCL and POLAR_ALGO_CASCL, POLAR_F64 and POLAR_F32, 32 <= N <= 1024, every L the context was
+ *      created with (1 .. 256); plain, dynamic, CRC-file, systematic and rate-matched contexts (rows of E values are
+ *      recovered first, as everywhere else).
+ *   7. refusals and launch behaviour: POLAR_ENOKERNEL for N > 1024; POLAR_EINVAL, the ctx staying usable, for any other algo,
+ *      for POLAR_Q8, and while a polar_cascl_set_stages rule with more than one stage is set (a frame's list would be that
+ *      of whichever stage decided it).  The calls are asynchronous on the ctx stream and read nothing back: after a warm-up
+ *      at the same B (which builds the tables of a context without dynamic bits and, on a rate-matched context, sizes the
+ *      scratch rows) they can be captured into a graph.  The kernels are scl_generic_body<..., DYN, LIST> (k_scl_list) and
+ *      k_scl_wide<..., DYN, LIST>: the decode of k_scl_dyn / k_scl_wide with another epilogue, a context without dynamic
+ *      bits being the D = 0 case.  polar_kernel_name keeps naming the ordinary decode's kernel.
+ * Masked-CRC selection (blind detection):
+ *   8. d_idx[f][m] = the smallest k < count[f] with rem[f][k] == masks[m], -1 if there is none.  By rule 3 that k is the
+ *      least-metric member of the list with that remainder.  Padding entries are never selected, whatever the mask.  Bits
+ *      of a mask at or above crc_r must be zero: d_masks is device memory and the call reads nothing back, so the library
+ *      does not check it -- such a mask matches nothing, every remainder being below 2^crc_r.
+ *   9. transmit convention: a transmitter that XORs mask bit i into u[I[i]] for i < crc_r sends a word whose remainder is
+ *      exactly the mask, because crc_tab[I[i]] = D^i mod g(D) = D^i for i < crc_r (with crc_systematic those are the
+ *      parity bits w[0..r)).  polar_payload_device on the gathered row returns the sent payload in both
+ *      CRC conventions (non-systematic: the quotient of v g + m by g is v; crc_systematic: the payload is w[r..A)); its
+ *      crc_ok is 0 for a mask m != 0, as it must be.
+ *  10. gather: row f of the output is paths[f][d_idx[f * idx_stride]]; an index of -1 (or outside 0 .. L - 1) takes rank 0,
+ *      so "the masked match, else the best path" is one call on column m of rule 8's d_idx (idx_stride = M).
+ * List soft output (max-log over the list):
+ *  11. candidates: the ranks k < count; with d_rem non-NULL only those with rem == want_rem, unless none of them matches, in
+ *      which case all ranks k < count are used.
+ *  12. domain 0 takes the path bits themselves, domain 1 each path's codeword x = u F^{(x)n} (formed inside the kernel).
+ *  13. value at position j, with m_b = the least pm over the candidates whose bit j is b: +clamp if no candidate has bit 1,
+ *      -clamp if none has bit 0, else min(max(m_1 - m_0, -clamp), clamp) -- one subtraction in binary64.  The sign is the
+ *      library's: positive means bit 0.  clamp must be > 0 and finite (POLAR_EINVAL).  The output is always double and every
+ *      value is exact.
+ * Out of scope: list output from the tuned kernels (their lists are the same lists by rule 5, their epilogues are not
+ * touched), N > 1024, POLAR_Q8, polar_group_*, log-sum soft output, 38.212 bit placement of the RNTI, early termination of
+ * blind decodes.
+ * Names: the four calls on device pointers are polar_list_decode, _select, _gather and _soft; polar_list_decode_host is the
+ * host-buffer form of the first.  Their output extents (guard words around every output at ragged batches, NULL outputs) are
+ * held by tests/test_gpu_list.py. */
+/* d_in as polar_decode_device ([B][E] on a rate-matched ctx).  Outputs, each nullable but not all: d_paths [B][L][N/32],
+ * d_pm [B][L], d_rem [B][L], d_count [B], d_flags [B]. */
+int polar_list_decode(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_paths,
+                      double *d_pm, uint32_t *d_rem, uint32_t *d_count, uint32_t *d_flags);
+/* host-buffer form: llr_in [B][N] ([B][E]), paths [B][L][N] ints 0/1, pm and rem [B][L], count and flags [B]; each output
+ * nullable, not all.  POLAR_ENOMEM (ctx usable) if the device buffers cannot be had. */
+int polar_list_decode_host(polar_ctx *ctx, const double *llr_in, size_t B, int *paths, double *pm, unsigned *rem,
+                           unsigned *count, unsigned *flags);
+/* rule 8: d_rem [B][L], d_count [B], d_masks [M] (device), 1 <= M <= 64 -> d_idx [B][M] */
+int polar_list_select(polar_ctx *ctx, const uint32_t *d_rem, const uint32_t *d_count, size_t B, const uint32_t *d_masks,
+                      int M, int32_t *d_idx);
+/* rule 10: d_paths [B][L][N/32], d_idx read at [f * idx_stride] (idx_stride >= 1) -> d_uhat_bits [B][N/32] */
+int polar_list_gather(polar_ctx *ctx, const uint32_t *d_paths, const int32_t *d_idx, int idx_stride, size_t B,
+                      uint32_t *d_uhat_bits);
+/* rules 11-13: d_rem nullable; domain 0 = u, 1 = x -> d_out [B][N] double */
+int polar_list_soft(polar_ctx *ctx, const uint32_t *d_paths, const double *d_pm, const uint32_t *d_count,
+                    const uint32_t *d_rem, uint32_t want_rem, int domain, double clamp, size_t B, double *d_out);
+
 /* --- Fixed-point min-sum decoding: int8 SC / SCL / CA-SCL (dtype POLAR_Q8; no reference counterpart) ----------------------
  * The decoder of hardware papers and 5G receivers: quantised LLRs, a check node that is a sign and a minimum, integer path
  * metrics.  Integer arithmetic has no rounding, so everything below is exact and is tested with == against a numpy model.

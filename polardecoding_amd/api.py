@@ -163,6 +163,11 @@ def load_library(testing=False):
     L.polar_q8_quantize_device.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp]
     L.polar_q8_decode_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     L.polar_q8_decode_batch.argtypes = [vp, C.POINTER(C.c_int8), C.c_size_t, ip, C.POINTER(C.c_int32), up]
+    L.polar_list_decode.argtypes = [vp, vp, C.c_int, C.c_double, C.c_size_t, vp, vp, vp, vp, vp]
+    L.polar_list_decode_host.argtypes = [vp, dp, C.c_size_t, ip, dp, up, up, up]
+    L.polar_list_select.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
+    L.polar_list_gather.argtypes = [vp, vp, vp, C.c_int, C.c_size_t, vp]
+    L.polar_list_soft.argtypes = [vp, vp, vp, vp, vp, C.c_uint, C.c_int, C.c_double, C.c_size_t, vp]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -953,6 +958,95 @@ class Decoder:
         self._check(self._lib.polar_bp_decode_batch(self._h, _ptr(llr, C.c_double), B, _ptr(uh, C.c_int),
                                                     _ptr(it, C.c_uint), _ptr(fl, C.c_uint)), "polar_bp_decode_batch")
         return uh, it, fl
+
+    # ---- list output (include/polar_hip.h, "List output") -------------------------------------------------
+    def decode_list_device(self, d_in, sigma=0.0, want_paths=True, want_pm=True, want_rem=True, want_count=True,
+                           want_flags=True):
+        """polar_list_decode: d_in as decode_device -> (paths [B][L][N/32] int32, pm [B][L] float64, rem [B][L] int32,
+        count [B] int32, flags [B] int32), rank k of a frame = its k-th live path in ascending (PM, slot); an output not
+        asked for is None and is not computed (at least one must be asked for)."""
+        import torch
+        B = self._dev_rows(d_in)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        dev, i32 = d_in.device, torch.int32
+        paths = torch.empty((B, self.L, self.NW), dtype=i32, device=dev) if want_paths else None
+        pm = torch.empty((B, self.L), dtype=torch.float64, device=dev) if want_pm else None
+        rem = torch.empty((B, self.L), dtype=i32, device=dev) if want_rem else None
+        count = torch.empty(B, dtype=i32, device=dev) if want_count else None
+        flags = torch.empty(B, dtype=i32, device=dev) if want_flags else None
+        self._check(self._lib.polar_list_decode(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), B,
+            *[C.c_void_p(t.data_ptr()) if t is not None else None for t in (paths, pm, rem, count, flags)]),
+            "polar_list_decode")
+        return paths, pm, rem, count, flags
+
+    def decode_list_batch(self, llr):
+        """polar_list_decode_host: host rows -> (paths [B][L][N] int32 0/1, pm [B][L], rem [B][L] uint32, count [B] uint32,
+        flags [B] uint32)."""
+        llr = self._rows(llr)
+        B = llr.shape[0]
+        paths = np.empty((B, self.L, self.N), dtype=np.int32)
+        pm = np.empty((B, self.L), dtype=np.float64)
+        rem = np.empty((B, self.L), dtype=np.uint32)
+        count = np.empty(B, dtype=np.uint32)
+        flags = np.empty(B, dtype=np.uint32)
+        self._check(self._lib.polar_list_decode_host(self._h, _ptr(llr, C.c_double), B, _ptr(paths, C.c_int),
+                                                      _ptr(pm, C.c_double), _ptr(rem, C.c_uint), _ptr(count, C.c_uint),
+                                                      _ptr(flags, C.c_uint)), "polar_list_decode_host")
+        return paths, pm, rem, count, flags
+
+    @staticmethod
+    def _list_t(t, shape, dtype, what):
+        if not (t.is_cuda and t.is_contiguous()) or t.dtype != dtype or tuple(t.shape[1:]) != tuple(shape):
+            raise ValueError(f"{what} must be a contiguous CUDA {dtype} tensor of shape [B]{list(shape)}")
+        return t.shape[0]
+
+    def list_select_device(self, rem, count, masks):
+        """polar_list_select: rem [B][L], count [B], masks [M] (int32 CUDA tensors, 1 <= M <= 64) -> idx [B][M] int32:
+        the least-metric rank whose remainder equals the mask, -1 if the list has none."""
+        import torch
+        B = self._list_t(rem, (self.L,), torch.int32, "rem")
+        if self._list_t(count, (), torch.int32, "count") != B:
+            raise ValueError("count must have one entry per frame")
+        if not (masks.is_cuda and masks.is_contiguous()) or masks.dtype != torch.int32 or masks.dim() != 1:
+            raise ValueError("masks must be a contiguous CUDA int32 tensor of shape [M]")
+        M = masks.shape[0]
+        idx = torch.empty((B, M), dtype=torch.int32, device=rem.device)
+        self._check(self._lib.polar_list_select(self._h, C.c_void_p(rem.data_ptr()), C.c_void_p(count.data_ptr()), B,
+                                                       C.c_void_p(masks.data_ptr()), M, C.c_void_p(idx.data_ptr())),
+                    "polar_list_select")
+        return idx
+
+    def list_gather_device(self, paths, idx):
+        """polar_list_gather: paths [B][L][N/32], idx [B] or a column idx[:, m] of list_select_device's result (int32;
+        -1 takes rank 0) -> bits [B][N/32] int32."""
+        import torch
+        B = self._list_t(paths, (self.L, self.NW), torch.int32, "paths")
+        if not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 1 or idx.shape[0] != B or (B > 1 and idx.stride(0) < 1):
+            raise ValueError("idx must be a CUDA int32 tensor of shape [B] (a column of a [B][M] tensor will do)")
+        stride = idx.stride(0) if B > 1 else 1
+        out = torch.empty((B, self.NW), dtype=torch.int32, device=paths.device)
+        self._check(self._lib.polar_list_gather(self._h, C.c_void_p(paths.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                                       stride, B, C.c_void_p(out.data_ptr())), "polar_list_gather")
+        return out
+
+    def list_soft_device(self, paths, pm, count, rem=None, want_rem=0, domain=0, clamp=64.0):
+        """polar_list_soft: max-log LLRs over the list -> [B][N] float64, positive = bit 0; domain 0: u, 1: x.  rem
+        given: only the ranks with remainder want_rem count, unless there is none."""
+        import torch
+        B = self._list_t(paths, (self.L, self.NW), torch.int32, "paths")
+        if self._list_t(pm, (self.L,), torch.float64, "pm") != B or self._list_t(count, (), torch.int32, "count") != B:
+            raise ValueError("pm and count must have one row per frame")
+        if rem is not None and self._list_t(rem, (self.L,), torch.int32, "rem") != B:
+            raise ValueError("rem must have one row per frame")
+        out = torch.empty((B, self.N), dtype=torch.float64, device=paths.device)
+        self._check(self._lib.polar_list_soft(
+            self._h, C.c_void_p(paths.data_ptr()), C.c_void_p(pm.data_ptr()), C.c_void_p(count.data_ptr()),
+            C.c_void_p(rem.data_ptr()) if rem is not None else None, int(want_rem) & 0xFFFFFFFF, int(domain), float(clamp), B,
+            C.c_void_p(out.data_ptr())), "polar_list_soft")
+        return out
 
     # ---- encoder side ---------------------------------------------------------------------------------
     @staticmethod

@@ -1,6 +1,6 @@
-// k_scl_launch.h -- launch code of scl_generic_body's two kernels and of k_scl_wide, shared by k_generic.hip (k_scl_generic),
-// k_dyn.hip (k_scl_dyn) and k_wide.hip (k_scl_wide: its own ladder over L, launch_scl below it), one translation unit each,
-// compiled in parallel.  Each names its kernel in a trait K:
+// k_scl_launch.h -- launch code of scl_generic_body's kernels and of k_scl_wide, shared by k_generic.hip (k_scl_generic),
+// k_dyn.hip (k_scl_dyn), k_wide.hip (k_scl_wide: its own ladder over L, launch_scl below it) and k_list.hip (their LIST
+// instantiations), one translation unit each, compiled in parallel.  Each names its kernel in a trait K:
 //     K::Params                                  the kernel's parameter struct
 //     K::kernel<R, IN, LOGL, GA>()               the instantiation
 //     K::lds_bytes<R, LOGL>(N, ga)               its dynamic LDS

@@ -128,6 +128,11 @@ struct polar_ctx : Lane {
     bool force_spill = false;   // no tuned L = 8 kernel; with force_generic: the global-scratch variant of k_scl_generic
     int big_split = 0;          // 35 | 46 | 57: LDS / scratch split of k_scl_big; 0 = the measured best
     size_t chunk_bytes = kChunkBytes;   // bytes of rows per pass of the chunked loops (chunk_rows, polar_hip.hip)
+    // list output (polar_list_decode): the D = 0 constraint tables a ctx without dynamic bits runs k_scl_list with
+    // (row = -1 at every leaf, one zero mask row), built on first use; staging of polar_list_decode_host
+    DevMem<uint32_t> d_list_mask;
+    DevMem<int> d_list_row;
+    Buf list_paths, list_pm, list_rem, list_cnt;
 };
 
 // c's lane <-> c->lane_b: work enqueued through c afterwards runs on the other stream with the other stream's buffers
@@ -323,6 +328,14 @@ int q8_decode(polar_ctx *c, const int8_t *d_q, size_t B, uint32_t *d_bits, int32
 int q8_quantize(polar_ctx *c, const void *d_in, bool in32, double sigma, size_t count, int8_t *d_out);   // count < 2^32 * 256
 int q8_pm_f64(polar_ctx *c, const int32_t *d_pm, size_t B, double *d_out);
 void q8_quantize_host(const double *in, size_t n, double sigma, double scale, int Cc, int8_t *out);
+// k_list.hip: list output (list_kernel.h): the LIST epilogue of scl_generic_body / k_scl_wide with the given constraint
+// tables (uses c->logL, c->force_spill), and the three kernels that work on a list
+int list_decode(polar_ctx *c, const polar::SclParams &P, const uint32_t *d_mask, const int *d_row, bool r32, bool in32,
+                uint32_t *d_paths, double *d_pm, uint32_t *d_rem, uint32_t *d_count);
+int list_select(polar_ctx *c, const uint32_t *d_rem, const uint32_t *d_count, size_t B, const uint32_t *d_masks, int M, int32_t *d_idx);
+int list_gather(polar_ctx *c, const uint32_t *d_paths, const int32_t *d_idx, int idx_stride, size_t B, uint32_t *d_out);
+int list_soft(polar_ctx *c, const uint32_t *d_paths, const double *d_pm, const uint32_t *d_count, const uint32_t *d_rem,
+              uint32_t want_rem, int domain, double clamp, size_t B, double *d_out);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

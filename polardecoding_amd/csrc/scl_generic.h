@@ -25,6 +25,7 @@
 #include "polar_math.h"
 #include "polar_lut.h"
 #include "polar_params.h"
+#include "list_out.h"
 
 namespace polar {
 
@@ -51,9 +52,13 @@ __device__ __forceinline__ float ld_bypass(const float *p) { return __hip_atomic
 // level arrays alpha[L][N] live in a per-workgroup slice of a global scratch buffer and the channel LLRs are
 // read from the input; only the bit-packed partial sums stay in LDS.
 // DYN = false: dyn_mask and dyn_row are never read.
-template <typename R, typename IN, int LOGL, bool GA, bool DYN>
-__device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint32_t *dyn_mask, const int *dyn_row)
+// LIST = true (needs DYN, k_list.hip): the decode is the same; the epilogue writes every live slot to *LO in ascending
+// (PM, slot) instead of the chosen path to P.out_bits / P.pm.  LIST = false: LO is never read.
+template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false>
+__device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint32_t *dyn_mask, const int *dyn_row,
+                                                 const ListOut *LO = nullptr)
 {
+    static_assert(DYN || !LIST, "the list epilogue reads the per-path history");
     constexpr int L = 1 << LOGL;
     constexpr int S = 64 / L;
     const int N = P.N, n = P.n, NW = N >> 5;
@@ -332,8 +337,26 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             }
             if (any) fl |= 0x2u;
         }
+        // LIST: rank of this slot among the live ones in ascending (PM, slot), counted over the shuffled metrics; the S lanes
+        // of a path write its history words to row `rank`, the lanes of a dead slot p the padding row p (>= act)
+        if constexpr (LIST) {
+            int rank = 0;
+            for (int q = 0; q < act; ++q) {
+                const R pq = __shfl(PM, q * S);
+                rank += (pq < PM || (pq == PM && q < p)) ? 1 : 0;
+            }
+            const bool live = p < act;
+            const size_t row = (size_t)frame * L + (size_t)(live ? rank : p);
+            if (LO->paths)
+                for (int w = pos; w < NW; w += S) LO->paths[row * NW + w] = !live ? 0u : (w == 0) ? h0 : hist[p * NW + w];
+            if (pos == 0) {
+                if (LO->pm) LO->pm[row] = live ? (double)PM : __builtin_huge_val();
+                if (LO->rem) LO->rem[row] = live ? crc : 0u;
+            }
+            if (lane == 0 && LO->count) LO->count[frame] = (uint32_t)act;
+        }
         // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
-        if constexpr (DYN) {
+        else if constexpr (DYN) {
             const uint32_t w0 = __shfl(h0, best * S);
             for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = (w == 0) ? w0 : hist[best * NW + w];
         } else if (n <= 5) {
@@ -365,7 +388,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = xw[w];
         }
         if (lane == 0) {
-            if (P.pm) P.pm[frame] = P.sc_mode ? 0.0 : (double)best_pm;
+            if (!LIST && P.pm) P.pm[frame] = P.sc_mode ? 0.0 : (double)best_pm;
             if (P.flags) P.flags[frame] = P.sc_mode ? 0u : fl;
         }
         __syncthreads();

@@ -40,6 +40,8 @@
 // Every __syncthreads() and every __ballot sits in control flow that is uniform for the workgroup: the conditions around
 // them are functions of j, the frozen mask, the constraint row and act only, never of the path.
 #pragma once
+#include <type_traits>
+
 #include "scl_dyn.h"
 
 namespace polar {
@@ -71,10 +73,21 @@ __device__ __forceinline__ void wide_level_barrier()
     __syncthreads();
 }
 
-template <typename R, typename IN, int LOGL, bool GA, bool DYN>
-__global__ __launch_bounds__(1 << LOGL) void k_scl_wide(DynParams DP)
+// LIST = true (needs DYN; launched by k_list.hip): the kernel takes a ListParams, the decode is the same, and the epilogue
+// writes every live slot to its ListOut in ascending (PM, slot) instead of the chosen path.
+struct ListParams {
+    DynParams d;
+    ListOut o;
+};
+__device__ __forceinline__ const DynParams &wide_dyn(const DynParams &P) { return P; }
+__device__ __forceinline__ const DynParams &wide_dyn(const ListParams &P) { return P.d; }
+
+template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false>
+__global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditional<LIST, ListParams, DynParams>::type KP)
 {
+    const DynParams &DP = wide_dyn(KP);
     static_assert(LOGL >= 6 && LOGL <= 8, "one thread per path: 1, 2 or 4 wavefronts");
+    static_assert(DYN || !LIST, "the list epilogue reads the per-path history");
     constexpr int L = 1 << LOGL;
     constexpr int NWAVES = L / 64;
     using Lay = WideLds<R, LOGL, DYN>;
@@ -340,8 +353,25 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(DynParams DP)
             best_pm = best_ok_pm;
             fl |= 0x2u;
         }
+        // LIST: rank of this slot among the live ones in ascending (PM, slot), counted over the metrics in cand[]; the path's
+        // thread writes its history words to row `rank`, the thread of a dead slot p the padding row p (>= act)
+        if constexpr (LIST) {
+            const ListOut *LO = &KP.o;
+            int rank = 0;
+            for (int q = 0; q < act; ++q) {
+                const R pq = cand[q];
+                rank += (pq < PM || (pq == PM && q < p)) ? 1 : 0;
+            }
+            const bool live = p < act;
+            const size_t row = (size_t)frame * L + (size_t)(live ? rank : p);
+            if (LO->paths)
+                for (int w = 0; w < NW; ++w) LO->paths[row * NW + w] = !live ? 0u : (w == 0) ? h0 : hist[w * L + p];
+            if (LO->pm) LO->pm[row] = live ? (double)PM : __builtin_huge_val();
+            if (LO->rem) LO->rem[row] = live ? crc : 0u;
+            if (p == 0 && LO->count) LO->count[frame] = (uint32_t)act;
+        }
         // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
-        if constexpr (DYN) {
+        else if constexpr (DYN) {
             if (p < NW) P.out_bits[(size_t)frame * NW + p] = (p == 0) ? xh0[best] : hist[p * L + best];
         } else if (n <= 5) {
             uint32_t x = xbl0[best];
@@ -371,7 +401,7 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(DynParams DP)
             if (p < NW) P.out_bits[(size_t)frame * NW + p] = xw[p * L];
         }
         if (p == 0) {
-            if (P.pm) P.pm[frame] = (double)best_pm;
+            if (!LIST && P.pm) P.pm[frame] = (double)best_pm;
             if (P.flags) P.flags[frame] = fl;
         }
         __syncthreads();
