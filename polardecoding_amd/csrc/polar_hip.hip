@@ -142,6 +142,40 @@ size_t chunk_rows(const polar_ctx *c, size_t B, size_t row_bytes, size_t floor =
     return std::min(B, std::max(floor, c->chunk_bytes / row_bytes));
 }
 
+constexpr size_t kMaxBatch = 0x7fffffffull;   // frames per call: the kernels count them in an int
+
+// Entry points whose host reads a count back between launches refuse a stream that is being captured.
+int refuse_capture(polar_ctx *c)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
+    return cs != hipStreamCaptureStatusNone ? POLAR_EINVAL : POLAR_OK;
+}
+
+// The compaction buffers for lists of at most n frames: one list, its block counts and the device count; pingpong: the second
+// list and the staged flags of the decoders whose later passes compact what the pass before left open.
+int ensure_compaction(polar_ctx *c, size_t n, bool pingpong)
+{
+    int rc;
+    if ((rc = ensure(c, c->ad_idx[0], n * sizeof(uint32_t)))) return rc;
+    for (Buf *b : {&c->ad_idx[1], &c->ad_sflags})
+        if (pingpong && (rc = ensure(c, *b, n * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(n) * sizeof(uint32_t)))) return rc;
+    return ensure(c, c->ad_cnt, sizeof(uint32_t));
+}
+
+// The frames of idx_in[0 .. n) (null: frames 0 .. n) whose flags lack a bit of `need`, in order, to idx_out; *count: how many,
+// read back -- one 4-byte copy and a stream sync.
+int compact_open(polar_ctx *c, const uint32_t *flags, const uint32_t *idx_in, size_t n, uint32_t need, uint32_t *idx_out, size_t *count)
+{
+    if (int rc = polar_tu::ad_compact(c, flags, idx_in, n, need, (uint32_t *)c->ad_blk.p, idx_out, (uint32_t *)c->ad_cnt.p)) return rc;
+    uint32_t h = 0;
+    HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *count = h;
+    return POLAR_OK;
+}
+
 // contexts whose code carries a CRC: r, crc_tab, the generator's CRC multiply, the systematic K-bit error metric
 // (BP list decoding: optional, crc_r = 0 is a code without one)
 bool has_crc(int algo) { return algo == POLAR_ALGO_CASCL || algo == POLAR_ALGO_SCF || algo == POLAR_ALGO_BPL; }
@@ -328,7 +362,7 @@ int decode_fixed(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, si
 {
     if (!c || !d_in || !d_bits) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
-    if (B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B > kMaxBatch) return POLAR_EINVAL;
     const polar_cfg &g = c->cfg;
     if (g.dtype == POLAR_Q8) return q8_decode_rows(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags);
     const bool f32 = g.dtype == POLAR_F32;
@@ -399,25 +433,20 @@ void sync_stage_ctx(polar_ctx *c)
 int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                    double *d_pm, uint32_t *d_flags, uint32_t *d_list)
 {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the per-stage syncs cannot be captured
+    int rc;
+    if ((rc = refuse_capture(c))) return rc;   // the per-stage syncs cannot be captured
     sync_stage_ctx(c);
     const std::vector<int> &st = c->cascl_stages;
     const int m = (int)st.size(), N = c->cfg.N, NW = c->NW;
     const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
     // later stages run in chunks of at most 256 MiB of gathered input
     const size_t CH = chunk_rows(c, B, row);
-    int rc;
     // every buffer of the call, before its first launch
     if (!d_flags) {
         if ((rc = ensure(c, c->ad_flags, B * sizeof(uint32_t)))) return rc;
         d_flags = (uint32_t *)c->ad_flags.p;
     }
-    for (Buf *b : {&c->ad_idx[0], &c->ad_idx[1], &c->ad_sflags})
-        if ((rc = ensure(c, *b, B * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
+    if ((rc = ensure_compaction(c, B, true))) return rc;
     if ((rc = ensure(c, c->ad_in, CH * row))) return rc;
     if ((rc = ensure(c, c->ad_bits, CH * NW * sizeof(uint32_t)))) return rc;
     if (d_pm && (rc = ensure(c, c->ad_pm, CH * sizeof(double)))) return rc;
@@ -430,13 +459,7 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
     size_t n = B;
     for (int s = 1; s < m; ++s) {
         uint32_t *idx = (uint32_t *)c->ad_idx[(s - 1) & 1].p;
-        if ((rc = polar_tu::ad_compact(c, cur_flags, cur_idx, n, POLAR_FLAG_CRC_PASS, (uint32_t *)c->ad_blk.p, idx,
-                                          (uint32_t *)c->ad_cnt.p)))
-            return rc;
-        uint32_t h = 0;
-        HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        n = h;
+        if ((rc = compact_open(c, cur_flags, cur_idx, n, POLAR_FLAG_CRC_PASS, idx, &n))) return rc;
         if (n == 0) break;
         polar_ctx *sc = c->stage_ctx[(size_t)s] ? c->stage_ctx[(size_t)s] : c;
         uint32_t *sflags = (uint32_t *)c->ad_sflags.p;
@@ -470,17 +493,15 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
 int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
                uint32_t *d_flags, uint32_t *d_attempts, int32_t *d_sets = nullptr)
 {
-    if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!d_in || !d_bits || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the host reads the failing count
+    int rc;
+    if ((rc = refuse_capture(c))) return rc;   // the host reads the failing count
     const int T = c->scf_T, NW = c->NW;
     const int omega = T > 0 ? c->scf_omega : 0;
     int Tk[polar::SCF_MAX_ORDER + 1] = {T, 0, 0, 0}, Ttot = T;
     for (int k = 1; k < omega; ++k) Ttot += (Tk[k] = c->scf_Tk[k]);
     const bool r32 = c->cfg.dtype == POLAR_F32, in32 = in_is_f32 != 0;
-    int rc;
     if (!d_flags) {
         if ((rc = ensure(c, c->ad_flags, B * sizeof(uint32_t)))) return rc;
         d_flags = (uint32_t *)c->ad_flags.p;
@@ -493,16 +514,10 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     if ((rc = polar_tu::scf_lanes(c, P, polar::SCF_CHECK, r32, in32))) return rc;
     P.T = T;
     if (T == 0) return POLAR_OK;
-    if ((rc = ensure(c, c->ad_idx[0], B * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
+    if ((rc = ensure_compaction(c, B, false))) return rc;
     uint32_t *idx = (uint32_t *)c->ad_idx[0].p;
-    if ((rc = polar_tu::ad_compact(c, d_flags, nullptr, B, POLAR_FLAG_CRC_PASS, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p)))
-        return rc;
-    uint32_t h = 0;
-    HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    size_t n = h;
+    size_t n = 0, h = 0;
+    if ((rc = compact_open(c, d_flags, nullptr, B, POLAR_FLAG_CRC_PASS, idx, &n))) return rc;
     if (n == 0) return POLAR_OK;
     if (omega > 0) {
         const size_t rsz = r32 ? 4 : 8, pair_bytes = (size_t)NW * sizeof(uint32_t);
@@ -552,10 +567,7 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
             }
             if (last) break;
             base += (int)Tl;
-            if ((rc = polar_tu::ad_compact(c, spass, nullptr, n, 1u, (uint32_t *)c->ad_blk.p, surv, (uint32_t *)c->ad_cnt.p)))
-                return rc;
-            HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if ((rc = compact_open(c, spass, nullptr, n, 1u, surv, &h))) return rc;
             if (h == 0) break;
             uint32_t *nidx = (uint32_t *)c->ad_idx[idx == (uint32_t *)c->ad_idx[0].p ? 1 : 0].p;
             if ((rc = polar_tu::scf_merge(c, r32, c->scf_lkey.p, lpos, lcnt, sets, surv, idx, h, (int)Tl, (int)Tnx,
@@ -604,17 +616,15 @@ int scf_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
 int bpl_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits, double *d_pm,
                uint32_t *d_flags, uint32_t *d_iters, uint32_t *d_graph, uint32_t *d_total)
 {
-    if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!d_in || !d_bits || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return POLAR_EINVAL;   // the host reads the count of open frames
+    int rc;
+    if ((rc = refuse_capture(c))) return rc;   // the host reads the count of open frames
     const int P = (int)c->bpl_ident.size(), N = c->cfg.N, NW = c->NW;
     const bool crc = c->cfg.crc_r > 0, direct = c->bpl_ident[0] != 0;
     const uint32_t need = POLAR_FLAG_BP_CONVERGED | (crc ? POLAR_FLAG_CRC_PASS : 0u);
     const size_t row = (size_t)N * (in_is_f32 ? 4 : 8);
     const size_t CH = chunk_rows(c, B, row);
-    int rc;
     // every buffer of the call, before its first launch
     if ((rc = ensure(c, c->bpl_siters, B * sizeof(uint32_t)))) return rc;
     if (!d_flags && (P > 1 || crc || d_graph || d_total)) {
@@ -622,10 +632,7 @@ int bpl_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
         d_flags = (uint32_t *)c->ad_flags.p;
     }
     if (P > 1 || !direct) {
-        for (Buf *b : {&c->ad_idx[0], &c->ad_idx[1], &c->ad_sflags})
-            if ((rc = ensure(c, *b, B * sizeof(uint32_t)))) return rc;
-        if ((rc = ensure(c, c->ad_blk, 2 * polar_tu::ad_blocks(B) * sizeof(uint32_t)))) return rc;
-        if ((rc = ensure(c, c->ad_cnt, sizeof(uint32_t)))) return rc;
+        if ((rc = ensure_compaction(c, B, true))) return rc;
         if ((rc = ensure(c, c->ad_in, CH * row))) return rc;
         if ((rc = ensure(c, c->ad_bits, CH * NW * sizeof(uint32_t)))) return rc;
     }
@@ -669,12 +676,7 @@ int bpl_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size
     size_t n = B;
     for (int p = 1; p < P; ++p) {
         uint32_t *idx = (uint32_t *)c->ad_idx[(p - 1) & 1].p;
-        if ((rc = polar_tu::ad_compact(c, cur_flags, cur_idx, n, need, (uint32_t *)c->ad_blk.p, idx, (uint32_t *)c->ad_cnt.p)))
-            return rc;
-        uint32_t h = 0;
-        HIP_TRY(c, hipMemcpyAsync(&h, c->ad_cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        n = h;
+        if ((rc = compact_open(c, cur_flags, cur_idx, n, need, idx, &n))) return rc;
         if (n == 0) break;
         for (size_t off = 0; off < n; off += CH)
             if ((rc = staged(p, idx + off, 0, std::min(CH, n - off), sflags + off, siters + off))) return rc;
@@ -690,7 +692,7 @@ int scan_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, siz
                 uint32_t *d_flags, const uint32_t *d_frozen, void *d_llr_u, void *d_ext_x)
 {
     const size_t rsz = c->cfg.dtype == POLAR_F32 ? 4 : 8;
-    if (!d_in || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % (in_is_f32 ? 4 : 8))) return POLAR_EINVAL;
+    if (!d_in || B > kMaxBatch || (reinterpret_cast<uintptr_t>(d_in) % (in_is_f32 ? 4 : 8))) return POLAR_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_llr_u) | reinterpret_cast<uintptr_t>(d_ext_x)) % rsz) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     if (d_pm) HIP_TRY(c, hipMemsetAsync(d_pm, 0, B * sizeof(double), c->stream));
@@ -713,7 +715,7 @@ int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double si
     if (c && c->cfg.algo == POLAR_ALGO_SCAN) return scan_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_llr_u, d_ext_x);
     if (c && c->cfg.algo == POLAR_ALGO_SCF) return scf_decode(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters, d_sets);
     if (c && c->cfg.algo == POLAR_ALGO_CASCL) {
-        if (!d_in || !d_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+        if (!d_in || !d_bits || B > kMaxBatch) return POLAR_EINVAL;
         if (B == 0) return POLAR_OK;
         if (!c->cascl_stages.empty()) return cascl_adaptive(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_iters);
         if (d_iters) HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), c->cfg.L, B, c->stream));
@@ -722,9 +724,25 @@ int decode_device_plain(polar_ctx *c, const void *d_in, int in_is_f32, double si
     return decode_fixed(c, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, d_frozen, d_iters);
 }
 
-// every decode of the C ABI.  On a rate-matched ctx (polar_create_rm) the rows hold E values: k_rm_recover turns them into
-// N-wide rows of the input type in ctx scratch (chunks of at most 256 MiB), which the ctx's own decoder reads with sigma = 0
-// (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (it is part of the lane, polar_host.h).
+// The rows of a rate-matched ctx (polar_create_rm) hold E values: k_rm_recover turns them into N-wide rows of the input type
+// in ctx scratch, in chunks of at most 256 MiB, and body(rows, off, nc) decodes the nc frames from frame off on with
+// sigma = 0 (include/polar_hip.h rule 7).  c->rm_rows belongs to c->stream (it is part of the lane, polar_host.h).
+template <class Body> int for_rm_chunks(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, Body body)
+{
+    const size_t esz = in_is_f32 ? 4 : 8, row = (size_t)c->cfg.N * esz;
+    const size_t CH = chunk_rows(c, B, row);
+    int rc;
+    if ((rc = ensure(c, c->rm_rows, CH * row))) return rc;
+    for (size_t off = 0; off < B; off += CH) {
+        const size_t nc = std::min(CH, B - off);
+        if ((rc = polar_tu::rm_recover(c, (const char *)d_in + off * (size_t)c->rm_E * esz, in_is_f32 != 0, sigma, nc, c->rm_rows.p)))
+            return rc;
+        if ((rc = body(c->rm_rows.p, off, nc))) return rc;
+    }
+    return POLAR_OK;
+}
+
+// every decode of the C ABI: the ctx's decoder, behind the recovery on a rate-matched ctx
 int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_bits,
                        double *d_pm, uint32_t *d_flags, const uint32_t *d_frozen, uint32_t *d_iters = nullptr,
                        void *d_llr_u = nullptr, void *d_ext_x = nullptr, uint32_t *d_graph = nullptr, uint32_t *d_total = nullptr,
@@ -736,25 +754,15 @@ int decode_device_impl(polar_ctx *c, const void *d_in, int in_is_f32, double sig
     const size_t esz = in_is_f32 ? 4 : 8;
     const bool scan = c->cfg.algo == POLAR_ALGO_SCAN;   // its three outputs are nullable
     const size_t soft_row = (size_t)c->cfg.N * (c->cfg.dtype == POLAR_F32 ? 4 : 8);
-    if (!d_in || (!d_bits && !scan) || B > 0x7fffffffull || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
+    if (!d_in || (!d_bits && !scan) || B > kMaxBatch || (reinterpret_cast<uintptr_t>(d_in) % esz)) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
-    const size_t row = (size_t)c->cfg.N * esz;
-    const size_t CH = chunk_rows(c, B, row);
-    int rc;
-    if ((rc = ensure(c, c->rm_rows, CH * row))) return rc;
-    for (size_t off = 0; off < B; off += CH) {
-        const size_t nc = std::min(CH, B - off);
-        if ((rc = polar_tu::rm_recover(c, (const char *)d_in + off * (size_t)c->rm_E * esz, in_is_f32 != 0, sigma, nc,
-                                       c->rm_rows.p)))
-            return rc;
-        if ((rc = decode_device_plain(c, c->rm_rows.p, in_is_f32, 0.0, nc, d_bits ? d_bits + off * (size_t)c->NW : nullptr,
-                                      d_pm ? d_pm + off : nullptr, d_flags ? d_flags + off : nullptr, d_frozen,
-                                      d_iters ? d_iters + off : nullptr, d_llr_u ? (char *)d_llr_u + off * soft_row : nullptr,
-                                      d_ext_x ? (char *)d_ext_x + off * soft_row : nullptr, d_graph ? d_graph + off : nullptr,
-                                      d_total ? d_total + off : nullptr, d_sets ? d_sets + off * polar::SCF_MAX_ORDER : nullptr)))
-            return rc;
-    }
-    return POLAR_OK;
+    return for_rm_chunks(c, d_in, in_is_f32, sigma, B, [&](const void *rows, size_t off, size_t nc) {
+        return decode_device_plain(c, rows, in_is_f32, 0.0, nc, d_bits ? d_bits + off * (size_t)c->NW : nullptr,
+                                   d_pm ? d_pm + off : nullptr, d_flags ? d_flags + off : nullptr, d_frozen,
+                                   d_iters ? d_iters + off : nullptr, d_llr_u ? (char *)d_llr_u + off * soft_row : nullptr,
+                                   d_ext_x ? (char *)d_ext_x + off * soft_row : nullptr, d_graph ? d_graph + off : nullptr,
+                                   d_total ? d_total + off : nullptr, d_sets ? d_sets + off * polar::SCF_MAX_ORDER : nullptr);
+    });
 }
 
 // the kernel instantiation decode_device_impl will launch for this ctx: kernel_family() for input of the arithmetic type
@@ -845,6 +853,34 @@ void unpack_words(const uint32_t *w, int NW, int *out)
         std::memcpy(out + 32 * i + 16, &tab[(x >> 16) & 255u], sizeof(Row));
         std::memcpy(out + 32 * i + 24, &tab[x >> 24], sizeof(Row));
     }
+}
+
+// rows of `width` ints (non-zero = 1) -> rows of ceil(width / 32) words, value j of a row in bit j & 31 of its word j / 32
+std::vector<uint32_t> pack_rows(const int *v, size_t rows, int width)
+{
+    const size_t W = (size_t)width, WW = (W + 31) / 32;
+    std::vector<uint32_t> w(rows * WW, 0u);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t j = 0; j < W; ++j)
+            if (v[r * W + j]) w[r * WW + (j >> 5)] |= 1u << (j & 31);
+    return w;
+}
+
+// the reverse: the whole words of a row through unpack_words, the values of a last partial word one by one
+void unpack_rows(const uint32_t *w, size_t rows, int width, int *out)
+{
+    const size_t W = (size_t)width, WW = (W + 31) / 32;
+    for (size_t r = 0; r < rows; ++r) {
+        unpack_words(w + r * WW, width / 32, out + r * W);
+        for (size_t j = W / 32 * 32; j < W; ++j) out[r * W + j] = (int)((w[r * WW + (j >> 5)] >> (j & 31)) & 1u);
+    }
+}
+
+// a one-piece host form whose launcher failed: nothing of the call is left in flight when it returns
+int sync_fail(polar_ctx *c, int rc)
+{
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
 }
 
 // helper threads per direction of the host pipeline (staging of the caller's rows / unpacking of the decisions)
@@ -1439,7 +1475,7 @@ int polar_dyn_pc5g(int N, const int *q_i, int n_qi, int n_pc, int n_pc_wm, int *
 
 int polar_rm_recover_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, void *d_out)
 {
-    if (!c || c->rm_mode == POLAR_RM_NONE || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || c->rm_mode == POLAR_RM_NONE || !d_in || !d_out || B > kMaxBatch) return POLAR_EINVAL;
     const size_t esz = in_is_f32 ? 4 : 8;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) % esz) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
@@ -1725,7 +1761,7 @@ int polar_scan_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u
 {
     if (!c || c->cfg.algo != POLAR_ALGO_SCAN || !llr_in) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
-    if (B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B > kMaxBatch) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     const int N = c->cfg.N, NW = c->NW;
     const size_t W = c->rm_mode != POLAR_RM_NONE ? (size_t)c->rm_E : (size_t)N;
@@ -1738,7 +1774,7 @@ int polar_scan_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u
     HIP_TRY(c, hipMemcpyAsync(c->in.p, llr_in, B * W * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if ((rc = decode_device_impl(c, c->in.p, 0, 0.0, B, u_hat ? (uint32_t *)c->bits.p : nullptr, nullptr, nullptr, c->d_frozen,
                                  nullptr, llr_u ? c->scan_llr.p : nullptr, ext_x ? c->scan_ext.p : nullptr)))
-        return rc;
+        return sync_fail(c, rc);
     std::vector<uint32_t> w;
     if (u_hat) {
         w.resize(B * (size_t)NW);
@@ -1747,7 +1783,7 @@ int polar_scan_decode_batch(polar_ctx *c, const double *llr_in, size_t B, int *u
     if (llr_u) HIP_TRY(c, hipMemcpyAsync(llr_u, c->scan_llr.p, soft, hipMemcpyDeviceToHost, c->stream));
     if (ext_x) HIP_TRY(c, hipMemcpyAsync(ext_x, c->scan_ext.p, soft, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t f = 0; u_hat && f < B; ++f) unpack_words(w.data() + f * NW, NW, u_hat + f * (size_t)N);
+    if (u_hat) unpack_rows(w.data(), B, N, u_hat);
     return POLAR_OK;
 }
 
@@ -1785,7 +1821,7 @@ int polar_bp_readout_device(polar_ctx *c, const void *d_in, int in_is_f32, doubl
                             uint32_t *d_uhat_bits)
 {
     if (!c || !d_in || !d_u_bits || !checkpoints || !d_E) return POLAR_EINVAL;
-    if (c->cfg.algo != POLAR_ALGO_BP || ncp < 1 || ncp > 8 || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (c->cfg.algo != POLAR_ALGO_BP || ncp < 1 || ncp > 8 || B > kMaxBatch) return POLAR_EINVAL;
     if (c->bp_stop != POLAR_BP_STOP_NONE) return POLAR_EINVAL;   // the checkpoints need every frame to run all round trips
     if (c->rm_mode != POLAR_RM_NONE) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
@@ -1816,24 +1852,20 @@ int polar_bp_readout_batch(polar_ctx *c, const double *in, double sigma, size_t 
     if ((rc = ensure(c, c->bits, B * NW * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->gen_u, B * NW * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(c, c->gen_cnt, sizeof(unsigned long long) * 8 * (size_t)(n + 1)))) return rc;
-    std::vector<uint32_t> uw(B * (size_t)NW, 0u);
-    for (size_t b = 0; b < B; ++b)
-        for (int j = 0; j < N; ++j)
-            if (u[b * N + j]) uw[b * NW + (j >> 5)] |= 1u << (j & 31);
+    const std::vector<uint32_t> uw = pack_rows(u, B, N);
     HIP_TRY(c, hipMemcpyAsync(c->in.p, in, B * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->gen_u.p, uw.data(), uw.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->gen_cnt.p, 0, sizeof(unsigned long long) * 8 * (size_t)(n + 1), c->stream));
     rc = polar_bp_readout_device(c, c->in.p, 0, sigma, B, (const uint32_t *)c->gen_u.p, checkpoints, ncp,
                                  (unsigned long long *)c->gen_cnt.p, (uint32_t *)c->bits.p);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (rc) return sync_fail(c, rc);
     std::vector<unsigned long long> he((size_t)ncp * (n + 1));
     std::vector<uint32_t> hb(u_hat ? B * (size_t)NW : 0);
     HIP_TRY(c, hipMemcpyAsync(he.data(), c->gen_cnt.p, he.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     if (u_hat) HIP_TRY(c, hipMemcpyAsync(hb.data(), c->bits.p, hb.size() * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < he.size(); ++i) E[i] += he[i];
-    if (u_hat)
-        for (size_t b = 0; b < B; ++b) unpack_words(hb.data() + b * NW, NW, u_hat + b * (size_t)N);
+    if (u_hat) unpack_rows(hb.data(), B, N, u_hat);
     return POLAR_OK;
 }
 
@@ -1844,7 +1876,7 @@ int polar_count_errors_device(polar_ctx *c, const uint32_t *d_uhat, const uint32
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     if (c->sys_polar) {   // systematic polar code: the comparison is on x_hat[I] against x[I]
-        if (B > 0x7fffffffull) return POLAR_EINVAL;
+        if (B > kMaxBatch) return POLAR_EINVAL;
         return polar_tu::enc_count_sys(c, d_uhat, d_u, B, d_counters, d_frame_err);
     }
     polar::CountParams P{d_uhat, d_u, c->d_info, d_counters, d_frame_err, c->NW, (int)B};
@@ -1858,7 +1890,7 @@ int polar_count_errors_device(polar_ctx *c, const uint32_t *d_uhat, const uint32
 int polar_stop_rule_cut_device(polar_ctx *c, const uint32_t *d_frame_err, size_t B, unsigned need, size_t min_frames,
                                unsigned long long *d_out)
 {
-    if (!c || !d_frame_err || !d_out || (need < 1 && min_frames < 1) || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !d_frame_err || !d_out || (need < 1 && min_frames < 1) || B > kMaxBatch) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     if (B == 0) {
         HIP_TRY(c, hipMemsetAsync(d_out, 0, 3 * sizeof(unsigned long long), c->stream));
@@ -1878,7 +1910,7 @@ int polar_stop_rule_batch_y(polar_ctx *c, const double *y, double sigma, const u
         return POLAR_EINVAL;
     *consumed = 0; *block_errors = 0; *bit_errors = 0;
     if (B == 0) return POLAR_OK;
-    if (B > 0x7fffffffull) return POLAR_EINVAL;
+    if (B > kMaxBatch) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     const int NW = c->NW;
     const int W = c->rm_mode != POLAR_RM_NONE ? c->rm_E : c->cfg.N;   // values per row
@@ -1892,10 +1924,10 @@ int polar_stop_rule_batch_y(polar_ctx *c, const double *y, double sigma, const u
     HIP_TRY(c, hipMemcpyAsync(c->in.p, y, B * W * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->gen_u.p, u_bits, B * NW * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(cnt, 0, 5 * sizeof(unsigned long long), c->stream));
-    if ((rc = decode_device_impl(c, c->in.p, 0, sigma, B, (uint32_t *)c->bits.p, nullptr, nullptr, c->d_frozen))) return rc;
+    if ((rc = decode_device_impl(c, c->in.p, 0, sigma, B, (uint32_t *)c->bits.p, nullptr, nullptr, c->d_frozen))) return sync_fail(c, rc);
     if ((rc = polar_count_errors_device(c, (uint32_t *)c->bits.p, (uint32_t *)c->gen_u.p, B, cnt, (uint32_t *)c->flags.p)))
-        return rc;
-    if ((rc = polar_stop_rule_cut_device(c, (uint32_t *)c->flags.p, B, need, min_frames, cnt + 2))) return rc;
+        return sync_fail(c, rc);
+    if ((rc = polar_stop_rule_cut_device(c, (uint32_t *)c->flags.p, B, need, min_frames, cnt + 2))) return sync_fail(c, rc);
     unsigned long long h[3];
     HIP_TRY(c, hipMemcpyAsync(h, cnt + 2, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1908,7 +1940,7 @@ int polar_stop_rule_batch_y(polar_ctx *c, const double *y, double sigma, const u
 // ---- Monte-Carlo construction (include/polar_hip.h) ---------------------------------------------------------------------
 int polar_genie_count_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, uint64_t *d_counts)
 {
-    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_in || !d_counts || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_in || !d_counts || B > kMaxBatch) return POLAR_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_in) % (in_is_f32 ? 4 : 8)) || (reinterpret_cast<uintptr_t>(d_counts) % 8)) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::genie_count(c, d_in, in_is_f32 != 0, sigma, B, reinterpret_cast<unsigned long long *>(d_counts));
@@ -1917,7 +1949,7 @@ int polar_genie_count_device(polar_ctx *c, const void *d_in, int in_is_f32, doub
 int polar_genie_rows_device(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
                             void *d_out, int out_is_f32)
 {
-    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_out || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
+    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_out || B > kMaxBatch || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_out) % (out_is_f32 ? 4 : 8)) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::genie_rows(c, seed, first_frame, sigma, B, d_out, out_is_f32 != 0);
@@ -1927,7 +1959,7 @@ int polar_genie_rows_device(polar_ctx *c, unsigned long long seed, unsigned long
 int polar_construct_batch(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
                           uint64_t *d_counts)
 {
-    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_counts || B > 0x7fffffffull || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
+    if (!c || c->rm_mode != POLAR_RM_NONE || c->cfg.dtype == POLAR_Q8 || !d_counts || B > kMaxBatch || !(sigma > 0) || !std::isfinite(sigma)) return POLAR_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_counts) % 8) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
@@ -1963,7 +1995,7 @@ int polar_construct_order(int N, const uint64_t *counts, const int *base_order, 
 int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long long first_frame, double snr_db,
                           size_t B, void *d_out, int out_is_f32, int out_is_y, uint32_t *d_u_bits)
 {
-    if (!c || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !d_out || B > kMaxBatch) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     if (B == 0) return POLAR_OK;
     const polar_cfg &g = c->cfg;
@@ -2092,7 +2124,7 @@ int polar_q8_quantize_host(const double *in, size_t n, double sigma, double scal
 
 int polar_q8_quantize_device(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, size_t B, int8_t *d_out)
 {
-    if (!c || c->cfg.dtype != POLAR_Q8 || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || c->cfg.dtype != POLAR_Q8 || !d_in || !d_out || B > kMaxBatch) return POLAR_EINVAL;
     const size_t esz = in_is_f32 ? 4 : 8;
     if (reinterpret_cast<uintptr_t>(d_in) % esz) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
@@ -2106,7 +2138,7 @@ int polar_q8_quantize_device(polar_ctx *c, const void *d_in, int in_is_f32, doub
 
 int polar_q8_decode_device(polar_ctx *c, const int8_t *d_q, size_t B, uint32_t *d_uhat_bits, int32_t *d_pm, uint32_t *d_flags)
 {
-    if (!c || c->cfg.dtype != POLAR_Q8 || !d_q || !d_uhat_bits || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || c->cfg.dtype != POLAR_Q8 || !d_q || !d_uhat_bits || B > kMaxBatch) return POLAR_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_q) % 4) return POLAR_EINVAL;   // the kernel loads the rows as dwords
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
@@ -2115,7 +2147,7 @@ int polar_q8_decode_device(polar_ctx *c, const int8_t *d_q, size_t B, uint32_t *
 
 int polar_q8_decode_batch(polar_ctx *c, const int8_t *q, size_t B, int *u_hat, int32_t *pm, unsigned *flags)
 {
-    if (!c || c->cfg.dtype != POLAR_Q8 || !q || !u_hat || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || c->cfg.dtype != POLAR_Q8 || !q || !u_hat || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     const size_t N = (size_t)c->cfg.N, NW = (size_t)c->NW;
@@ -2125,16 +2157,14 @@ int polar_q8_decode_batch(polar_ctx *c, const int8_t *q, size_t B, int *u_hat, i
     if ((rc = ensure(c, c->q8_pm, B * sizeof(int32_t)))) return rc;
     if ((rc = ensure(c, c->flags, B * sizeof(uint32_t)))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->q8_rows.p, q, B * N, hipMemcpyHostToDevice, c->stream));
-    if ((rc = polar_tu::q8_decode(c, (const int8_t *)c->q8_rows.p, B, (uint32_t *)c->bits.p, (int32_t *)c->q8_pm.p, (uint32_t *)c->flags.p))) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
+    if ((rc = polar_tu::q8_decode(c, (const int8_t *)c->q8_rows.p, B, (uint32_t *)c->bits.p, (int32_t *)c->q8_pm.p, (uint32_t *)c->flags.p)))
+        return sync_fail(c, rc);
     std::vector<uint32_t> w(B * NW);
     HIP_TRY(c, hipMemcpyAsync(w.data(), c->bits.p, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (pm) HIP_TRY(c, hipMemcpyAsync(pm, c->q8_pm.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (flags) HIP_TRY(c, hipMemcpyAsync(flags, c->flags.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t f = 0; f < B; ++f) unpack_words(w.data() + f * NW, (int)NW, u_hat + f * N);
+    unpack_rows(w.data(), B, (int)N, u_hat);
     return POLAR_OK;
 }
 
@@ -2274,14 +2304,14 @@ int polar_set_systematic(polar_ctx *c, int on)
 
 int polar_transform_device(polar_ctx *c, const uint32_t *d_in, size_t B, uint32_t *d_out)
 {
-    if (!c || !d_in || !d_out || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !d_in || !d_out || B > kMaxBatch) return POLAR_EINVAL;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::enc_transform(c, d_in, nullptr, false, B, d_out);
 }
 
 int polar_encode_device(polar_ctx *c, const uint32_t *d_payload, size_t B, uint32_t *d_u_bits, uint32_t *d_x_bits)
 {
-    if (!c || !d_payload || (!d_u_bits && !d_x_bits) || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !d_payload || (!d_u_bits && !d_x_bits) || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     int rc;
@@ -2306,7 +2336,7 @@ int polar_encode_device(polar_ctx *c, const uint32_t *d_payload, size_t B, uint3
 
 int polar_payload_device(polar_ctx *c, const uint32_t *d_uhat_bits, size_t B, uint32_t *d_payload, uint32_t *d_crc_ok)
 {
-    if (!c || !d_uhat_bits || !d_payload || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !d_uhat_bits || !d_payload || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     int rc;
@@ -2317,7 +2347,7 @@ int polar_payload_device(polar_ctx *c, const uint32_t *d_uhat_bits, size_t B, ui
 
 int polar_encode_batch(polar_ctx *c, const int *payload, size_t B, int *u, int *x)
 {
-    if (!c || !payload || (!u && !x) || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !payload || (!u && !x) || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     const int K = c->cfg.K, KW = (K + 31) / 32, N = c->cfg.N, NW = c->NW;
@@ -2326,28 +2356,22 @@ int polar_encode_batch(polar_ctx *c, const int *payload, size_t B, int *u, int *
     if ((rc = ensure_nomem(c, c->in, B * KW * 4, kEncScratch))) return rc;
     if ((rc = ensure_nomem(c, c->bits, B * NW * 4, kEncScratch))) return rc;
     if ((rc = ensure_nomem(c, c->enc_io, B * XW * 4, kEncScratch))) return rc;
-    std::vector<uint32_t> pw(B * (size_t)KW, 0u);
-    for (size_t b = 0; b < B; ++b)
-        for (int k = 0; k < K; ++k)
-            if (payload[b * K + k]) pw[b * KW + (k >> 5)] |= 1u << (k & 31);
+    const std::vector<uint32_t> pw = pack_rows(payload, B, K);
     HIP_TRY(c, hipMemcpyAsync(c->in.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, c->stream));
     rc = polar_encode_device(c, (const uint32_t *)c->in.p, B, (uint32_t *)c->bits.p, x ? (uint32_t *)c->enc_io.p : nullptr);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (rc) return sync_fail(c, rc);
     std::vector<uint32_t> hu(u ? B * (size_t)NW : 0), hx(x ? B * (size_t)XW : 0);
     if (u) HIP_TRY(c, hipMemcpyAsync(hu.data(), c->bits.p, hu.size() * 4, hipMemcpyDeviceToHost, c->stream));
     if (x) HIP_TRY(c, hipMemcpyAsync(hx.data(), c->enc_io.p, hx.size() * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (u)
-        for (size_t b = 0; b < B; ++b) unpack_words(hu.data() + b * NW, NW, u + b * (size_t)N);
-    if (x)
-        for (size_t b = 0; b < B; ++b)
-            for (int t = 0; t < W; ++t) x[b * (size_t)W + t] = (int)((hx[b * XW + (t >> 5)] >> (t & 31)) & 1u);
+    if (u) unpack_rows(hu.data(), B, N, u);
+    if (x) unpack_rows(hx.data(), B, W, x);
     return POLAR_OK;
 }
 
 int polar_payload_batch(polar_ctx *c, const int *u_hat, size_t B, int *payload, unsigned *crc_ok)
 {
-    if (!c || !u_hat || !payload || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!c || !u_hat || !payload || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     const int K = c->cfg.K, KW = (K + 31) / 32, N = c->cfg.N, NW = c->NW;
@@ -2355,19 +2379,15 @@ int polar_payload_batch(polar_ctx *c, const int *u_hat, size_t B, int *payload, 
     if ((rc = ensure_nomem(c, c->in, B * KW * 4, kEncScratch))) return rc;
     if ((rc = ensure_nomem(c, c->bits, B * NW * 4, kEncScratch))) return rc;
     if ((rc = ensure_nomem(c, c->flags, B * 4, kEncScratch))) return rc;
-    std::vector<uint32_t> uw(B * (size_t)NW, 0u);
-    for (size_t b = 0; b < B; ++b)
-        for (int j = 0; j < N; ++j)
-            if (u_hat[b * N + j]) uw[b * NW + (j >> 5)] |= 1u << (j & 31);
+    const std::vector<uint32_t> uw = pack_rows(u_hat, B, N);
     HIP_TRY(c, hipMemcpyAsync(c->bits.p, uw.data(), uw.size() * 4, hipMemcpyHostToDevice, c->stream));
     rc = polar_payload_device(c, (const uint32_t *)c->bits.p, B, (uint32_t *)c->in.p, (uint32_t *)c->flags.p);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (rc) return sync_fail(c, rc);
     std::vector<uint32_t> pw(B * (size_t)KW);
     HIP_TRY(c, hipMemcpyAsync(pw.data(), c->in.p, pw.size() * 4, hipMemcpyDeviceToHost, c->stream));
     if (crc_ok) HIP_TRY(c, hipMemcpyAsync(crc_ok, c->flags.p, B * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t b = 0; b < B; ++b)
-        for (int k = 0; k < K; ++k) payload[b * (size_t)K + k] = (int)((pw[b * KW + (k >> 5)] >> (k & 31)) & 1u);
+    unpack_rows(pw.data(), B, K, payload);
     return POLAR_OK;
 }
 
@@ -2434,26 +2454,19 @@ int polar_list_decode(polar_ctx *c, const void *d_in, int in_is_f32, double sigm
     int rc = list_ctx_check(c);
     if (rc) return rc;
     const size_t esz = in_is_f32 ? 4 : 8;
-    if (!d_in || (!d_paths && !d_pm && !d_rem && !d_count && !d_flags) || B > 0x7fffffffull ||
+    if (!d_in || (!d_paths && !d_pm && !d_rem && !d_count && !d_flags) || B > kMaxBatch ||
         (reinterpret_cast<uintptr_t>(d_in) % esz))
         return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     if (c->rm_mode == POLAR_RM_NONE) return list_decode_plain(c, d_in, in_is_f32, sigma, B, d_paths, d_pm, d_rem, d_count, d_flags);
-    // a rate-matched ctx: the rows of E values are recovered first, in chunks, as in decode_device_impl
-    const size_t L = (size_t)c->cfg.L, row = (size_t)c->cfg.N * esz;
-    const size_t CH = chunk_rows(c, B, row);
-    if ((rc = ensure(c, c->rm_rows, CH * row))) return rc;
-    for (size_t off = 0; off < B; off += CH) {
-        const size_t nc = std::min(CH, B - off);
-        if ((rc = polar_tu::rm_recover(c, (const char *)d_in + off * (size_t)c->rm_E * esz, in_is_f32 != 0, sigma, nc, c->rm_rows.p)))
-            return rc;
-        if ((rc = list_decode_plain(c, c->rm_rows.p, in_is_f32, 0.0, nc, d_paths ? d_paths + off * L * (size_t)c->NW : nullptr,
-                                    d_pm ? d_pm + off * L : nullptr, d_rem ? d_rem + off * L : nullptr,
-                                    d_count ? d_count + off : nullptr, d_flags ? d_flags + off : nullptr)))
-            return rc;
-    }
-    return POLAR_OK;
+    // a rate-matched ctx: the rows of E values are recovered first, in the chunks of decode_device_impl
+    const size_t L = (size_t)c->cfg.L;
+    return for_rm_chunks(c, d_in, in_is_f32, sigma, B, [&](const void *rows, size_t off, size_t nc) {
+        return list_decode_plain(c, rows, in_is_f32, 0.0, nc, d_paths ? d_paths + off * L * (size_t)c->NW : nullptr,
+                                 d_pm ? d_pm + off * L : nullptr, d_rem ? d_rem + off * L : nullptr,
+                                 d_count ? d_count + off : nullptr, d_flags ? d_flags + off : nullptr);
+    });
 }
 
 // host-buffer form: the batch goes through the device buffers in one piece
@@ -2462,7 +2475,7 @@ int polar_list_decode_host(polar_ctx *c, const double *llr_in, size_t B, int *pa
 {
     int rc = list_ctx_check(c);
     if (rc) return rc;
-    if (!llr_in || (!paths && !pm && !rem && !count && !flags) || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!llr_in || (!paths && !pm && !rem && !count && !flags) || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     const size_t N = (size_t)c->cfg.N, NW = (size_t)c->NW, L = (size_t)c->cfg.L;
@@ -2478,7 +2491,7 @@ int polar_list_decode_host(polar_ctx *c, const double *llr_in, size_t B, int *pa
     rc = polar_list_decode(c, c->in.p, 0, 0.0, B, paths ? (uint32_t *)c->list_paths.p : nullptr,
                                   pm ? (double *)c->list_pm.p : nullptr, rem ? (uint32_t *)c->list_rem.p : nullptr,
                                   count ? (uint32_t *)c->list_cnt.p : nullptr, flags ? (uint32_t *)c->flags.p : nullptr);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (rc) return sync_fail(c, rc);
     std::vector<uint32_t> w(paths ? B * L * NW : 0);
     if (paths) HIP_TRY(c, hipMemcpyAsync(w.data(), c->list_paths.p, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (pm) HIP_TRY(c, hipMemcpyAsync(pm, c->list_pm.p, B * L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2486,7 +2499,7 @@ int polar_list_decode_host(polar_ctx *c, const double *llr_in, size_t B, int *pa
     if (count) HIP_TRY(c, hipMemcpyAsync(count, c->list_cnt.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (flags) HIP_TRY(c, hipMemcpyAsync(flags, c->flags.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t r = 0; paths && r < B * L; ++r) unpack_words(w.data() + r * NW, (int)NW, paths + r * N);
+    if (paths) unpack_rows(w.data(), B * L, (int)N, paths);
     return POLAR_OK;
 }
 
@@ -2495,7 +2508,7 @@ int polar_list_select(polar_ctx *c, const uint32_t *d_rem, const uint32_t *d_cou
 {
     int rc = list_ctx_check(c);
     if (rc) return rc;
-    if (!d_rem || !d_count || !d_masks || !d_idx || M < 1 || M > 64 || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!d_rem || !d_count || !d_masks || !d_idx || M < 1 || M > 64 || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::list_select(c, d_rem, d_count, B, d_masks, M, d_idx);
@@ -2506,7 +2519,7 @@ int polar_list_gather(polar_ctx *c, const uint32_t *d_paths, const int32_t *d_id
 {
     int rc = list_ctx_check(c);
     if (rc) return rc;
-    if (!d_paths || !d_idx || !d_uhat_bits || idx_stride < 1 || B > 0x7fffffffull) return POLAR_EINVAL;
+    if (!d_paths || !d_idx || !d_uhat_bits || idx_stride < 1 || B > kMaxBatch) return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
     return polar_tu::list_gather(c, d_paths, d_idx, idx_stride, B, d_uhat_bits);
@@ -2518,7 +2531,7 @@ int polar_list_soft(polar_ctx *c, const uint32_t *d_paths, const double *d_pm, c
     int rc = list_ctx_check(c);
     if (rc) return rc;
     if (!d_paths || !d_pm || !d_count || !d_out || (domain != 0 && domain != 1) || !(clamp > 0) || !std::isfinite(clamp) ||
-        B > 0x7fffffffull)
+        B > kMaxBatch)
         return POLAR_EINVAL;
     if (B == 0) return POLAR_OK;
     DeviceGuard guard(c->cfg.device);
@@ -2787,7 +2800,7 @@ int polar_group_stop_rule_batch(polar_group *g, unsigned long long seed, unsigne
     if (!g || !frames_used || !block_errors || !bit_errors) return POLAR_EINVAL;
     const int ngpus = (int)g->ctx.size();
     const size_t total = frames_per_gpu * (size_t)ngpus;
-    if (frames_per_gpu == 0 || total > 0x7fffffffull || min_frames > total) return POLAR_EINVAL;
+    if (frames_per_gpu == 0 || total > kMaxBatch || min_frames > total) return POLAR_EINVAL;
     RcclApi &R = rccl();
     int rc = POLAR_OK;
     for (int i = 0; i < ngpus && !rc; ++i) {

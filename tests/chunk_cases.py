@@ -2,9 +2,10 @@
 tests/test_chunks_host.py and tests/test_gpu_chunks.py).
 
 Seven loops cut a batch into passes of at most 256 MiB of rows (chunk_rows) and offset every input, output and list pointer
-by hand for the second and later passes: q8_decode_rows, the rate-matched loop of decode_device_impl, the later stages of
-cascl_adaptive, pass B of scf_decode, the levels of its dynamic rule, the attempts of bpl_decode (attempt 0 through the
-staging buffers when the first graph is not the identity, and every later attempt) and polar_construct_batch.  At 256 MiB a
+by hand for the second and later passes: q8_decode_rows, the rate-matched loop (for_rm_chunks, which decode_device_impl and
+polar_list_decode share; each offsets its own outputs in the loop's body), the later stages of cascl_adaptive, pass B of
+scf_decode, the levels of its dynamic rule, the attempts of bpl_decode (attempt 0 through the staging buffers when the first
+graph is not the identity, and every later attempt) and polar_construct_batch.  At 256 MiB a
 second pass takes batches no model can follow; polardecoding_amd.testing.chunk_bytes() lowers the cap of one context, and
 the cases here are the rows, contexts and caps at which a few hundred frames of N = 32 .. 128 make three and more passes.
 

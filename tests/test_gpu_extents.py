@@ -641,6 +641,45 @@ def test_decode_batch_across_the_chunks_of_the_host_pipeline(B, oracle):
         dec.close()
 
 
+def test_scf_sets_batch_across_the_chunks_of_the_host_pipeline(oracle):
+    """polar_scf_decode_sets_batch at 16385 frames of N = 32 (two host chunks, the second of one frame): `sets` is the one
+    output of the host pipeline whose rows are wider than a word (3 positions per frame), so its slice per chunk and its
+    copy-back are held to the device form on the same rows here.  Dynamic SC-Flip (4, 4, 4) on random valid codewords at
+    Eb/N0 = 3 dB, where a minority of the frames reports a set and the case takes well under a second; the last frame, alone
+    in the second chunk, is one whose reported set is not empty."""
+    N, K, B = 32, 16, HOST_CHUNK + 1
+    sigma = 10.0 ** (-3.0 / 20.0)
+    case = X.Case("host dscf N=32", "polar_scf_decode_sets_device",
+                  X.ctx("DSCF", N, K, budgets=(4, 4, 4), c=1.5, tau=5.0, crc_taps=X.CRC6), "", 64, (B,),
+                  BY_NAME["dscf (4,4,4) N=128"].outputs, "", {})
+    dec = X.make_ctx(case.ctx)
+    try:
+        io = dec.info_order.tolist()
+        code = oracle.Code(N, K, X.CRC6, Q=[j for j in range(N) if j not in set(io)] + io)
+        assert np.array_equal(code.info_order, dec.info_order)
+        basis, _ = oracle.Sim(1533).frames(code, sigma, 32)   # valid words u; the code and its CRC are linear, so are their sums
+        rng = np.random.default_rng(1533)
+        u = ((rng.integers(0, 2, (B, 32)) @ np.asarray(basis, dtype=np.int64)) & 1).astype(np.uint8)
+        x = CC.f32_exact(2.0 * ((1.0 - 2.0 * EM.transform(u)) + sigma * rng.standard_normal((B, N))) / sigma / sigma)
+        sets = run(case, dec, B, dict(t={"in": _cuda(x)}))["d_sets"].reshape(B, 3)
+        assert (sets[:, 0] >= 0).any(), "no frame flipped"
+        j = int(np.flatnonzero(sets[:, 0] >= 0)[0])
+        x[[j, B - 1]] = x[[B - 1, j]]   # a frame that flips goes last: the only frame of the second chunk
+        dev = run(case, dec, B, dict(t={"in": _cuda(x)}))
+        sets = dev["d_sets"].reshape(B, 3)
+        assert sets[B - 1, 0] >= 0 and (sets[:HOST_CHUNK, 0] >= 0).any() and (sets[:HOST_CHUNK, 0] < 0).any()
+        snap = X.snapshot(x)
+        arena, views = _host_views(B, [("u_hat", "int32", N), ("flags", "uint32", 1), ("attempts", "uint32", 1), ("sets", "int32", 3)])
+        rc = _host_call("polar_scf_decode_sets_batch", dec, x, (), B, list(views.values()))
+        assert rc == 0 and arena.check() == [] and X.unchanged(x, snap)
+        bad = np.flatnonzero((views["u_hat"].reshape(B, N) != _bits(dev["d_uhat_bits"], B, N)).any(axis=1))
+        assert bad.size == 0, f"u_hat differs from frame {bad[0]} on ({bad.size} frames)"
+        for n, dname in (("flags", "d_flags"), ("attempts", "d_attempts"), ("sets", "d_sets")):
+            assert views[n].dtype == dev[dname].dtype and np.array_equal(views[n], dev[dname]), n
+    finally:
+        dec.close()
+
+
 @pytest.mark.parametrize("B", X.HOST_BATCHES)
 def test_encoder_side_host_forms(B, oracle):
     """polar_encode_batch (u only, x only, both) and polar_payload_batch at N = 32 against the device forms"""
