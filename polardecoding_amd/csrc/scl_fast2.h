@@ -14,6 +14,7 @@
 // the leaf schedule (frozen pattern) is the same for both codewords, so control flow stays uniform.
 // Arithmetic is the same as k_scl_fast / the reference, operation for operation.
 #pragma once
+#include "fast2_lds.h"
 #include "octet_bits.h"
 #include "scl_fast.h"
 
@@ -42,14 +43,19 @@ struct Fast2Cfg {
     static constexpr size_t off_stair = off_kth + 256 * 8;  // room for a Stair<R> (chk_idx): not used
     static constexpr size_t shared_bytes = off_stair + ((Stair<R>::bytes + 15) / 16) * 16;
     // per-wave LDS
-    static constexpr size_t off_bl = 0;                        // saved partial sums [2][8][NW]
-    static constexpr size_t off_cw = off_bl + 4 * 2 * 8 * NW;  // working partial sums [2][8][NW]
-    static constexpr size_t off_cd = off_cw + 4 * 2 * 8 * NW;  // candidates [2][16]
+    // partial-sum rows: row slot of codeword c at word cw_base(c) + row(slot) (fast2_lds.h: a 32-lane group's rows in
+    // banks of their own)
+    static constexpr size_t off_bl = 0;                                    // saved partial sums
+    static constexpr size_t off_cw = off_bl + 4 * fast2_lds::ROWS_WORDS;   // working partial sums
+    static constexpr size_t off_cd = off_cw + 4 * fast2_lds::ROWS_WORDS;   // candidates [2][16]
     static constexpr size_t off_ky = off_cd + sizeof(R) * 32;  // keys [2][16]
     static constexpr size_t off_sg = off_ky + 128;             // top-level staging [2][256]
     static constexpr size_t per_wave = off_sg + sizeof(R) * 512;
     static constexpr size_t total = shared_bytes + WAVES * per_wave;
+    static_assert(off_cw % 16 == 0 && off_cd % 16 == 0 && per_wave % 16 == 0 && shared_bytes % 16 == 0, "LDS regions are 16-byte aligned");
 };
+// LDS never becomes what limits occupancy: three workgroups per CU in f64, four in f32, of 160 KiB
+static_assert(3 * Fast2Cfg<double>::total <= 163840 && 4 * Fast2Cfg<float>::total <= 163840, "the pair kernel's LDS limits its occupancy");
 
 template <int QP>
 __device__ __forceinline__ double quadp(double x) { return quad_lanes<QP>(x); }
@@ -129,6 +135,8 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     };
     static __device__ __forceinline__ R ld_sc(SPtr q) { return ld_buf(q.d->rs_scr, q.off, R(0), 1); }
 
+    // word offset of a slot's row in blw / curw: every reader and writer of the rows asks here, where it uses the row
+    static __device__ __forceinline__ int row(int slot) { return fast2_lds::row(slot); }
     __device__ __forceinline__ int pa(int t) const { return (ptr >> (3 * (t - 4))) & 7; }
     __device__ __forceinline__ void set_pa(int t, int v) { ptr = (ptr & ~(7u << (3 * (t - 4)))) | ((uint32_t)v << (3 * (t - 4))); }
     __device__ __forceinline__ int pb(int t) const { return (ptr >> (3 * (NFA + t - 5))) & 7; }
@@ -173,7 +181,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         constexpr int RO = (1 << T) / 4;
         const int sl = pa(T + 1) * 8 + gl;
         uint32_t w;
-        if constexpr (T == 5) w = blw[pb(5) * NW + 1] >> pos;   // level 5: word 1, bit e = pos + 4r
+        if constexpr (T == 5) w = blw[row(pb(5)) + 1] >> pos;   // level 5: word 1, bit e = pos + 4r
         else w = bl0 >> (16 + pos);                              // level 4: bits 16 + e
 #pragma unroll
         for (int r = 0; r < RO; ++r) {
@@ -220,8 +228,8 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     __device__ __forceinline__ void from_top(bool right, bool gstep)
     {
         vm_drain();
-        const uint32_t *bt = blw + pb(TOP) * NW + 16;  // beta_9: words 16..31
-        const uint32_t *bh = blw + pb(HI) * NW + 8;    // beta_8: words 8..15
+        const uint32_t *bt = blw + row(pb(TOP)) + 16;  // beta_9: words 16..31
+        const uint32_t *bh = blw + row(pb(HI)) + 8;    // beta_8: words 8..15
         const SPtr o8 = l8(p), o7 = l7(p);
         const int w32 = (int)fresh((unsigned)(p * 4 + pos));   // lane index inside the codeword (recomputed here: the staged
                                                                // elements' offsets are not worth a register each across the frame loop)
@@ -279,7 +287,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     {
         vm_drain();
         const SPtr s8 = l8(pa(8));
-        const uint32_t *b7 = blw + pb(7) * NW + 4;  // beta_7: words 4..7
+        const uint32_t *b7 = blw + row(pb(7)) + 4;  // beta_7: words 4..7
         const SPtr o7 = l7(p);
         constexpr int CP = sizeof(R) == 8 ? 2 : 4;   // passes per chunk (4 loads each); f64: 8 in flight is the measured optimum
         for (int q = 0; q < 16 / CP; ++q) {
@@ -310,7 +318,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     {
         vm_drain();
         const SPtr s7 = l7(pa(7)) + pos;
-        const uint32_t *b6 = blw + pb(6) * NW + 2;  // beta_6: words 2, 3
+        const uint32_t *b6 = blw + row(pb(6)) + 2;  // beta_6: words 2, 3
         const uint32_t w0 = b6[0] >> pos, w1 = b6[1] >> pos;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -381,26 +389,26 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     {
         // the slot's row offset is recomputed here (one instruction) rather than kept across the frame loop: as a
         // loop invariant it was spilled and re-loaded from the stack at every carry step
-        const int row = (int)fresh((unsigned)(p * NW));
+        const int own = (int)fresh((unsigned)row(p));
         lds_fence();
-        if (pos == 0) curw[row] = cur;
+        if (pos == 0) curw[own] = cur;
         lds_fence();
         int t = 5;
         while (t < 10 && ((j >> t) & 1)) {
             const int nw = 1 << (t - 5);
             const int sb = pb(t);
             for (int w = pos; w < nw; w += 4) {
-                const uint32_t cc = curw[row + w];
-                const uint32_t l = blw[sb * NW + nw + w];
-                curw[row + w] = l ^ cc;
-                curw[row + w + nw] = cc;
+                const uint32_t cc = curw[own + w];
+                const uint32_t l = blw[row(sb) + nw + w];
+                curw[own + w] = l ^ cc;
+                curw[own + w + nw] = cc;
             }
             lds_fence();
             ++t;
         }
         if (t < 10) {
             const int nw = 1 << (t - 5);
-            for (int w = pos; w < nw; w += 4) blw[row + nw + w] = curw[row + w];
+            for (int w = pos; w < nw; w += 4) blw[own + nw + w] = curw[own + w];
             set_pb(t, p);
             lds_fence();
         }
@@ -675,7 +683,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         const uint32_t wv0 = fill_tail(frz[3] >> 30, stg[126], xl, yl);
         uint32_t wv1 = 0;
         lds_fence();
-        blw[p * NW + 4 + pos] = wv0;   // beta_7
+        blw[row(p) + 4 + pos] = wv0;   // beta_7
         lds_fence();
 #pragma unroll 1
         for (int S = 128; S < E; S += 64) {
@@ -751,11 +759,11 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             lds_fence();
             if (S == 128) {
                 wv1 = wv;
-                if (pos < 2) blw[p * NW + 2 + pos] = wv;   // beta_6
+                if (pos < 2) blw[row(p) + 2 + pos] = wv;   // beta_6
             } else {          // beta_8 = (beta_7 ^ b, b), b = the partial sums of leaves 128 .. 255 = (wv1 ^ wv, wv)
                 const uint32_t b = pos < 2 ? wv1 ^ wv : wv;
-                blw[p * NW + 8 + pos] = wv0 ^ b;
-                blw[p * NW + 12 + pos] = b;
+                blw[row(p) + 8 + pos] = wv0 ^ b;
+                blw[row(p) + 12 + pos] = b;
             }
             lds_fence();
         }
@@ -923,8 +931,8 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
     s.gl = s.lane & 7;
     s.lut.bind(smem + C::off_lut);
     s.kth = kth;
-    s.blw = reinterpret_cast<uint32_t *>(base + C::off_bl) + s.c * 8 * NW;
-    s.curw = reinterpret_cast<uint32_t *>(base + C::off_cw) + s.c * 8 * NW;
+    s.blw = reinterpret_cast<uint32_t *>(base + C::off_bl) + fast2_lds::cw_base(1) * s.c;
+    s.curw = reinterpret_cast<uint32_t *>(base + C::off_cw) + fast2_lds::cw_base(1) * s.c;
     s.cand = reinterpret_cast<R *>(base + C::off_cd) + s.c * 16;
     s.keys = reinterpret_cast<uint32_t *>(base + C::off_ky) + s.c * 16;
     s.stg = reinterpret_cast<R *>(base + C::off_sg) + s.c * 256;
@@ -963,7 +971,8 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
 #pragma unroll 2
             for (int e = w; e < N / 2; e += 32) t[e] = s.chk(s.chv(e), s.chv(e + N / 2));
         }
-        for (int w = lane; w < 2 * 8 * NW; w += 64) (s.blw - c * 8 * NW)[w] = 0;
+#pragma unroll
+        for (int j = 0; j < NW / 4; ++j) s.blw[D::row(p) + pos + 4 * j] = 0;   // the slot's own row, four lanes to a row
         lds_fence();
 
         s.PM = R(0);
@@ -1011,7 +1020,7 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
             lds_fence();
             uint32_t x[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = s.curw[p * NW + pos + 4 * j];
+            for (int j = 0; j < 8; ++j) x[j] = s.curw[D::row(p) + pos + 4 * j];
             typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
             const u4_t *mk = reinterpret_cast<const u4_t *>(msk + 8 * pos);
             const int rows = (P.crc_r + 3) & ~3;
@@ -1050,7 +1059,7 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         lds_fence();
         {
             const int w = p * 4 + pos;
-            uint32_t x = s.curw[best * NW + w];
+            uint32_t x = s.curw[D::row(best) + w];
             x ^= (x >> 1) & 0x55555555u;
             x ^= (x >> 2) & 0x33333333u;
             x ^= (x >> 4) & 0x0F0F0F0Fu;
