@@ -16,6 +16,7 @@
 // twice per iteration for N = 1024 instead of 18 times, and the waves of a codeword drift apart enough to
 // overlap one wave's table reads with another's arithmetic.
 #pragma once
+#include "polar_bits.h"
 #include "polar_math.h"
 #include "polar_lut.h"
 #include "polar_params.h"
@@ -42,24 +43,14 @@ __device__ __forceinline__ void bp_sync(int stage_a, int stage_b)
 }
 
 // ---- stop rule POLAR_BP_STOP_G (include/polar_hip.h): after a round trip, u_hat F^{(x)n} == x_hat? ----------------------
-// x = u F^{(x)n} in natural order (gen_kernel.h, SCL_1024.c:242-250): x[j] ^= x[j + s] for every j with bit s clear, s = 1,
-// 2, .. N/2.  In a 32-bit word of decisions (bit j & 31 of word j >> 5) the strides below 32 are shifts under a mask.
-__device__ __forceinline__ uint32_t bp_encode_word(uint32_t v)
-{
-    v ^= (v >> 1) & 0x55555555u;
-    v ^= (v >> 2) & 0x33333333u;
-    v ^= (v >> 4) & 0x0F0F0F0Fu;
-    v ^= (v >> 8) & 0x00FF00FFu;
-    v ^= (v >> 16) & 0x0000FFFFu;
-    return v;
-}
+// x = u F^{(x)n} in natural order (gen_kernel.h): the strides below 32 are polar_word_transform (polar_bits.h).
 // One wavefront: the N/32 <= 128 words of u_hat and x_hat (LDS) -> does u_hat F == x_hat hold?  Wave-uniform result.  Lane l
 // holds words l and l + 64; strides of 32..1024 elements are lane exchanges, 2048 is the lane's own pair.
 __device__ __forceinline__ bool bp_g_holds(const uint32_t *u, const uint32_t *x, int NW)
 {
     const int lane = threadIdx.x & 63;
-    uint32_t v0 = lane < NW ? bp_encode_word(u[lane]) : 0u;
-    uint32_t v1 = lane + 64 < NW ? bp_encode_word(u[lane + 64]) : 0u;
+    uint32_t v0 = lane < NW ? polar_word_transform(u[lane]) : 0u;
+    uint32_t v1 = lane + 64 < NW ? polar_word_transform(u[lane + 64]) : 0u;
     for (int sw = 1; sw < NW && sw < 64; sw <<= 1) {
         const uint32_t o0 = (uint32_t)__shfl_xor((int)v0, sw), o1 = (uint32_t)__shfl_xor((int)v1, sw);
         if (!(lane & sw)) {
@@ -103,9 +94,7 @@ __global__ __launch_bounds__(512) void k_bp(BpParams P)
     for (int frame = blockIdx.x; frame < P.B; frame = next_job_block(P.queue, frame, (int)gridDim.x, P.B, &job_slot)) {
         const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
         for (int i = tid; i < N; i += nt) {
-            double v = (double)src[i];
-            if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-            ch[i] = (R)v;  // BP_1024.c:381-382
+            ch[i] = (R)channel_llr<IN>(src, i, P.sigma);  // BP_1024.c:381-382
         }
         for (int i = tid; i < (n - 1) * N; i += nt) {
             lm[i] = R(0);  // BP_1024.c:378-380
@@ -245,9 +234,7 @@ __global__ __launch_bounds__(256) void k_bp_readout(BpReadoutParams P)
         }
         __syncthreads();
         for (int j = tid; j < N; j += nt) {
-            double v = (double)src[j];
-            if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-            LM(n, j) = (R)v;                                                        // :382-383
+            LM(n, j) = (R)channel_llr<IN>(src, j, P.sigma);                         // :382-383
             RM(0, j) = ((P.frozen[j >> 5] >> (j & 31)) & 1) ? R(999) : R(0);        // :388-393
         }
         for (int i = tid; i < NW; i += nt) obits[i] = 0;
@@ -352,9 +339,7 @@ __global__ __launch_bounds__(512) void k_bp_global(BpParams P, R *scratch)
         }
         __syncthreads();
         for (int j = tid; j < N; j += nt) {
-            double v = (double)src[j];
-            if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-            LM(n, j) = (R)v;
+            LM(n, j) = (R)channel_llr<IN>(src, j, P.sigma);
             RM(0, j) = ((P.frozen[j >> 5] >> (j & 31)) & 1) ? R(999) : R(0);
         }
         for (int i = tid; i < NW; i += nt) obits[i] = 0;

@@ -213,9 +213,7 @@ __global__ __launch_bounds__(256, (BpR4Cfg<R>::MIN_BLOCKS)) void k_bp_r4(BpParam
         const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {   // group-4 elements t + 256 k: coalesced
-            double v = (double)src[s.t + 256 * k];
-            if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-            s.ch[k] = (R)v;   // BP_1024.c:381-382
+            s.ch[k] = (R)channel_llr<IN>(src, s.t + 256 * k, P.sigma);   // BP_1024.c:381-382
         }
 #pragma unroll
         for (int g = 0; g < 5; ++g)

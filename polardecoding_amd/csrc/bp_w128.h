@@ -156,9 +156,7 @@ __global__ __launch_bounds__(256, (BpW128Cfg<R>::MIN_WAVES_PER_SIMD)) void k_bp_
         const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * C::N;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            double v = (double)src[lane + 64 * e];
-            if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-            s.ch[e] = (R)v;                      // BP_128.c:343-344
+            s.ch[e] = (R)channel_llr<IN>(src, lane + 64 * e, P.sigma);   // BP_128.c:343-344
         }
 #pragma unroll
         for (int i = 0; i < 6; ++i)

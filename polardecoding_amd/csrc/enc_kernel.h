@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "polar_bits.h"
+
 namespace polar {
 
 constexpr int ENC_THREADS = 256;
@@ -36,13 +38,7 @@ __device__ __forceinline__ void enc_xform(uint32_t (&x)[WPL], int NW, int g)
 {
 #pragma unroll
     for (int k = 0; k < WPL; ++k) {
-        uint32_t v = x[k];
-        v ^= (v >> 1) & 0x55555555u;    // element j with bit s of j clear takes element j + 2^s
-        v ^= (v >> 2) & 0x33333333u;
-        v ^= (v >> 4) & 0x0F0F0F0Fu;
-        v ^= (v >> 8) & 0x00FF00FFu;
-        v ^= (v >> 16) & 0x0000FFFFu;
-        x[k] = v;
+        x[k] = polar_word_transform(x[k]);   // the strides below 32
     }
     const int G = NW < 64 ? NW : 64;
     for (int o = 1; o < G; o <<= 1) {

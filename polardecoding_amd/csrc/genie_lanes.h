@@ -122,9 +122,7 @@ __global__ __launch_bounds__(256, (GenieCfg<R>::MIN_WAVES_PER_SIMD)) void k_geni
             }
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
-                double v = have ? (double)raw[u] : 0.0;
-                if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-                dst[u] = (R)v;
+                dst[u] = (R)channel_llr(have ? (double)raw[u] : 0.0, P.sigma);
             }
         };
         sync();

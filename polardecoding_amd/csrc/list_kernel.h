@@ -107,15 +107,7 @@ __global__ __launch_bounds__(64) void k_list_soft(ListSoftParams P)
         }
         __syncthreads();
         if (P.domain == 1) {
-            for (int i = lane; i < nc * NW; i += 64) {
-                uint32_t x = rows[i];
-                x ^= (x >> 1) & 0x55555555u;
-                x ^= (x >> 2) & 0x33333333u;
-                x ^= (x >> 4) & 0x0F0F0F0Fu;
-                x ^= (x >> 8) & 0x00FF00FFu;
-                x ^= (x >> 16) & 0x0000FFFFu;
-                rows[i] = x;
-            }
+            for (int i = lane; i < nc * NW; i += 64) rows[i] = polar_word_transform(rows[i]);
             __syncthreads();
             for (int s = 5; s < P.n; ++s) {
                 const int hw = 1 << (s - 5);

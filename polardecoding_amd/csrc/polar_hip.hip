@@ -17,6 +17,7 @@
 
 #include "count_kernel.h"
 #include "gen_kernel.h"
+#include "polar_bits.h"
 #include "scf_params.h"
 #include "scan_params.h"
 
@@ -2174,9 +2175,7 @@ namespace {
 // x F^{(x)n} on one packed host row, the stages of enc_kernel.h
 void host_transform(uint32_t *w, int NW)
 {
-    static const uint32_t m[5] = {0x55555555u, 0x33333333u, 0x0F0F0F0Fu, 0x00FF00FFu, 0x0000FFFFu};
-    for (int i = 0; i < NW; ++i)
-        for (int s = 0; s < 5; ++s) w[i] ^= (w[i] >> (1 << s)) & m[s];
+    for (int i = 0; i < NW; ++i) w[i] = polar::polar_word_transform(w[i]);
     for (int o = 1; o < NW; o <<= 1)
         for (int i = 0; i < NW; ++i)
             if (!(i & o)) w[i] ^= w[i + o];

@@ -82,4 +82,23 @@ __device__ __forceinline__ R g_bit(R cU, R cL, uint32_t w, int sh)
 // channel LLR from an observation: 2*y/std/std, that order (SCL_1024.c:576), always in double
 __device__ __forceinline__ double llr_from_y(double y, double sigma) { return 2 * y / sigma / sigma; }
 
+// an input value as a channel LLR (SCL_1024.c:574-578): the value itself, or the LLR of an observation when the caller gave
+// a noise level (sigma > 0).  The caller casts to its working type.  The second form takes element i of an input row.
+__device__ __forceinline__ double channel_llr(double v, double sigma)
+{
+    if (sigma > 0) v = llr_from_y(v, sigma);
+    return v;
+}
+template <typename IN>
+__device__ __forceinline__ double channel_llr(const IN *src, int i, double sigma)
+{
+    return channel_llr((double)src[i], sigma);
+}
+
+// Loads of scratch rows that another step wrote with plain stores (write-through to L2): a relaxed agent-scope atomic load
+// (global_load ... sc1) goes round the per-CU L1, so a line cached from an earlier frame can never be returned.
+__device__ __forceinline__ double ld_bypass(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float ld_bypass(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t ld_bypass(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 }  // namespace polar

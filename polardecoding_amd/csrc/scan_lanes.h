@@ -200,9 +200,7 @@ __global__ __launch_bounds__(256) void k_scan_lanes(ScanParams P)
                 }
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
-                    double v = have ? (double)raw[u] : 0.0;
-                    if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-                    *at((size_t)N + e0 + u) = (R)v;
+                    *at((size_t)N + e0 + u) = (R)channel_llr(have ? (double)raw[u] : 0.0, P.sigma);
                 }
             }
         }

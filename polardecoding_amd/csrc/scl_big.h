@@ -7,8 +7,8 @@
 //   LLR level t <= TL (the 2^(TL+1) - 1 lowest values of a path): LDS, lowA[L][2^(TL+1)], level t at offset 2^t.
 //   LLR level t > TL: per-wave slice of a global scratch buffer, hiA[L][N]; channel LLRs chg[N].
 //     Written with plain stores (write-through to L2), read back with sc1 loads, vmcnt drained in between.
-//   Partial sums, bit-packed (level t, element e <-> bit 2^t + e): bits < 32 in a register, levels 5..TB in
-//     LDS, levels > TB in the scratch slice.
+//   Partial sums, bit-packed (polar_bits.h): bits < 32 in a register, levels 5..TB in LDS, levels > TB in
+//     the scratch slice.
 //   The decoder is a chain of dependent LDS / L2 round trips, so throughput follows the number of resident
 //   wavefronts, which the LDS footprint sets: TL and TB trade a few more L2 round trips per frame for more
 //   codewords per CU (profiles/README.md).
@@ -23,6 +23,11 @@
 //   Pruning: candidate (p, b) is owned by lane p*S + b.  Every owner counts #{m : c_m <= c_own} over the 2L
 //   keys broadcast from LDS; "count <= L" is the reference's strict "< median" (SCL_1024.c:610-632).  The
 //   m-th both-survivor is paired with the m-th dead slot through a rank table in LDS (:636-661).
+//
+//   Against scl_wave_ops.h: the lane layout and the pointer tables are the same; the word-0 steps and the
+//   in-word transform are polar_bits.h's.  The partial-sum rows stay here: the saved row is read through ptrB
+//   (bs, not p), a level's words are in LDS (stride WL) or in the scratch slice depending on TB, and the wave
+//   orders its own accesses with wave_sync(), not with a workgroup barrier.  The epilogue reads the scratch.
 #pragma once
 #include "polar_math.h"
 #include "polar_lut.h"
@@ -39,8 +44,6 @@ __device__ __forceinline__ R chk_wide(R a, R b, const Lut<R> &L)
     if constexpr (sizeof(R) == 8) return chk_lut1<R>(a, b, L);
     else return chk_lut<R>(a, b, L);
 }
-
-__device__ __forceinline__ uint32_t ld_bypass(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 template <typename R, int LOGL, int TLv, int TBv, int RLv = 0>
 struct BigCfg {
@@ -147,11 +150,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? 3 : 4) : 1) void k_scl_big(Sc
     for (int frame = slot; frame < P.B; frame = next_job_wave(P.queue, frame, nslots, P.B)) {
         {   // channel LLRs (SCL_1024.c:574-578)
             const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
-            for (int i = lane; i < N; i += 64) {
-                double v = (double)src[i];
-                if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-                chg[i] = (R)v;
-            }
+            for (int i = lane; i < N; i += 64) chg[i] = (R)channel_llr<IN>(src, i, P.sigma);
         }
         wave_sync();
 
@@ -706,11 +705,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? 3 : 4) : 1) void k_scl_big(Sc
             int t = 0;
             while (t < n && ((j >> t) & 1)) {
                 if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    const uint32_t l = (bl0 >> h) & mask;
-                    const uint32_t c = cur0 & mask;
-                    cur0 = (l ^ c) | (c << h);
+                    cur0 = ps_fold0(bl0, cur0, t);
                 } else {
                     const int nw = 1 << (t - 5);
                     if (t == 5) {
@@ -742,9 +737,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? 3 : 4) : 1) void k_scl_big(Sc
             }
             if (t < n) {
                 if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    bl0 = (bl0 & ~(mask << h)) | ((cur0 & mask) << h);
+                    bl0 = ps_save0(bl0, cur0, t);
                 } else {
                     const int nw = 1 << (t - 5);
                     if (p < act) {
@@ -780,15 +773,7 @@ __global__ __launch_bounds__(256, RLv == 1 ? (CH ? 3 : 4) : 1) void k_scl_big(Sc
         if (any) fl |= 0x2u;
         // x_hat of the chosen path: root partial sums (scratch slice); u_hat = x_hat * F^{(x)n}, in place
         uint32_t *xw = gcur + (size_t)best * NW;
-        for (int w = lane; w < NW; w += 64) {
-            uint32_t x = ld_bypass(xw + w);
-            x ^= (x >> 1) & 0x55555555u;
-            x ^= (x >> 2) & 0x33333333u;
-            x ^= (x >> 4) & 0x0F0F0F0Fu;
-            x ^= (x >> 8) & 0x00FF00FFu;
-            x ^= (x >> 16) & 0x0000FFFFu;
-            xw[w] = x;
-        }
+        for (int w = lane; w < NW; w += 64) xw[w] = polar_word_transform(ld_bypass(xw + w));
         wave_sync();
         for (int s = 5; s < n; ++s) {
             const int hw = 1 << (s - 5);

@@ -28,6 +28,7 @@
 #pragma once
 #include "polar_math.h"
 #include "polar_lut.h"
+#include "polar_bits.h"
 #include "scl_generic.h"
 
 namespace polar {
@@ -132,10 +133,7 @@ struct FastCfg {
     static constexpr size_t total = shared_bytes + WAVES * per_wave;
 };
 
-// scratch traffic: plain stores (write-through to L2), loads that bypass the per-CU L1 (relaxed agent-scope
-// atomic load = global_load ... sc1) so that a line cached from an earlier frame can never be returned
-__device__ __forceinline__ double ld_sc(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_sc(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// scratch traffic: plain stores (write-through to L2), loads that bypass the per-CU L1 (ld_bypass, polar_math.h)
 __device__ __forceinline__ void vm_drain() { __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // 32-bit ordering key of a non-negative metric: f32 bits are exact, the high word of an f64 is exact
@@ -171,12 +169,7 @@ struct FastDec {
     double sigma;
 
     // channel LLR straight from the input (SCL_1024.c:574-578)
-    __device__ __forceinline__ R chv(int e) const
-    {
-        double v = (double)src[e];
-        if (sigma > 0) v = llr_from_y(v, sigma);
-        return (R)v;
-    }
+    __device__ __forceinline__ R chv(int e) const { return (R)channel_llr<IN>(src, e, sigma); }
 
     __device__ __forceinline__ int pa(int t) const { return (ptr >> (3 * (t - 4))) & 7; }
     __device__ __forceinline__ void set_pa(int t, int v) { ptr = (ptr & ~(7u << (3 * (t - 4)))) | ((uint32_t)v << (3 * (t - 4))); }
@@ -274,7 +267,7 @@ struct FastDec {
         vm_drain();
         const R *q = l6s(p) + pos;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) A[8 + r] = ld_sc(q + 8 * r);
+        for (int r = 0; r < 8; ++r) A[8 + r] = ld_bypass(q + 8 * r);
         set_pa(6, p);
     }
     // Octet heads with d >= 8 (j = 0, 256, 512, 768): level 8 from the top level (f or g), then f to 7 and 6.
@@ -301,8 +294,8 @@ struct FastDec {
                     x = g_bit<R>(chv(e), chv(e + 512), w0, sh);
                     y = g_bit<R>(chv(e + 256), chv(e + 768), w1, sh);
                 } else {
-                    x = ld_sc(t + e);
-                    y = ld_sc(t + e + 256);
+                    x = ld_bypass(t + e);
+                    y = ld_bypass(t + e + 256);
                 }
                 if (gstep) v8[k] = g_bit<R>(x, y, bh[2 * k + wq] >> pos, sh);
                 else v8[k] = chk(x, y);
@@ -328,7 +321,7 @@ struct FastDec {
             const int e0 = pos + 8 * rr;
             const int sh = 8 * (rr & 3);
             const int wq = rr >> 2;
-            const R a0 = ld_sc(s8 + e0), a1_ = ld_sc(s8 + e0 + 64), a2_ = ld_sc(s8 + e0 + 128), a3_ = ld_sc(s8 + e0 + 192);
+            const R a0 = ld_bypass(s8 + e0), a1_ = ld_bypass(s8 + e0 + 64), a2_ = ld_bypass(s8 + e0 + 128), a3_ = ld_bypass(s8 + e0 + 192);
             const R v70 = g_bit<R>(a0, a2_, b7[wq] >> pos, sh);
             const R v71 = g_bit<R>(a1_, a3_, b7[2 + wq] >> pos, sh);
             o7[e0] = v70;
@@ -347,7 +340,7 @@ struct FastDec {
         const uint32_t w0 = b6[0] >> pos, w1 = b6[1] >> pos;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const R x = ld_sc(s7 + 8 * r), y = ld_sc(s7 + 8 * r + 64);
+            const R x = ld_bypass(s7 + 8 * r), y = ld_bypass(s7 + 8 * r + 64);
             A[8 + r] = g_bit<R>(x, y, r < 4 ? w0 : w1, 8 * (r & 3));
         }
         set_pa(6, p);
@@ -420,16 +413,9 @@ struct FastDec {
         uint32_t cur = bit;
         const int z = __builtin_ctz(~(unsigned)j);  // trailing ones of j (uniform), >= 3 here
         const int zl = z < 5 ? z : 5;
-        for (int t = 0; t < zl; ++t) {
-            const int h = 1 << t;
-            const uint32_t mask = (1u << h) - 1u;
-            const uint32_t l = (bl0 >> h) & mask;
-            cur = (l ^ (cur & mask)) | ((cur & mask) << h);
-        }
+        for (int t = 0; t < zl; ++t) cur = ps_fold0(bl0, cur, t);
         if (z < 5) {
-            const int h = 1 << z;
-            const uint32_t mask = (1u << h) - 1u;
-            bl0 = (bl0 & ~(mask << h)) | ((cur & mask) << h);
+            bl0 = ps_save0(bl0, cur, z);
             return;
         }
         // rare path (every 32 leaves): levels >= 5 are words in LDS
@@ -763,11 +749,7 @@ __global__ __launch_bounds__(256, (FastCfg<R, NLOG>::MIN_WAVES_PER_SIMD)) void k
         uint32_t *xw = s.curw + (size_t)best * NW;
         {
             uint32_t x = xw[lane & (NW - 1)];
-            x ^= (x >> 1) & 0x55555555u;
-            x ^= (x >> 2) & 0x33333333u;
-            x ^= (x >> 4) & 0x0F0F0F0Fu;
-            x ^= (x >> 8) & 0x00FF00FFu;
-            x ^= (x >> 16) & 0x0000FFFFu;
+            x = polar_word_transform(x);
 #pragma unroll
             for (int hw = 1; hw < NW; hw <<= 1) {
                 const uint32_t o = __shfl_down(x, hw);

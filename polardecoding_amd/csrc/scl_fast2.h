@@ -1060,11 +1060,7 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         {
             const int w = p * 4 + pos;
             uint32_t x = s.curw[D::row(best) + w];
-            x ^= (x >> 1) & 0x55555555u;
-            x ^= (x >> 2) & 0x33333333u;
-            x ^= (x >> 4) & 0x0F0F0F0Fu;
-            x ^= (x >> 8) & 0x00FF00FFu;
-            x ^= (x >> 16) & 0x0000FFFFu;
+            x = polar_word_transform(x);
 #pragma unroll
             for (int hw = 1; hw < NW; hw <<= 1) {
                 const int wo = w ^ hw;  // partner word; the lower one of the pair absorbs the upper one

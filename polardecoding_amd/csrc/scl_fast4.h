@@ -88,12 +88,7 @@ struct Fast4Dec {
         else return chk_lut<R>(a, b, lut);
     }
     __device__ __forceinline__ R chks(R a, R b) const { return chk_lut1<R>(a, b, lut); }
-    __device__ __forceinline__ R chv(int e) const
-    {
-        double v = (double)src[e];
-        if (sigma > 0) v = llr_from_y(v, sigma);
-        return (R)v;
-    }
+    __device__ __forceinline__ R chv(int e) const { return (R)channel_llr<IN>(src, e, sigma); }
     static __device__ __forceinline__ unsigned fresh(unsigned off)
     {
         __asm__ volatile("" : "+v"(off));
@@ -178,7 +173,7 @@ struct Fast4Dec {
             const int off = (h & 1) * 512 + (h >> 1) * 256;
             return chv(e + off);
         }
-        return ld_sc(tls() + e + 256 * h);
+        return ld_bypass(tls() + e + 256 * h);
     }
     __device__ __forceinline__ void from_top(bool right, bool gstep)
     {
@@ -253,7 +248,7 @@ struct Fast4Dec {
                 for (int j = 0; j < NB; ++j) {
                     const int rr = 8 * q + i2 + j;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) in[4 * j + k] = ld_sc(s8 + at(k, rr));
+                    for (int k = 0; k < 4; ++k) in[4 * j + k] = ld_bypass(s8 + at(k, rr));
                 }
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
@@ -286,8 +281,8 @@ struct Fast4Dec {
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                     const int rr = 8 * q + i4 + j;
-                    x[j] = ld_sc(s7 + at(0, rr));
-                    y[j] = ld_sc(s7 + at(1, rr));
+                    x[j] = ld_bypass(s7 + at(0, rr));
+                    y[j] = ld_bypass(s7 + at(1, rr));
                 }
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
@@ -337,16 +332,9 @@ struct Fast4Dec {
         uint32_t cur = bit;
         const int z = __builtin_ctz(~(unsigned)j);
         const int zl = z < 5 ? z : 5;
-        for (int t = 0; t < zl; ++t) {
-            const int h = 1 << t;
-            const uint32_t mask = (1u << h) - 1u;
-            const uint32_t l = (bl0 >> h) & mask;
-            cur = (l ^ (cur & mask)) | ((cur & mask) << h);
-        }
+        for (int t = 0; t < zl; ++t) cur = ps_fold0(bl0, cur, t);
         if (z < 5) {
-            const int h = 1 << z;
-            const uint32_t mask = (1u << h) - 1u;
-            bl0 = (bl0 & ~(mask << h)) | ((cur & mask) << h);
+            bl0 = ps_save0(bl0, cur, z);
             return;
         }
         lds_fence();
@@ -535,7 +523,7 @@ struct Fast4Dec {
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int e = w16 + 16 * k;
-                v8[k] = chk(ld_sc(tl + e), ld_sc(tl + e + 256));
+                v8[k] = chk(ld_bypass(tl + e), ld_bypass(tl + e + 256));
                 *slot0(C::sc_l8, e) = v8[k];
             }
             lds_fence();
@@ -783,11 +771,7 @@ __global__ __launch_bounds__(256, (Fast4Cfg<R>::MIN_WAVES_PER_SIMD)) void k_scl_
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 uint32_t &x = h ? x1 : x0;
-                x ^= (x >> 1) & 0x55555555u;
-                x ^= (x >> 2) & 0x33333333u;
-                x ^= (x >> 4) & 0x0F0F0F0Fu;
-                x ^= (x >> 8) & 0x00FF00FFu;
-                x ^= (x >> 16) & 0x0000FFFFu;
+                x = polar_word_transform(x);
             }
 #pragma unroll
             for (int hw = 1; hw < 16; hw <<= 1) {

@@ -5,8 +5,7 @@
 //
 //     ch[N]                    channel LLRs (level n), shared by all paths
 //     alpha[L][N]              level t (2^t values) at offset 2^t of each slot's row
-//     blw[L][N/32], curw[..]   saved left-child partial sums / working partial sums, bit-packed;
-//                              level t, element e  <->  bit 2^t + e
+//     blw[L][N/32], curw[..]   saved left-child partial sums / working partial sums, bit-packed (polar_bits.h)
 //
 // The reference clones whole factor graphs on every fork (copyPath / simpleCopy,
 // SCL_1024.c:451-478: 81 % of its run time).  Here a fork copies a per-level pointer table
@@ -18,6 +17,7 @@
 // Schedule = the reference's lazy recursion getLLR/updateBit (SCL_1024.c:404-448) in its
 // natural-order form.  This kernel is the correctness baseline and
 // the fallback for shapes without a tuned instantiation; scl_fast.h holds the tuned ones.
+// The steps it shares with k_scl_q8 (fork pairing, partial sums at levels >= 5, path choice, epilogue) are scl_wave_ops.h's.
 //
 // The kernel text is scl_generic_body<..., DYN>; k_scl_generic is its DYN = false wrapper and k_scl_dyn (scl_dyn.h, which
 // says what DYN adds: a per-path history of the decided bits and the dynamic frozen leaf) its DYN = true wrapper.
@@ -26,27 +26,9 @@
 #include "polar_lut.h"
 #include "polar_params.h"
 #include "list_out.h"
+#include "scl_wave_ops.h"
 
 namespace polar {
-
-
-template <int LOGL>
-__device__ __forceinline__ int ptr_get(uint64_t tbl, int t)
-{
-    if (LOGL == 0) return 0;
-    return (int)((tbl >> (t * LOGL)) & ((1u << LOGL) - 1));
-}
-template <int LOGL>
-__device__ __forceinline__ uint64_t ptr_set(uint64_t tbl, int t, int v)
-{
-    if (LOGL == 0) return 0;
-    const uint64_t m = (uint64_t)((1u << LOGL) - 1) << (t * LOGL);
-    return (tbl & ~m) | ((uint64_t)v << (t * LOGL));
-}
-
-// scratch loads that must not be served from a stale per-CU L1 line (relaxed agent-scope atomic = sc1 load)
-__device__ __forceinline__ double ld_bypass(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_bypass(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // GA = false: every LLR level of every path in LDS.  GA = true ("LLRs spill HBM", BASELINE config 5): the
 // level arrays alpha[L][N] live in a per-workgroup slice of a global scratch buffer and the channel LLRs are
@@ -98,11 +80,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
         // ---- channel LLRs (SCL_1024.c:574-578) ----
         {
             const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
-            for (int i = lane; i < N; i += 64) {
-                double v = (double)src[i];
-                if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-                ch[i] = (R)v;
-            }
+            for (int i = lane; i < N; i += 64) ch[i] = (R)channel_llr<IN>(src, i, P.sigma);
         }
         if constexpr (DYN)
             for (int w = lane; w < L * NW; w += 64) hist[w] = 0u;
@@ -220,23 +198,8 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                 const uint64_t m_dead = __ballot(lead) & ~(m_s0 | m_s1);
                 if (__popcll(m_s0) + __popcll(m_s1) < L) fl |= 0x1u;  // median tie ("Oops!", :621-622)
                 const bool dead = !s0 && !s1;
-                // m-th both-survivor (ascending slot) forks into the m-th dead slot (:636-661)
-                const int myrank = __popcll(m_dead & ((1ull << (p * S)) - 1ull));
                 int sg = p;
-                bool refilled = false;
-                {
-                    uint64_t bm = m_both;
-                    int cnt = 0;
-                    while (bm) {
-                        const int b = __builtin_ctzll(bm);
-                        if (dead && cnt == myrank) {
-                            sg = b / S;
-                            refilled = true;
-                        }
-                        bm &= bm - 1;
-                        ++cnt;
-                    }
-                }
+                const bool refilled = fork_source<S>(m_both, m_dead, p, dead, sg);
                 const int sl = sg * S + pos;
                 const R c1_s = __shfl(c1, sl);
                 ptrA = __shfl(ptrA, sl);
@@ -278,44 +241,13 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             cur0 = (uint32_t)bit;
             int t = 0;
             while (t < n && ((j >> t) & 1)) {
-                if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    const uint32_t l = (bl0 >> h) & mask;
-                    const uint32_t c = cur0 & mask;
-                    cur0 = (l ^ c) | (c << h);
-                } else {
-                    const int nw = 1 << (t - 5);
-                    if (t == 5) {
-                        if (pos == 0 && p < act) curw[p * NW] = cur0;
-                        __syncthreads();
-                    }
-                    if (p < act) {
-                        for (int w = pos; w < nw; w += S) {
-                            const uint32_t c = curw[p * NW + w];
-                            const uint32_t l = blw[p * NW + nw + w];
-                            curw[p * NW + w] = l ^ c;
-                            curw[p * NW + w + nw] = c;
-                        }
-                    }
-                    __syncthreads();
-                }
+                if (t < 5) cur0 = ps_fold0(bl0, cur0, t);
+                else ps_update_rows<S>(blw, curw, NW, p, pos, act, cur0, t);
                 ++t;
             }
             if (t < n) {
-                if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    bl0 = (bl0 & ~(mask << h)) | ((cur0 & mask) << h);
-                } else {
-                    const int nw = 1 << (t - 5);
-                    if (t == 5) {
-                        if (pos == 0 && p < act) blw[p * NW + 1] = cur0;
-                    } else if (p < act) {
-                        for (int w = pos; w < nw; w += S) blw[p * NW + nw + w] = curw[p * NW + w];
-                    }
-                    __syncthreads();
-                }
+                if (t < 5) bl0 = ps_save0(bl0, cur0, t);
+                else ps_save_rows<S>(blw, curw, NW, p, pos, act, cur0, t);
             }
         }
 
@@ -360,32 +292,10 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             const uint32_t w0 = __shfl(h0, best * S);
             for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = (w == 0) ? w0 : hist[best * NW + w];
         } else if (n <= 5) {
-            uint32_t x = __shfl(cur0, best * S);
-            for (int s = 0; s < n; ++s) {
-                const uint32_t msk = (s == 0) ? 0x55555555u : (s == 1) ? 0x33333333u : (s == 2) ? 0x0F0F0F0Fu
-                                   : (s == 3) ? 0x00FF00FFu : 0x0000FFFFu;
-                x ^= (x >> (1 << s)) & msk;
-            }
+            const uint32_t x = polar_word_transform_n(__shfl(cur0, best * S), n);
             if (lane == 0) P.out_bits[(size_t)frame * NW] = x;
         } else {
-            uint32_t *xw = curw + (size_t)best * NW;
-            for (int w = lane; w < NW; w += 64) {
-                uint32_t x = xw[w];
-                x ^= (x >> 1) & 0x55555555u;
-                x ^= (x >> 2) & 0x33333333u;
-                x ^= (x >> 4) & 0x0F0F0F0Fu;
-                x ^= (x >> 8) & 0x00FF00FFu;
-                x ^= (x >> 16) & 0x0000FFFFu;
-                xw[w] = x;
-            }
-            __syncthreads();
-            for (int s = 5; s < n; ++s) {
-                const int hw = 1 << (s - 5);
-                for (int w = lane; w < NW; w += 64)
-                    if (!(w & hw)) xw[w] ^= xw[w + hw];
-                __syncthreads();
-            }
-            for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = xw[w];
+            uhat_from_rows(curw + (size_t)best * NW, NW, n, lane, P.out_bits + (size_t)frame * NW);
         }
         if (lane == 0) {
             if (!LIST && P.pm) P.pm[frame] = P.sc_mode ? 0.0 : (double)best_pm;

@@ -6,7 +6,7 @@
 //
 //     ch[N]                    quantised channel LLRs (level n), shared by all paths
 //     alpha[L][N (+ pad)]      level t (2^t values) at byte offset 2^t of each slot's row
-//     blw[L][N/32], curw[..]   saved left-child partial sums / working partial sums, bit-packed as in scl_generic.h
+//     blw[L][N/32], curw[..]   saved left-child partial sums / working partial sums, bit-packed (polar_bits.h)
 //     cand[2L]                 the 32-bit candidate keys of rule 5
 //
 // A level of 4 or more elements moves whole dwords: a lane loads the two source dwords (4 + 4 int8), unpacks them with
@@ -16,14 +16,15 @@
 //
 // Slots and ranks.  Rule 5 orders the live paths; a path's position in that order is its rank.  Moving a path to the slot of
 // its rank would copy its partial sums at every information leaf, so a path keeps its slot (forks copy the per-level pointer
-// table ptrA and one row of packed partial sums, as scl_generic.h does: the m-th both-survivor, ascending slot, forks into
-// the m-th dead slot) and carries its rank in a register.  The rank is only ever read as the low bits of a key.
+// table ptrA and one row of packed partial sums, as scl_generic.h does: fork_source of scl_wave_ops.h, which also holds the
+// partial-sum rows, the path choice and the epilogue) and carries its rank in a register.  The rank is only ever read as the
+// low bits of a key.
 //
 // Ranking is by counting: every path counts the keys below its two candidate keys (all keys differ), which IS the position
 // in the sorted order.  No floating point anywhere in this file's kernels except the quantiser, which is rule 1.
 #pragma once
 #include "polar_params.h"
-#include "scl_generic.h"   // ptr_get / ptr_set
+#include "scl_wave_ops.h"
 
 namespace polar {
 
@@ -224,20 +225,10 @@ __global__ __launch_bounds__(64) void k_scl_q8(Q8Params P)
                     const uint64_t m_both = m_s0 & m_s1;
                     const uint64_t m_dead = __ballot(lead) & ~(m_s0 | m_s1);
                     const bool dead = !s0 && !s1;
-                    // exactly L keys are below the L-th, so there are as many dead slots as both-survivors: the m-th
-                    // both-survivor (ascending slot) forks into the m-th dead slot
-                    const int myrank = __popcll(m_dead & ((1ull << (p * S)) - 1ull));
+                    // exactly L keys are below the L-th, so there are as many dead slots as both-survivors: every dead
+                    // slot is refilled, and `dead` stands for fork_source's result below
                     int sg = p;
-                    {
-                        uint64_t bm = m_both;
-                        int cnt = 0;
-                        while (bm) {
-                            const int b = __builtin_ctzll(bm);
-                            if (dead && cnt == myrank) sg = b / S;
-                            bm &= bm - 1;
-                            ++cnt;
-                        }
-                    }
+                    fork_source<S>(m_both, m_dead, p, dead, sg);
                     const int sl = sg * S + pos;
                     const int c1_s = __shfl(c1, sl);
                     const int n1_s = __shfl(n1, sl);
@@ -262,49 +253,18 @@ __global__ __launch_bounds__(64) void k_scl_q8(Q8Params P)
                 }
             }
 
-            // ================= partial sums (as scl_generic.h) =================
+            // ================= partial sums (updateBit: polar_bits.h, scl_wave_ops.h) =================
             if (P.crc_tab && bit) crc ^= P.crc_tab[j];
             cur0 = (uint32_t)bit;
             int t = 0;
             while (t < n && ((j >> t) & 1)) {
-                if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    const uint32_t l = (bl0 >> h) & mask;
-                    const uint32_t c = cur0 & mask;
-                    cur0 = (l ^ c) | (c << h);
-                } else {
-                    const int nw = 1 << (t - 5);
-                    if (t == 5) {
-                        if (pos == 0 && p < act) curw[p * NW] = cur0;
-                        __syncthreads();
-                    }
-                    if (p < act) {
-                        for (int w = pos; w < nw; w += S) {
-                            const uint32_t c = curw[p * NW + w];
-                            const uint32_t l = blw[p * NW + nw + w];
-                            curw[p * NW + w] = l ^ c;
-                            curw[p * NW + w + nw] = c;
-                        }
-                    }
-                    __syncthreads();
-                }
+                if (t < 5) cur0 = ps_fold0(bl0, cur0, t);
+                else ps_update_rows<S>(blw, curw, NW, p, pos, act, cur0, t);
                 ++t;
             }
             if (t < n) {
-                if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    bl0 = (bl0 & ~(mask << h)) | ((cur0 & mask) << h);
-                } else {
-                    const int nw = 1 << (t - 5);
-                    if (t == 5) {
-                        if (pos == 0 && p < act) blw[p * NW + 1] = cur0;
-                    } else if (p < act) {
-                        for (int w = pos; w < nw; w += S) blw[p * NW + nw + w] = curw[p * NW + w];
-                    }
-                    __syncthreads();
-                }
+                if (t < 5) bl0 = ps_save0(bl0, cur0, t);
+                else ps_save_rows<S>(blw, curw, NW, p, pos, act, cur0, t);
             }
         }
 
@@ -328,32 +288,10 @@ __global__ __launch_bounds__(64) void k_scl_q8(Q8Params P)
         }
         // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}
         if (n <= 5) {
-            uint32_t x = __shfl(cur0, best * S);
-            for (int s = 0; s < n; ++s) {
-                const uint32_t msk = (s == 0) ? 0x55555555u : (s == 1) ? 0x33333333u : (s == 2) ? 0x0F0F0F0Fu
-                                   : (s == 3) ? 0x00FF00FFu : 0x0000FFFFu;
-                x ^= (x >> (1 << s)) & msk;
-            }
+            const uint32_t x = polar_word_transform_n(__shfl(cur0, best * S), n);
             if (lane == 0) P.out_bits[(size_t)frame * NW] = x;
         } else {
-            uint32_t *xw = curw + (size_t)best * NW;
-            for (int w = lane; w < NW; w += 64) {
-                uint32_t x = xw[w];
-                x ^= (x >> 1) & 0x55555555u;
-                x ^= (x >> 2) & 0x33333333u;
-                x ^= (x >> 4) & 0x0F0F0F0Fu;
-                x ^= (x >> 8) & 0x00FF00FFu;
-                x ^= (x >> 16) & 0x0000FFFFu;
-                xw[w] = x;
-            }
-            __syncthreads();
-            for (int s = 5; s < n; ++s) {
-                const int hw = 1 << (s - 5);
-                for (int w = lane; w < NW; w += 64)
-                    if (!(w & hw)) xw[w] ^= xw[w + hw];
-                __syncthreads();
-            }
-            for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = xw[w];
+            uhat_from_rows(curw + (size_t)best * NW, NW, n, lane, P.out_bits + (size_t)frame * NW);
         }
         if (lane == 0) {
             if (P.pm) P.pm[frame] = P.sc_mode ? 0 : (int32_t)(best_key >> 5);

@@ -20,7 +20,7 @@
 //     alpha[N][L]              level t of slot s: elements (2^t + e) * L + s -- scl_generic.h's alpha[L][N] transposed, so
 //                              that the L threads writing element e of their own slots touch L consecutive words (no LDS
 //                              bank conflicts; coalesced stores in the global-scratch variant)
-//     blw / curw / hist [N/32][L]   bit-packed as in scl_generic.h, transposed the same way; word 0 of blw and hist lives in
+//     blw / curw / hist [N/32][L]   bit-packed (polar_bits.h), transposed the same way; word 0 of blw and hist lives in
 //                              registers (bl0, h0), cur0 is the working word below level 5
 //     cand[2L]                 candidate metrics of a forking leaf: [p] = 0-branch, [L + p] = 1-branch of slot p
 //     xptr / xcrc / xbl0 / xh0 [L]   the state that moves with a path, written by its owner before a fork, indexed by source slot
@@ -39,6 +39,10 @@
 //
 // Every __syncthreads() and every __ballot sits in control flow that is uniform for the workgroup: the conditions around
 // them are functions of j, the frozen mask, the constraint row and act only, never of the path.
+//
+// Against scl_wave_ops.h: the word-0 steps and the in-word transform are polar_bits.h's, as there.  The steps over rows stay
+// here: a row is indexed [w * L + p], its one thread walks all of its words, and the partial-sum update has no barrier
+// inside (scl_wave_ops.h's has S lanes per row and two), the fork pairing and the path choice go through LDS, not __shfl.
 #pragma once
 #include <type_traits>
 
@@ -132,11 +136,7 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
         // ---- channel LLRs (SCL_1024.c:574-578) ----
         {
             const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
-            for (int i = p; i < N; i += L) {
-                double v = (double)src[i];
-                if (P.sigma > 0) v = llr_from_y(v, P.sigma);
-                ch[i] = (R)v;
-            }
+            for (int i = p; i < N; i += L) ch[i] = (R)channel_llr<IN>(src, i, P.sigma);
         }
         if constexpr (DYN)
             for (int w = 1; w < NW; ++w) hist[w * L + p] = 0u;
@@ -297,11 +297,7 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
             int t = 0;
             while (t < n && ((j >> t) & 1)) {
                 if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    const uint32_t l = (bl0 >> h) & mask;
-                    const uint32_t c = cur0 & mask;
-                    cur0 = (l ^ c) | (c << h);
+                    cur0 = ps_fold0(bl0, cur0, t);
                 } else if (p < act) {
                     const int nw = 1 << (t - 5);
                     if (t == 5) curw[p] = cur0;
@@ -316,9 +312,7 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
             }
             if (t < n) {
                 if (t < 5) {
-                    const int h = 1 << t;
-                    const uint32_t mask = (1u << h) - 1u;
-                    bl0 = (bl0 & ~(mask << h)) | ((cur0 & mask) << h);
+                    bl0 = ps_save0(bl0, cur0, t);
                 } else if (p < act) {
                     const int nw = 1 << (t - 5);
                     if (t == 5) blw[L + p] = cur0;
@@ -374,24 +368,10 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
         else if constexpr (DYN) {
             if (p < NW) P.out_bits[(size_t)frame * NW + p] = (p == 0) ? xh0[best] : hist[p * L + best];
         } else if (n <= 5) {
-            uint32_t x = xbl0[best];
-            for (int s = 0; s < n; ++s) {
-                const uint32_t msk = (s == 0) ? 0x55555555u : (s == 1) ? 0x33333333u : (s == 2) ? 0x0F0F0F0Fu
-                                   : (s == 3) ? 0x00FF00FFu : 0x0000FFFFu;
-                x ^= (x >> (1 << s)) & msk;
-            }
-            if (p == 0) P.out_bits[(size_t)frame * NW] = x;
+            if (p == 0) P.out_bits[(size_t)frame * NW] = polar_word_transform_n(xbl0[best], n);
         } else {
             uint32_t *xw = curw + best;   // word w at xw[w * L]
-            if (p < NW) {
-                uint32_t x = xw[p * L];
-                x ^= (x >> 1) & 0x55555555u;
-                x ^= (x >> 2) & 0x33333333u;
-                x ^= (x >> 4) & 0x0F0F0F0Fu;
-                x ^= (x >> 8) & 0x00FF00FFu;
-                x ^= (x >> 16) & 0x0000FFFFu;
-                xw[p * L] = x;
-            }
+            if (p < NW) xw[p * L] = polar_word_transform(xw[p * L]);
             __syncthreads();
             for (int s = 5; s < n; ++s) {
                 const int hw = 1 << (s - 5);

@@ -1,5 +1,5 @@
-"""Developer tool: a SHA-256 per case of what k_scl_generic, k_scl_dyn and the three generators (k_generate, k_generate_rm,
-k_generate_dyn) write, for comparing two builds more finely than the tests do.
+"""Developer tool: a SHA-256 per case of what k_scl_generic, k_scl_dyn, k_scl_q8, k_scl_wide and the three generators
+(k_generate, k_generate_rm, k_generate_dyn) write, for comparing two builds more finely than the tests do.
 
     python3 tools/kernel_digests.py [ROOT] > A.txt
     python3 tools/kernel_digests.py [OTHER_ROOT] > B.txt     (same box, same session)
@@ -8,7 +8,8 @@ k_generate_dyn) write, for comparing two builds more finely than the tests do.
 ROOT is the checkout whose package and libraries are used (default: this one).  Decoders: decisions, metrics and flags of
 one batch below and one above the resident count, N = 32 / 64 / 128, L = 1 / 2 / 8 / 32, f64 and f32, LDS and global-scratch
 variant, SC / SCL / CA-SCL (CRC-6) and PAC / PC-CA-polar / random-mask dynamic sets; a quarter of the rows sits on a grid so
-that metrics tie.  Generators: LLR and y rows, f64 and f32, with u_bits.  Generator digests depend on the ROCm math library
+that metrics tie.  k_scl_q8 (float rows into a POLAR_Q8 context): SCL / CA-SCL, L = 1 / 8 / 32 at the same N; k_scl_wide:
+L = 64 at N = 32 / 64, f64 and f32, SCL / CA-SCL / PAC.  Generators: LLR and y rows, f64 and f32, with u_bits.  Generator digests depend on the ROCm math library
 (log, sincospi), so they compare builds on one installation and are not pinned anywhere."""
 import hashlib
 import os
@@ -44,8 +45,10 @@ def rows(N, f32):
     return _rows[(N, f32)]
 
 
-def decode(label, dec, variant):
-    T.select_kernel(dec, variant)
+def decode(label, dec, variant=None):
+    """variant None: the context keeps the kernel it chose (k_scl_q8, k_scl_wide)"""
+    if variant is not None:
+        T.select_kernel(dec, variant)
     f32 = dec.dtype == pa.F32
     for B in (B_SMALL, B_LARGE):
         x = rows(dec.N, f32)[:B]
@@ -53,7 +56,7 @@ def decode(label, dec, variant):
         fl = torch.zeros(B, dtype=torch.int32, device="cuda")
         bits = dec.decode_device(x, pm=pm, flags=fl)
         dec.synchronize()
-        print(f"{label} {'GA' if variant == T.KERNEL_GENERIC_SPILL else 'LDS'} B={B} {dec.kernel_name} "
+        print(f"{label} {'-' if variant is None else 'GA' if variant == T.KERNEL_GENERIC_SPILL else 'LDS'} B={B} {dec.kernel_name} "
               f"ties={int((fl & 1).sum())} {sha(bits, pm, fl)}", flush=True)
     dec.close()
 
@@ -114,4 +117,16 @@ for variant in (T.KERNEL_GENERIC, T.KERNEL_GENERIC_SPILL):
                 decode(f"dyn pc N={N} L={L} {d}", pa.PCCASCL(N, K - 9, n_pc_wm=1, L=L, dtype=dt), variant)
                 io, dyn = dyn_sets(N, K)
                 decode(f"dyn random N={N} L={L} {d}", pa.Decoder(N, K, pa.ALGO_SCL, L=L, dtype=dt, info_order=io, dyn=dyn), variant)
+for N in (32, 64, 128):
+    K = N // 2
+    for L in (1, 8, 32):
+        decode(f"q8 scl N={N} L={L}", pa.SCLdecode(N, K, L=L, dtype=pa.Q8))
+        decode(f"q8 cascl N={N} L={L}", pa.CASCL(N, K - 6, L=L, crc_taps=CRC6, dtype=pa.Q8))
+for dt in (pa.F64, pa.F32):
+    d = "f32" if dt else "f64"
+    for N in (32, 64):
+        K = N // 2
+        decode(f"wide scl N={N} L=64 {d}", pa.SCLdecode(N, K, L=64, dtype=dt))
+        decode(f"wide cascl N={N} L=64 {d}", pa.CASCL(N, K - 6, L=64, crc_taps=CRC6, dtype=dt))
+        decode(f"wide pac N={N} L=64 {d}", pa.PAC(N, K, L=64, dtype=dt))
 print("done", flush=True)
