@@ -760,6 +760,80 @@ int polar_list_gather(polar_ctx *ctx, const uint32_t *d_paths, const int32_t *d_
 int polar_list_soft(polar_ctx *ctx, const uint32_t *d_paths, const double *d_pm, const uint32_t *d_count,
                     const uint32_t *d_rem, uint32_t want_rem, int domain, double clamp, size_t B, double *d_out);
 
+/* --- Code books: one launch decodes frames of different codes (no reference counterpart) -----------------------------------
+ * Every decode above binds one launch to one context, that is to one (N, frozen set, CRC, E) for all B frames.  A receiver
+ * sees a few dozen candidates per slot at several lengths and payload sizes.  A code book holds C contexts' codes; each frame
+ * of a call names its code by an index, and one persistent kernel (k_scl_book: the text of k_scl_dyn / k_scl_list with a
+ * per-frame choice of the tables) decodes them all.  tests/test_gpu_codebook.py holds every rule below with == against the
+ * members' own contexts.
+ *   1. members: C contexts, 1 <= C <= 1024, all on one device, all of one dtype (POLAR_F64 or POLAR_F32), all of one L (a power
+ *      of two in 1..32); either every member is POLAR_ALGO_SC, or every member is POLAR_ALGO_SCL or POLAR_ALGO_CASCL (those two
+ *      mix: an SCL member has no CRC table).  They may differ in N (32..1024), K, info_order, CRC (r, taps, crc_systematic),
+ *      dynamic frozen bits (polar_create_dyn), rate matching (polar_create_rm: E, mode, ibil) and CRC-file origin.
+ *   2. snapshot: polar_codebook_create copies what a decode reads from each member into device memory the code book owns: the
+ *      frozen mask, the CRC table or none, the dynamic mask rows and row index (the D = 0 tables for a member without
+ *      constraints), N, n, E, the rate-matching mode and interleaver table, and whether the member is SC.  Members may be
+ *      changed or destroyed afterwards; the code book does not notice.  It has its own stream, scratch and work queue.
+ *   3. input: d_in is [B][ld] of double or float, ld the row stride in elements, ld >= W_max.  Frame f uses code
+ *      c = d_code[f] and reads d_in[f*ld .. f*ld + W_c), W_c = E_c on a rate-matched member and N_c otherwise; the elements
+ *      of the row beyond W_c are never read.  d_in needs the alignment of its element type only.  One sigma per call;
+ *      sigma > 0 means the input is y, as everywhere else.
+ *   4. identity -- the whole specification of the decode: for a frame with c < C the bits, the metric and the flags word are
+ *      bit for bit what polar_decode_device(members[c], row_f, in_is_f32, sigma, 1, ...) returns for that row, and for the
+ *      list call what polar_list_decode(members[c], ...) returns, all five outputs, padding included (POLAR_FLAG_RERANK
+ *      excluded, as in rule 5 of "List output").  On a rate-matched member the value at decoder position J(n) is rule 6 of
+ *      "5G NR rate matching": terms accumulated in double, rounded once to the input's type, then converted to the
+ *      arithmetic type; the recovery runs in the kernel's load stage, with no second kernel and no scratch rows.
+ *   5. output extents: d_uhat_bits is [B][N_max/32]; frame f writes all N_max/32 words, the words at or above N_c/32 as 0.
+ *      d_paths is [B][L][N_max/32] with the same rule per rank.  d_pm, d_rem, d_count and d_flags are as in the per-context
+ *      calls.  Every output is nullable, but not all of them at once.  Nothing outside these extents is written at any B.
+ *   6. bad index: a frame with d_code[f] >= C gets, from the decode, bits all 0, pm = +inf, flags = POLAR_FLAG_NO_CODE, and
+ *      from the list call count 0, every rank padding (bits 0, pm = +inf, rem 0), flags = POLAR_FLAG_NO_CODE.  The index is
+ *      device memory: the kernel compares it with C before it forms any address from it, so a bad index reads nothing.
+ *   7. asynchronous: both device calls run on the code book's stream and read nothing back; nothing grows with B (no chunk
+ *      loop, no scratch rows).  After one warm-up call they can be captured into a graph at any B.
+ *   8. composition with the list helpers: polar_list_select, polar_list_gather and polar_list_soft read only L, and N/32 for
+ *      the gather, so they work unchanged on a code book's list outputs when called on a member context with N = N_max (and
+ *      the book's L).  polar_list_soft in the x domain is only meaningful for frames whose N_c = N_max.
+ *   9. refusals, POLAR_EINVAL with nothing leaked and the members untouched: a NULL or empty list, C out of range, a NULL
+ *      member, mixed device, dtype or L, SC mixed with the list algos, any other algo, POLAR_Q8, L > 32, a member with
+ *      polar_set_systematic on, a member with a polar_cascl_set_stages rule of more than one stage; in a call ld < W_max,
+ *      B > 2^31 - 1, all outputs NULL, a misaligned d_in, a NULL d_in or d_code, the list call on a book of SC members.  A
+ *      member with N > 1024 gives POLAR_ENOKERNEL.  B == 0 returns POLAR_OK and touches nothing.
+ * Occupancy: the LDS layout, the choice between LDS-resident and global-scratch levels and the scratch slice are fixed once
+ * per launch from N_max, so a code book that mixes N = 32 with N = 1024 runs its short frames at the long frames' occupancy.
+ * Where rates matter, make one code book per N.
+ * Out of scope: wide lists (L > 32), POLAR_Q8, BP / SCF / SCAN / BPL members, systematic-polar members, adaptive stages, a
+ * per-frame sigma (callers with per-frame noise pass LLRs), generator, error-counter and fer_batch forms, polar_group_*,
+ * sorting or bucketing frames by code inside the library.
+ * Names: the two calls on device pointers are polar_codebook_decode and polar_codebook_list_decode;
+ * polar_codebook_decode_host is the host-buffer form of the first.  Their output extents (guard words around every output
+ * at ragged batches, NULL outputs) are held by tests/test_gpu_codebook.py. */
+typedef struct polar_codebook polar_codebook;
+#define POLAR_FLAG_NO_CODE 0x10u /* code-book decodes only: the frame's code index was >= C */
+int polar_codebook_create(polar_ctx *const *members, int C, polar_codebook **out);
+void polar_codebook_destroy(polar_codebook *cb);
+/* each output nullable: C, largest N, largest row width, L, dtype */
+int polar_codebook_info(const polar_codebook *cb, int *C, int *N_max, int *W_max, int *L, int *dtype);
+/* member c: N, row width W (E on a rate-matched member, else N), A; each nullable */
+int polar_codebook_member(const polar_codebook *cb, int c, int *N, int *W, int *A);
+int polar_codebook_set_stream(polar_codebook *cb, void *hip_stream);
+void *polar_codebook_get_stream(polar_codebook *cb);
+int polar_codebook_synchronize(polar_codebook *cb);
+const char *polar_codebook_kernel_name(const polar_codebook *cb); /* "k_scl_book<...>" */
+const char *polar_codebook_last_error(const polar_codebook *cb);
+/* rules 3-7: d_in [B][ld], d_code [B] -> d_uhat_bits [B][N_max/32], d_pm [B], d_flags [B]; each output nullable, not all */
+int polar_codebook_decode(polar_codebook *cb, const void *d_in, int in_is_f32, size_t ld, const uint32_t *d_code,
+                          double sigma, size_t B, uint32_t *d_uhat_bits, double *d_pm, uint32_t *d_flags);
+/* the list form: d_paths [B][L][N_max/32], d_pm [B][L], d_rem [B][L], d_count [B], d_flags [B]; each nullable, not all */
+int polar_codebook_list_decode(polar_codebook *cb, const void *d_in, int in_is_f32, size_t ld, const uint32_t *d_code,
+                               double sigma, size_t B, uint32_t *d_paths, double *d_pm, uint32_t *d_rem,
+                               uint32_t *d_count, uint32_t *d_flags);
+/* host-buffer form: in [B][ld] doubles, code [B], u_hat [B][N_max] ints 0/1, pm / flags (nullable) [B].  POLAR_ENOMEM (code
+ * book usable) if the device buffers cannot be had. */
+int polar_codebook_decode_host(polar_codebook *cb, const double *in, size_t ld, const uint32_t *code, double sigma,
+                               size_t B, int *u_hat, double *pm, unsigned *flags);
+
 /* --- Fixed-point min-sum decoding: int8 SC / SCL / CA-SCL (dtype POLAR_Q8; no reference counterpart) ----------------------
  * The decoder of hardware papers and 5G receivers: quantised LLRs, a check node that is a sign and a minimum, integer path
  * metrics.  Integer arithmetic has no rounding, so everything below is exact and is tested with == against a numpy model.

@@ -17,6 +17,7 @@ import numpy as np
 ALGO_SC, ALGO_BP, ALGO_SCL, ALGO_CASCL, ALGO_SCF, ALGO_SCAN, ALGO_BPL = 0, 1, 2, 3, 4, 5, 6
 F64, F32, Q8 = 0, 1, 2   # Q8: fixed-point min-sum on int8 LLRs (SC / SCL / CA-SCL, N <= 1024)
 FLAG_TIE, FLAG_CRC_PASS, FLAG_RERANK, FLAG_BP_CONVERGED = 1, 2, 4, 8
+FLAG_NO_CODE = 16   # code-book decodes only: the frame's code index was >= C
 RM_NONE, RM_REPEAT, RM_PUNCTURE, RM_SHORTEN = 0, 1, 2, 3   # polar_rm_info modes (5G rate matching)
 RM_SHORT_LLR = 1048576.0   # POLAR_RM_SHORT_LLR: the recovered value at a shortened position
 BP_STOP_NONE, BP_STOP_G = 0, 1   # polar_bp_set_stop: iterMax round trips / stop at the first with u_hat F == x_hat
@@ -168,6 +169,22 @@ def load_library(testing=False):
     L.polar_list_select.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
     L.polar_list_gather.argtypes = [vp, vp, vp, C.c_int, C.c_size_t, vp]
     L.polar_list_soft.argtypes = [vp, vp, vp, vp, vp, C.c_uint, C.c_int, C.c_double, C.c_size_t, vp]
+    L.polar_codebook_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
+    L.polar_codebook_destroy.argtypes = [vp]
+    L.polar_codebook_destroy.restype = None
+    L.polar_codebook_info.argtypes = [vp, ip, ip, ip, ip, ip]
+    L.polar_codebook_member.argtypes = [vp, C.c_int, ip, ip, ip]
+    L.polar_codebook_set_stream.argtypes = [vp, vp]
+    L.polar_codebook_get_stream.restype = vp
+    L.polar_codebook_get_stream.argtypes = [vp]
+    L.polar_codebook_synchronize.argtypes = [vp]
+    L.polar_codebook_kernel_name.restype = C.c_char_p
+    L.polar_codebook_kernel_name.argtypes = [vp]
+    L.polar_codebook_last_error.restype = C.c_char_p
+    L.polar_codebook_last_error.argtypes = [vp]
+    L.polar_codebook_decode.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_double, C.c_size_t, vp, vp, vp]
+    L.polar_codebook_list_decode.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_double, C.c_size_t, vp, vp, vp, vp, vp]
+    L.polar_codebook_decode_host.argtypes = [vp, dp, C.c_size_t, C.POINTER(C.c_uint32), C.c_double, C.c_size_t, ip, dp, up]
     L.polar_kernel_name.restype = C.c_char_p
     L.polar_kernel_name.argtypes = [vp]
     L.polar_version.restype = C.c_char_p
@@ -1293,6 +1310,124 @@ class Group:
             self.close()
         except Exception:
             pass
+
+
+class Codebook:
+    """polar_codebook: C decoders' codes behind one launch (include/polar_hip.h, "Code books").  Every frame of a call names
+    its code by an index into `decoders`; its bits, metric and flags are what that decoder's own decode_device returns.  The
+    codes are copied at construction: the decoders may be closed afterwards."""
+
+    def __init__(self, decoders):
+        decoders = list(decoders)
+        if not decoders:
+            raise ValueError("a code book needs at least one decoder")
+        self._lib = decoders[0]._lib
+        self._h = C.c_void_p()
+        arr = (C.c_void_p * len(decoders))(*[d._h.value for d in decoders])
+        rc = self._lib.polar_codebook_create(arr, len(decoders), C.byref(self._h))
+        if rc != 0:
+            self._h = C.c_void_p()
+            raise PolarError(f"polar_codebook_create: {self._lib.polar_strerror(rc).decode()} (rc={rc})")
+        c, n, w, l, dt = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._lib.polar_codebook_info(self._h, C.byref(c), C.byref(n), C.byref(w), C.byref(l), C.byref(dt))
+        self.C, self.N_max, self.W_max, self.L, self.dtype = c.value, n.value, w.value, l.value, dt.value
+        self.NW = self.N_max // 32
+        self.device = decoders[0].device
+        self.members = []
+        for i in range(self.C):
+            self._lib.polar_codebook_member(self._h, i, C.byref(n), C.byref(w), C.byref(c))
+            self.members.append((n.value, w.value, c.value))
+
+    @property
+    def kernel_name(self):
+        return self._lib.polar_codebook_kernel_name(self._h).decode()
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.polar_codebook_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._lib.polar_strerror(rc).decode()
+            det = self._lib.polar_codebook_last_error(self._h).decode()
+            raise PolarError(f"{what}: {msg} {det} (rc={rc})")
+
+    def use_torch_stream(self):
+        """Run on torch's current stream so that torch ops and decodes are ordered."""
+        import torch
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.polar_codebook_set_stream(self._h, C.c_void_p(s)), "polar_codebook_set_stream")
+
+    def synchronize(self):
+        self._check(self._lib.polar_codebook_synchronize(self._h), "polar_codebook_synchronize")
+
+    def _dev_args(self, d_in, code):
+        """(B, ld, in_is_f32) of rows d_in [B][>= W_max] (unit stride inside a row, any row stride) and code [B] int32"""
+        import torch
+        if not d_in.is_cuda or d_in.dim() != 2 or d_in.shape[1] < self.W_max or (d_in.shape[1] > 1 and d_in.stride(1) != 1):
+            raise ValueError(f"device rows must be a CUDA tensor of shape [B][>= {self.W_max}] with unit stride inside a row")
+        if d_in.dtype not in (torch.float32, torch.float64):
+            raise ValueError("input must be float64 or float32")
+        B = d_in.shape[0]
+        ld = d_in.stride(0) if B > 1 else d_in.shape[1]
+        if not (code.is_cuda and code.is_contiguous()) or code.dtype != torch.int32 or tuple(code.shape) != (B,):
+            raise ValueError("code must be a contiguous CUDA int32 tensor of shape [B]")
+        return B, ld, 1 if d_in.dtype == torch.float32 else 0
+
+    def decode_device(self, d_in, code, sigma=0.0, out_bits=None, pm=None, flags=None):
+        """polar_codebook_decode: d_in [B][ld] float64 or float32 (the row stride is read from d_in.stride(0)), code [B] int32
+        (the bits of an unsigned index).  Returns out_bits: int32 [B][N_max/32]; pm (float64 [B]) and flags (int32 [B]) are
+        optional tensors."""
+        import torch
+        B, ld, f32 = self._dev_args(d_in, code)
+        if out_bits is None:
+            out_bits = torch.empty((B, self.NW), dtype=torch.int32, device=d_in.device)
+        self._check(self._lib.polar_codebook_decode(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, ld, C.c_void_p(code.data_ptr()), float(sigma), B,
+            C.c_void_p(out_bits.data_ptr()), C.c_void_p(pm.data_ptr()) if pm is not None else None,
+            C.c_void_p(flags.data_ptr()) if flags is not None else None), "polar_codebook_decode")
+        return out_bits
+
+    def decode_list_device(self, d_in, code, sigma=0.0, want_paths=True, want_pm=True, want_rem=True, want_count=True,
+                           want_flags=True):
+        """polar_codebook_list_decode -> (paths [B][L][N_max/32] int32, pm [B][L] float64, rem [B][L] int32, count [B] int32,
+        flags [B] int32) as Decoder.decode_list_device; an output not asked for is None and is not computed."""
+        import torch
+        B, ld, f32 = self._dev_args(d_in, code)
+        dev, i32 = d_in.device, torch.int32
+        paths = torch.empty((B, self.L, self.NW), dtype=i32, device=dev) if want_paths else None
+        pm = torch.empty((B, self.L), dtype=torch.float64, device=dev) if want_pm else None
+        rem = torch.empty((B, self.L), dtype=i32, device=dev) if want_rem else None
+        count = torch.empty(B, dtype=i32, device=dev) if want_count else None
+        flags = torch.empty(B, dtype=i32, device=dev) if want_flags else None
+        self._check(self._lib.polar_codebook_list_decode(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, ld, C.c_void_p(code.data_ptr()), float(sigma), B,
+            *[C.c_void_p(t.data_ptr()) if t is not None else None for t in (paths, pm, rem, count, flags)]),
+            "polar_codebook_list_decode")
+        return paths, pm, rem, count, flags
+
+    def decode_batch(self, rows, code, sigma=0.0):
+        """polar_codebook_decode_host: host rows [B][ld >= W_max] and code [B] -> (u_hat [B][N_max] int32 0/1, pm [B], flags
+        [B] uint32)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        code = np.ascontiguousarray(code, dtype=np.uint32)
+        if rows.ndim != 2 or rows.shape[1] < self.W_max or code.shape != (rows.shape[0],):
+            raise ValueError(f"rows must have shape [B][>= {self.W_max}] and code shape [B]")
+        B, ld = rows.shape
+        uh = np.empty((B, self.N_max), dtype=np.int32)
+        pm = np.zeros(B, dtype=np.float64)
+        fl = np.zeros(B, dtype=np.uint32)
+        self._check(self._lib.polar_codebook_decode_host(self._h, _ptr(rows, C.c_double), ld, _ptr(code, C.c_uint32), float(sigma), B,
+                                                         _ptr(uh, C.c_int), _ptr(pm, C.c_double), _ptr(fl, C.c_uint)),
+                    "polar_codebook_decode_host")
+        return uh, pm, fl
 
 
 # ---- mirrors of the reference entry points (same names, same argument meaning) -----------------------

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "book_desc.h"
 #include "dev_owned.h"
 #include "polar_params.h"
 
@@ -336,6 +337,11 @@ int list_select(polar_ctx *c, const uint32_t *d_rem, const uint32_t *d_count, si
 int list_gather(polar_ctx *c, const uint32_t *d_paths, const int32_t *d_idx, int idx_stride, size_t B, uint32_t *d_out);
 int list_soft(polar_ctx *c, const uint32_t *d_paths, const double *d_pm, const uint32_t *d_count, const uint32_t *d_rem,
               uint32_t want_rem, int domain, double clamp, size_t B, double *d_out);
+// k_book.hip: code books (scl_book.h): c is the book's internal context (the largest member's N, the book's L); P.N / P.n
+// are that member's, K names the descriptors, the frames' code indices and the input's row stride
+int book_decode(polar_ctx *c, const polar::SclParams &P, const polar::BookArgs &K, bool r32, bool in32);
+int book_list(polar_ctx *c, const polar::SclParams &P, const polar::BookArgs &K, bool r32, bool in32, uint32_t *d_paths,
+              double *d_pm, uint32_t *d_rem, uint32_t *d_count);
 #ifdef POLAR_TESTING
 int scl_fast4(polar_ctx *c, const polar::SclParams &P, bool r32, bool in32, bool crc);     // k_fast4.hip (libpolar_hip_testing.so only)
 #endif

@@ -26,6 +26,7 @@
 #include "polar_lut.h"
 #include "polar_params.h"
 #include "list_out.h"
+#include "book_desc.h"
 #include "scl_wave_ops.h"
 
 namespace polar {
@@ -36,14 +37,21 @@ namespace polar {
 // DYN = false: dyn_mask and dyn_row are never read.
 // LIST = true (needs DYN, k_list.hip): the decode is the same; the epilogue writes every live slot to *LO in ascending
 // (PM, slot) instead of the chosen path to P.out_bits / P.pm.  LIST = false: LO is never read.
-template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false>
+// BOOK = true (needs DYN, k_book.hip): a code book.  P.N / P.n are the largest member's and fix the LDS layout, the scratch
+// slice and the width of the output rows once per workgroup; every frame takes N, n, the frozen mask, the CRC table, the
+// constraint tables and sc_mode from the descriptor BK->codes[BK->code[frame]] (book_desc.h), and its loops and row strides
+// run on its own N.  Whatever a longer earlier frame left in LDS lies outside this frame's rows or is rewritten before it
+// is read; hist, the one array read before it is written, is cleared over this frame's rows.  Output words from N / 32 up
+// to P.N / 32 are written as 0, and every output is nullable.  BOOK = false: BK is never read.
+template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false, bool BOOK = false>
 __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint32_t *dyn_mask, const int *dyn_row,
-                                                 const ListOut *LO = nullptr)
+                                                 const ListOut *LO = nullptr, const BookArgs *BK = nullptr)
 {
     static_assert(DYN || !LIST, "the list epilogue reads the per-path history");
+    static_assert(DYN || !BOOK, "a code book runs the dynamic leaf of every member");
     constexpr int L = 1 << LOGL;
     constexpr int S = 64 / L;
-    const int N = P.N, n = P.n, NW = N >> 5;
+    const int NL = P.N, NWL = NL >> 5;   // the layout's N: the frame's own N but in a code book
     const int lane = threadIdx.x;
     const int p = lane / S, pos = lane % S;
 
@@ -51,21 +59,21 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
     R *ch, *alpha;
     uint32_t *blw;
     if constexpr (GA) {
-        ch = reinterpret_cast<R *>(P.scratch) + (size_t)blockIdx.x * (size_t)(L + 1) * N;
-        alpha = ch + N;
+        ch = reinterpret_cast<R *>(P.scratch) + (size_t)blockIdx.x * (size_t)(L + 1) * NL;
+        alpha = ch + NL;
         blw = reinterpret_cast<uint32_t *>(smem);
     } else {
         ch = reinterpret_cast<R *>(smem);
-        alpha = ch + N;
-        blw = reinterpret_cast<uint32_t *>(alpha + (size_t)L * N);
+        alpha = ch + NL;
+        blw = reinterpret_cast<uint32_t *>(alpha + (size_t)L * NL);
     }
-    uint32_t *curw = blw + (size_t)L * NW;
-    R *cand = reinterpret_cast<R *>(curw + (size_t)L * NW);
+    uint32_t *curw = blw + (size_t)L * NWL;
+    R *cand = reinterpret_cast<R *>(curw + (size_t)L * NWL);
     // table-driven staircase (polar_lut.h): same bits as polar_math.h's chk / phi, a third of the instructions
     unsigned char *lut_mem = reinterpret_cast<unsigned char *>(cand + 2 * L);
     // DYN: hist[L][NW] behind cand (L * NW may be odd, cand holds doubles) and the tables behind hist
     uint32_t *hist = reinterpret_cast<uint32_t *>(cand + 2 * L);
-    if constexpr (DYN) lut_mem = reinterpret_cast<unsigned char *>(hist + (size_t)L * NW);
+    if constexpr (DYN) lut_mem = reinterpret_cast<unsigned char *>(hist + (size_t)L * NWL);
     lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
     Lut<R>::build(lut_mem, lane, 64);
     Lut<R> lut;
@@ -77,10 +85,43 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
     };
 
     for (int frame = blockIdx.x; frame < P.B; frame = next_job_wave(P.queue, frame, (int)gridDim.x, P.B)) {   // one wavefront per workgroup
+        // ---- the frame's code: the launch's, or in a code book the member its index names ----
+        int N = NL, n = P.n, NW = NWL, sc_mode = P.sc_mode;
+        const uint32_t *fmask = P.frozen, *crc_tab = P.crc_tab;
+        size_t ld_in = (size_t)NL;
+        BookCode bc{};
+        if constexpr (BOOK) {
+            // the index comes from device memory: it is compared with C before any address is formed from it
+            const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)BK->code[frame]);
+            if (code >= BK->C) {
+                if constexpr (LIST) {
+                    if (LO->paths)
+                        for (int w = lane; w < L * NWL; w += 64) LO->paths[(size_t)frame * L * NWL + w] = 0u;
+                    if (lane < L) {
+                        if (LO->pm) LO->pm[(size_t)frame * L + lane] = __builtin_huge_val();
+                        if (LO->rem) LO->rem[(size_t)frame * L + lane] = 0u;
+                    }
+                    if (lane == 0 && LO->count) LO->count[frame] = 0u;
+                } else {
+                    if (P.out_bits)
+                        for (int w = lane; w < NWL; w += 64) P.out_bits[(size_t)frame * NWL + w] = 0u;
+                    if (lane == 0 && P.pm) P.pm[frame] = __builtin_huge_val();
+                }
+                if (lane == 0 && P.flags) P.flags[frame] = BOOK_FLAG_NO_CODE;
+                continue;
+            }
+            bc = book_code(BK->codes, code);
+            N = bc.N, n = bc.n, NW = N >> 5, sc_mode = bc.sc_mode;
+            fmask = bc.frozen, crc_tab = bc.crc_tab;
+            dyn_mask = bc.dyn_mask, dyn_row = bc.dyn_row;
+            ld_in = BK->ld;
+        }
         // ---- channel LLRs (SCL_1024.c:574-578) ----
         {
-            const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * N;
-            for (int i = lane; i < N; i += 64) ch[i] = (R)channel_llr<IN>(src, i, P.sigma);
+            const IN *src = reinterpret_cast<const IN *>(P.in) + (size_t)frame * ld_in;
+            if (BOOK && bc.rm_mode != BOOK_RM_NONE) book_rm_load<R, IN>(ch, src, bc, P.sigma, lane);
+            else
+                for (int i = lane; i < N; i += 64) ch[i] = (R)channel_llr<IN>(src, i, P.sigma);
         }
         if constexpr (DYN)
             for (int w = lane; w < L * NW; w += 64) hist[w] = 0u;
@@ -127,7 +168,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             const R lam = (p < act) ? ld(alpha + (size_t)p * N + 1) : R(0);
 
             // ================= decision =================
-            const bool frozen = (P.frozen[j >> 5] >> (j & 31)) & 1;
+            const bool frozen = (fmask[j >> 5] >> (j & 31)) & 1;
             int row = -1;   // DYN: row of leaf j in the constraint matrix, -1 = not dynamic (wave-uniform, like j)
             if constexpr (DYN) row = dyn_row[j];
             int bit = 0;
@@ -144,9 +185,9 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                     for (int o = S >> 1; o > 0; o >>= 1) par ^= (uint32_t)__shfl_xor((int)par, o);
                     bit = (int)(par & 1u);
                     // PHI(., b) with the rounding of an information leaf's branch b
-                    if (!P.sc_mode && p < act) PM = PM + (lut.tabv(lam) + (bit ? posmax(lam) : negmax(lam)));
+                    if (!sc_mode && p < act) PM = PM + (lut.tabv(lam) + (bit ? posmax(lam) : negmax(lam)));
                 }
-            } else if (P.sc_mode) {
+            } else if (sc_mode) {
                 bit = (!frozen && lam < R(0)) ? 1 : 0;  // SC_128.c:426-431
             } else if (frozen) {
                 if (p < act) PM += lut.tabv(lam) + negmax(lam);  // PHI(.,0), SCL_1024.c:601-604, :662-665
@@ -237,7 +278,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             }
 
             // ================= partial sums (updateBit, SCL_1024.c:424-448) =================
-            if (P.crc_tab && bit) crc ^= P.crc_tab[j];
+            if (crc_tab && bit) crc ^= crc_tab[j];
             cur0 = (uint32_t)bit;
             int t = 0;
             while (t < n && ((j >> t) & 1)) {
@@ -254,8 +295,8 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
         // ================= choose the path (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) =================
         int best = 0;
         R best_pm = PM;
-        if (!P.sc_mode) {
-            const bool pass = (P.crc_tab != nullptr) && (crc == 0);
+        if (!sc_mode) {
+            const bool pass = (crc_tab != nullptr) && (crc == 0);
             const bool any = __ballot(pass && p < act) != 0ull;
             best = -1;
             best_pm = R(0);
@@ -279,7 +320,11 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             }
             const bool live = p < act;
             const size_t row = (size_t)frame * L + (size_t)(live ? rank : p);
-            if (LO->paths)
+            if constexpr (BOOK) {
+                if (LO->paths)
+                    for (int w = pos; w < NWL; w += S)
+                        LO->paths[row * NWL + w] = (!live || w >= NW) ? 0u : (w == 0) ? h0 : hist[p * NW + w];
+            } else if (LO->paths)
                 for (int w = pos; w < NW; w += S) LO->paths[row * NW + w] = !live ? 0u : (w == 0) ? h0 : hist[p * NW + w];
             if (pos == 0) {
                 if (LO->pm) LO->pm[row] = live ? (double)PM : __builtin_huge_val();
@@ -290,7 +335,9 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
         // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
         else if constexpr (DYN) {
             const uint32_t w0 = __shfl(h0, best * S);
-            for (int w = lane; w < NW; w += 64) P.out_bits[(size_t)frame * NW + w] = (w == 0) ? w0 : hist[best * NW + w];
+            if (!BOOK || P.out_bits)
+                for (int w = lane; w < NWL; w += 64)
+                    P.out_bits[(size_t)frame * NWL + w] = (BOOK && w >= NW) ? 0u : (w == 0) ? w0 : hist[best * NW + w];
         } else if (n <= 5) {
             const uint32_t x = polar_word_transform_n(__shfl(cur0, best * S), n);
             if (lane == 0) P.out_bits[(size_t)frame * NW] = x;
@@ -298,8 +345,8 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             uhat_from_rows(curw + (size_t)best * NW, NW, n, lane, P.out_bits + (size_t)frame * NW);
         }
         if (lane == 0) {
-            if (!LIST && P.pm) P.pm[frame] = P.sc_mode ? 0.0 : (double)best_pm;
-            if (P.flags) P.flags[frame] = P.sc_mode ? 0u : fl;
+            if (!LIST && P.pm) P.pm[frame] = sc_mode ? 0.0 : (double)best_pm;
+            if (P.flags) P.flags[frame] = sc_mode ? 0u : fl;
         }
         __syncthreads();
     }
