@@ -15,6 +15,7 @@
 // Arithmetic is the same as k_scl_fast / the reference, operation for operation.
 #pragma once
 #include "fast2_lds.h"
+#include "fast2_scratch.h"
 #include "octet_bits.h"
 #include "scl_fast.h"
 
@@ -28,13 +29,17 @@ struct Fast2Cfg {
     static constexpr int WAVES = 4;
     static constexpr int MIN_WAVES_PER_SIMD = sizeof(R) == 8 ? 3 : 4;
     static constexpr int NFA = HI - 3;  // pointer fields: LLR levels 4..8, then partial-sum levels 5..9
-    // per-codeword scratch (elements of R)
-    static constexpr size_t sc_l8 = 0;
-    static constexpr size_t sc_l7 = sc_l8 + 8 * 256;
-    static constexpr size_t sc_l6 = sc_l7 + 8 * 128;   // level 6 rows: not used (level 6 is in registers)
-    static constexpr size_t sc_tl = sc_l6 + 8 * 64;
-    static constexpr size_t scratch_cw = sc_tl + 512;
+    // per-codeword scratch (elements of R); the elements of a level-7 / level-8 row lie in the order of fast2_scratch.h
+    static constexpr size_t sc_l8 = fast2_scratch::SC_L8;
+    static constexpr size_t sc_l7 = fast2_scratch::SC_L7;   // behind 8 rows of 256
+    static constexpr size_t sc_l6 = fast2_scratch::SC_L6;   // behind 8 rows of 128; level 6 rows: not used (level 6 is in registers)
+    static constexpr size_t sc_tl = fast2_scratch::SC_TL;   // behind 8 rows of 64
+    static constexpr size_t scratch_cw = fast2_scratch::SCRATCH_CW;   // the top-left level: 512
     static constexpr size_t scratch_elems = 2 * scratch_cw;  // per wave
+    // f64: the level-7 / level-8 rows in the order of fast2_scratch.h, a lane's passes 2m, 2m + 1 in one 16-byte access.
+    // f32 keeps the rows in element order and one access per element: the permuted order measured 1.4 % slower there,
+    // with 8-byte paired accesses and without
+    static constexpr bool PAIRED = sizeof(R) == 8;
     // block-shared LDS
     static constexpr size_t off_lut = 0;
     static constexpr size_t off_frz = off_lut + ((Lut<R>::bytes + 15) / 16) * 16;
@@ -121,6 +126,23 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     {
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, eoff * 4u, 0, 0);
     }
+    // f64: two adjacent elements from an even element offset in one 16-byte access (a lane's passes 2m, 2m + 1 of a
+    // level-7 / level-8 row: fast2_scratch.h); same descriptors, same sc1 policy
+    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+    struct R2 {
+        R a, b;
+    };
+    static __device__ __forceinline__ R2 ld_buf2(__amdgpu_buffer_rsrc_t r, unsigned eoff, int aux)
+    {
+        static_assert(sizeof(R2) == 16, "paired accesses are for f64");
+        return aux ? __builtin_bit_cast(R2, __builtin_amdgcn_raw_buffer_load_b128(r, eoff * 8u, 0, 16))
+                   : __builtin_bit_cast(R2, __builtin_amdgcn_raw_buffer_load_b128(r, eoff * 8u, 0, 0));
+    }
+    static __device__ __forceinline__ void st_buf2(__amdgpu_buffer_rsrc_t r, unsigned eoff, R2 v)
+    {
+        static_assert(sizeof(R2) == 16, "paired accesses are for f64");
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_t, v), r, eoff * 8u, 0, 0);
+    }
     // "pointer" into the wavefront's scratch: an element offset; q + k, q[k] = v and ld_sc(q) read like the pointer code
     struct SPtr {
         const Fast2Dec *d;
@@ -134,6 +156,25 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         __device__ __forceinline__ Ref operator[](int k) const { return Ref{d, off + (unsigned)k}; }
     };
     static __device__ __forceinline__ R ld_sc(SPtr q) { return ld_buf(q.d->rs_scr, q.off, R(0), 1); }
+    // where an element of a level-7 / level-8 row lies behind l7() / l8(): every reader and writer of the rows asks here,
+    // where it uses the row.  sg(e): element e; sg2(pos, m): the first of the pair (pos + 8m, pos + 8m + 4), a lane's
+    // passes 2m and 2m + 1; the second lies sg(4) behind it (PAIRED: 1)
+    static __device__ __forceinline__ int sg(int e) { return C::PAIRED ? (int)fast2_scratch::sigma((unsigned)e) : e; }
+    static __device__ __forceinline__ int sg2(int pos, int m) { return C::PAIRED ? (int)fast2_scratch::pair_at((unsigned)pos, (unsigned)m) : pos + 8 * m; }
+    // a lane's pair at q = row + sg2(pos, m): one access where the order makes it adjacent, else one per element
+    static __device__ __forceinline__ R2 ld_sc2(SPtr q)
+    {
+        if constexpr (C::PAIRED) return ld_buf2(q.d->rs_scr, q.off, 1);
+        else return R2{ld_sc(q), ld_sc(q + sg(4))};
+    }
+    static __device__ __forceinline__ void st_sc2(SPtr q, R a, R b)
+    {
+        if constexpr (C::PAIRED) st_buf2(q.d->rs_scr, q.off, R2{a, b});
+        else {
+            q[0] = a;
+            q[sg(4)] = b;
+        }
+    }
 
     // word offset of a slot's row in blw / curw: every reader and writer of the rows asks here, where it uses the row
     static __device__ __forceinline__ int row(int slot) { return fast2_lds::row(slot); }
@@ -250,14 +291,13 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
 #pragma unroll 1
             for (int i = 0; i < 4; ++i) {
                 const int rr = 4 * q + i;
-                const int e0 = pos + 4 * rr;
+                const int s0 = sg(pos + 4 * rr);   // where element e0 = pos + 4 rr lies in a level-8 / level-7 row
                 const int sh = 4 * (rr & 7);
                 const int wq = rr >> 3;
                 const int wi = 4 * i + pos;  // position inside a staged segment
                 R *v8 = A + 12;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const int e = e0 + 64 * k;
                     R x, y;
                     if (right) {
                         const uint32_t w0 = bt[2 * k + wq] >> pos, w1 = bt[8 + 2 * k + wq] >> pos;
@@ -269,11 +309,11 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
                     }
                     if (gstep) v8[k] = g_bit<R>(x, y, bh[2 * k + wq] >> pos, sh);
                     else v8[k] = chk(x, y);
-                    o8[e] = v8[k];
+                    o8[s0 + 64 * k] = v8[k];   // element e0 + 64 k
                 }
                 const R v70 = chk(v8[0], v8[2]), v71 = chk(v8[1], v8[3]);
-                o7[e0] = v70;
-                o7[e0 + 64] = v71;
+                o7[s0] = v70;
+                o7[s0 + 64] = v71;
                 push_l6(chk(v70, v71));
             }
         }
@@ -289,26 +329,39 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         const SPtr s8 = l8(pa(8));
         const uint32_t *b7 = blw + row(pb(7)) + 4;  // beta_7: words 4..7
         const SPtr o7 = l7(p);
-        constexpr int CP = sizeof(R) == 8 ? 2 : 4;   // passes per chunk (4 loads each); f64: 8 in flight is the measured optimum
+        // passes per chunk; the passes 2m, 2m + 1 share their four paired loads and two paired stores.  In bytes per lane
+        // a chunk is what it was with 8-byte accesses (f64: 64, the measured optimum), in half the instructions
+        constexpr int CP = sizeof(R) == 8 ? 2 : 4;
+        static_assert(CP % 2 == 0 && 4 * CP <= 16, "a chunk is whole pairs of passes and fits the dead registers");
         for (int q = 0; q < 16 / CP; ++q) {
             R *in = A;       // levels 2..5: dead here, recomputed by the f chain below
 #pragma unroll
-            for (int i = 0; i < CP; ++i) {
-                const int e0 = pos + 4 * (CP * q + i);
+            for (int j = 0; j < CP / 2; ++j) {
+                const int m = CP / 2 * q + j;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) in[4 * i + k] = ld_sc(s8 + e0 + 64 * k);
+                for (int k = 0; k < 4; ++k) {
+                    const R2 v = ld_sc2(s8 + sg2(pos, m) + 64 * k);
+                    in[8 * j + k] = v.a;       // pass 2m
+                    in[8 * j + 4 + k] = v.b;   // pass 2m + 1
+                }
             }
 #pragma unroll
-            for (int i = 0; i < CP; ++i) {
-                const int rr = CP * q + i;
-                const int e0 = pos + 4 * rr;
-                const int sh = 4 * (rr & 7);
-                const int wq = rr >> 3;
-                const R v70 = g_bit<R>(in[4 * i], in[4 * i + 2], b7[wq] >> pos, sh);
-                const R v71 = g_bit<R>(in[4 * i + 1], in[4 * i + 3], b7[2 + wq] >> pos, sh);
-                o7[e0] = v70;
-                o7[e0 + 64] = v71;
-                push_l6(chk(v70, v71));
+            for (int j = 0; j < CP / 2; ++j) {
+                const int m = CP / 2 * q + j;
+                R v70[2], v71[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int i = 2 * j + h;
+                    const int rr = CP * q + i;
+                    const int sh = 4 * (rr & 7);
+                    const int wq = rr >> 3;
+                    v70[h] = g_bit<R>(in[4 * i], in[4 * i + 2], b7[wq] >> pos, sh);
+                    v71[h] = g_bit<R>(in[4 * i + 1], in[4 * i + 3], b7[2 + wq] >> pos, sh);
+                }
+                st_sc2(o7 + sg2(pos, m), v70[0], v70[1]);
+                st_sc2(o7 + sg2(pos, m) + 64, v71[0], v71[1]);
+                push_l6(chk(v70[0], v71[0]));
+                push_l6(chk(v70[1], v71[1]));
             }
         }
         set_pa(7, p);
@@ -317,13 +370,15 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     __device__ __forceinline__ void from_l7()  // d == 6
     {
         vm_drain();
-        const SPtr s7 = l7(pa(7)) + pos;
+        const SPtr s7 = l7(pa(7));
         const uint32_t *b6 = blw + row(pb(6)) + 2;  // beta_6: words 2, 3
         const uint32_t w0 = b6[0] >> pos, w1 = b6[1] >> pos;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const R x = ld_sc(s7 + 4 * r), y = ld_sc(s7 + 4 * r + 64);
-            A[16 + r] = g_bit<R>(x, y, r < 8 ? w0 : w1, 4 * (r & 7));
+        for (int m = 0; m < 8; ++m) {   // passes r = 2m, 2m + 1: elements pos + 4r and + 64, one paired load each
+            const R2 x = ld_sc2(s7 + sg2(pos, m)), y = ld_sc2(s7 + sg2(pos, m) + 64);
+            const int r = 2 * m;
+            A[16 + r] = g_bit<R>(x.a, y.a, r < 8 ? w0 : w1, 4 * (r & 7));
+            A[17 + r] = g_bit<R>(x.b, y.b, r < 8 ? w0 : w1, 4 * ((r + 1) & 7));
         }
         set_pa(6, p);
     }
@@ -587,19 +642,19 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         vm_drain();   // the top-left level written by the root step
         {
             const SPtr tl = tls();
-            const SPtr o8 = l8(0), o7 = l7(0);
+            const SPtr o8 = l8(0) + sg(w32), o7 = l7(0) + sg(w32);   // element w32 + 32 k lies at sg(w32) + 32 k
             R v8[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int e = w32 + 32 * k;
                 v8[k] = chk(ld_sc(tl + e), ld_sc(tl + e + 256));
-                o8[e] = v8[k];
+                o8[32 * k] = v8[k];
             }
             lds_fence();
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const R v7 = chk(v8[k], v8[k + 4]);   // elements e and e + 128 of level 8
-                o7[w32 + 32 * k] = v7;
+                o7[32 * k] = v7;
                 stg[w32 + 32 * k] = v7;
             }
             set_pa(8, 0);
@@ -694,13 +749,13 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             wq[0] = (uint32_t)__shfl((int)wsel, gl) >> w32;
             wq[1] = (uint32_t)__shfl((int)wsel, 8 + gl) >> w32;
             if (S == 128) {   // g at level 7 from slot 0's level-8 row (the prefix's), f to level 6
-                const SPtr s8 = l8(0) + w32;
+                const SPtr s8 = l8(0) + sg(w32);   // element w32 + 32 k of a row lies at sg(w32) + 32 k
                 R v8[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v8[k] = ld_sc(s8 + 32 * k);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const SPtr o7 = l7(q) + w32;
+                    const SPtr o7 = l7(q) + sg(w32);
                     R v7[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
@@ -714,7 +769,7 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             } else {          // g at level 6 from the path's level-7 row
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const SPtr s7 = l7(q) + w32;
+                    const SPtr s7 = l7(q) + sg(w32);
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
                         stg[64 * q + w32 + 32 * i] = g_bit<R>(ld_sc(s7 + 32 * i), ld_sc(s7 + 32 * i + 64), wq[q], 0);
