@@ -1,6 +1,6 @@
 // polar_host.h -- internal: the context object behind the C ABI and the launcher each kernel translation unit exports.
 // The library is built from several translation units (one per kernel family, compiled in parallel; see
-// __graft_entry__.py): polar_hip.hip holds the C ABI and the host logic, k_*.hip the kernels with their launch code.
+// __graft_entry__.py): polar_hip.hip and h_*.hip hold the C ABI and the host logic, k_*.hip the kernels with their launch code.
 #pragma once
 #include "../../include/polar_hip.h"
 
@@ -23,7 +23,7 @@ struct ScanParams;  // scan_lanes.h
 }
 
 // What belongs to one stream of a ctx.  The rule: a buffer that a decode on c->stream writes and that the two halves of
-// fer_batch_impl (polar_hip.hip) would share belongs here, beside the stream.  A polar_ctx IS its current lane (c->stream,
+// fer_batch_impl (h_fer.hip) would share belongs here, beside the stream.  A polar_ctx IS its current lane (c->stream,
 // c->scratch, ... are the names the k_*.hip launchers read) and holds a second one, lane_b; swap_lane() below is the only
 // code that exchanges the two, so a member added here is swapped without another line.
 // Deliberately outside the lane: the ad_* / scf_* buffers (fer_batch_impl does not split for adaptive CA-SCL or SC-Flip)

@@ -1068,7 +1068,7 @@ __device__ __forceinline__ void scl_fast2_body(const SclParams &P)
         // ---- choose the path, per codeword (SCL_1024.c:667-674; CASCL_1024_L8.c:725-755) ----
         // The CRC remainder is read once, here, so it is computed once, here: it is linear in u_hat = x_hat F^{(x)n}, and
         // every slot's x_hat is in curw since leaf 1023 carried to the root.  Bit i of the remainder is the parity of
-        // x_hat AND mask i (polar_hip.hip make_crc_masks); a lane takes its eight words pos + 4j of the slot's row, and the
+        // x_hat AND mask i (h_code.hip make_crc_masks); a lane takes its eight words pos + 4j of the slot's row, and the
         // four lanes of the slot add their parities.  Masks come four at a time (the ones from crc_r up are zero).
         bool pass = false;
         if constexpr (CRC_ON) {

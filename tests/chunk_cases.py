@@ -1,4 +1,4 @@
-"""The cases that run the chunked host loops of csrc/polar_hip.hip across a pass boundary (a plain helper module, imported by
+"""The cases that run the chunked host loops of csrc/polar_hip.hip and csrc/h_*.hip across a pass boundary (a plain helper module, imported by
 tests/test_chunks_host.py and tests/test_gpu_chunks.py).
 
 Seven loops cut a batch into passes of at most 256 MiB of rows (chunk_rows) and offset every input, output and list pointer

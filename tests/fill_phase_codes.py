@@ -2,7 +2,7 @@
 phase ends, restated.  tests/test_fill_phase_host.py holds polar_fill_phase_end to the restatement on every code here;
 tests/test_gpu_fast2_fill_phase.py decodes them.
 
-The rule (N = 1024; csrc/polar_hip.hip fill_phase_end): E is the largest of 256, 192, 128 with
+The rule (N = 1024; csrc/h_code.hip fill_phase_end): E is the largest of 256, 192, 128 with
   (a) at most three information leaves below E,
   (b) each of them one of the last two leaves of its 64-leaf block, and none below leaf 126,
   (c) for E > 128, exactly one of them below leaf 128 and no other one below E - 64 (exactly two paths enter every block

@@ -1,6 +1,6 @@
 """CPU: the cases of tests/chunk_cases.py do what they are there for, from the models alone.
 
-tests/test_gpu_chunks.py runs the chunked host loops of csrc/polar_hip.hip across pass boundaries and compares with ==.  It
+tests/test_gpu_chunks.py runs the chunked host loops of csrc/polar_hip.hip and csrc/h_*.hip across pass boundaries and compares with ==.  It
 can only see a slipped offset if the frames really spread over several passes and if the frames of the later passes have
 something to get wrong: a frame decided at every level, lists built from the sets of the level before, open frames of every
 class.  Those conditions are asserted here, not assumed."""

@@ -1,4 +1,4 @@
-"""GPU: every chunked host loop of csrc/polar_hip.hip across its pass boundaries, at small shapes.
+"""GPU: every chunked host loop of csrc/polar_hip.hip and csrc/h_*.hip across its pass boundaries, at small shapes.
 
 The loops cut a batch into passes of at most 256 MiB of rows and offset every input, output and list pointer per pass; a
 slipped offset changes every frame beyond the first pass and nothing else.  polardecoding_amd.testing.chunk_bytes() lowers

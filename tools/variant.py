@@ -44,7 +44,7 @@ def build(args):
     flags += args.flags.split() if args.flags else []
     objs = []
     procs = []
-    for tu in g.KERNEL_TUS + ["polar_hip"]:
+    for tu in g.KERNEL_TUS + g.HOST_TUS + ["polar_hip"]:
         if tu in tus:
             obj = os.path.join(odir, tu + ".o")
             cmd = [g._hipcc()] + flags + ["-c", "-o", obj, os.path.join(g.CSRC, tu + ".hip")]
