@@ -38,6 +38,25 @@ int polar_testing_big_split(polar_ctx *ctx, int split);
  * 256 MiB.  The kernels and what they compute per frame do not depend on it. */
 int polar_testing_chunk_bytes(polar_ctx *ctx, size_t bytes);
 
+/* Every decoder kernel is persistent: a launch starts as many blocks as stay resident at once, a wavefront (or block) takes
+ * its first job by its index and every further one from a counter.  On an MI355X that resident set is thousands of
+ * wavefronts, so a second job on the same wavefront needs batches no model can follow.  This caps the grid of every launch
+ * of ctx (and of its stage contexts) whose kernel loops over its jobs, by the work queue or by a fixed stride, at `blocks`
+ * blocks, so that a few dozen frames reach the second, third and ragged last job.  Kernels with one thread per element and
+ * no loop keep their grid.  0 restores the library's own choice.  What a kernel computes per frame does not depend on it. */
+int polar_testing_resident_blocks(polar_ctx *ctx, int blocks);
+
+/* The most recent launch plan of a decoder kernel of ctx (plan_launch(), and the two fixed-stride BP launchers): its grid, its
+ * jobs (codewords, or groups of 2 / 4 / 64 of them), the jobs a block takes at a time, and whether the kernel was handed the
+ * work queue (jobs > grid * jobs_per_block on a kernel that uses it).  Adaptive CA-SCL copies the plan of a stage context here
+ * after each stage: a batch that ends at a stage leaves that stage's plan.  Any of the four pointers may be NULL. */
+int polar_testing_last_plan(const polar_ctx *ctx, int *grid, long long *jobs, int *jobs_per_block, int *queued);
+
+/* The most recent launch of ctx whose launcher sizes the grid itself for a kernel that loops by a fixed stride (k_bp_global,
+ * k_bp_readout, k_rm_recover, the generators, k_genie_rows, k_count_errors, the SC-Flip, adaptive and BPL glue): its grid and
+ * the blocks the work needs; need > grid means that the loop made a second trip.  Either pointer may be NULL. */
+int polar_testing_last_stride(const polar_ctx *ctx, int *grid, long long *need);
+
 /* The kernels' scalar arithmetic on caller-chosen operands, one thread per element, through the SAME device
  * functions the decoders inline (csrc/polar_math.h, csrc/polar_lut.h):
  *   op 0  chk(a, b)        compare chain, CHK of SCL_1024.c:343-374

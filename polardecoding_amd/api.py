@@ -443,6 +443,7 @@ class Decoder:
         self.scan_iters = None  # None: the library's default (4)
         self._bpl_graphs = None # None: the library's default list (min(n, 8) cyclic shifts)
         self._chunk_bytes = 0   # test-only cap of the chunked passes (testing.chunk_bytes); 0: the library's 256 MiB
+        self._resident_blocks = 0   # test-only cap of the resident grid (testing.resident_blocks); 0: the library's choice
         self._rm = (int(E), 1 if ibil else 0) if E is not None else None
         self._dyn = None
         if dyn is not None:
@@ -489,6 +490,9 @@ class Decoder:
         """Re-create this decoder's context inside another build of the library (polardecoding_amd/testing.py)."""
         if lib is self._lib:
             return
+        if (self._chunk_bytes or self._resident_blocks) and not hasattr(lib, "polar_testing_resident_blocks"):
+            raise PolarError("this decoder carries a test-only cap (testing.chunk_bytes / testing.resident_blocks): set it to 0 "
+                             "before moving the decoder into a library without the test entry points")
         self.close()
         self._lib = lib
         self._create()
@@ -512,6 +516,9 @@ class Decoder:
         if self._chunk_bytes:   # only a test library has the setter
             lib.polar_testing_chunk_bytes.argtypes = [C.c_void_p, C.c_size_t]
             self._check(lib.polar_testing_chunk_bytes(self._h, self._chunk_bytes), "polar_testing_chunk_bytes")
+        if self._resident_blocks:
+            lib.polar_testing_resident_blocks.argtypes = [C.c_void_p, C.c_int]
+            self._check(lib.polar_testing_resident_blocks(self._h, self._resident_blocks), "polar_testing_resident_blocks")
 
     @property
     def info_order(self):

@@ -76,6 +76,7 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
 
     polar_ctx *s0 = c->stage_ctx[0] ? c->stage_ctx[0] : c;
     if ((rc = decode_fixed(s0, d_in, in_is_f32, sigma, B, d_bits, d_pm, d_flags, s0->d_frozen))) return rc;
+    c->last_plan = s0->last_plan;   // a stage context's plan is read through its owner (polar_testing_last_plan)
     if (st[0] == 1 && (rc = polar_tu::ad_crc_check(c, d_bits, c->d_crc_tab, d_flags, B))) return rc;
     if (d_list) HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_list), st[0], B, c->stream));
     const uint32_t *cur_idx = nullptr, *cur_flags = d_flags;
@@ -92,6 +93,7 @@ int cascl_adaptive(polar_ctx *c, const void *d_in, int in_is_f32, double sigma, 
             if ((rc = decode_fixed(sc, c->ad_in.p, in_is_f32, sigma, nc, (uint32_t *)c->ad_bits.p,
                                    d_pm ? (double *)c->ad_pm.p : nullptr, sflags + off, sc->d_frozen)))
                 return rc;
+            c->last_plan = sc->last_plan;
             if ((rc = polar_tu::ad_scatter(c, (uint32_t *)c->ad_bits.p, (double *)c->ad_pm.p, sflags + off, idx + off, nc,
                                            d_bits, d_pm, d_flags, d_list, st[(size_t)s])))
                 return rc;

@@ -80,7 +80,7 @@ int polar_count_errors_device(polar_ctx *c, const uint32_t *d_uhat, const uint32
     }
     polar::CountParams P{d_uhat, d_u, c->d_info, d_counters, d_frame_err, c->NW, (int)B};
     const int waves_per_block = 4;
-    int grid = (int)std::min<size_t>((B + waves_per_block - 1) / waves_per_block, (size_t)c->num_cu * 8);
+    const int grid = stride_grid(c, (long long)((B + waves_per_block - 1) / waves_per_block), (long long)c->num_cu * 8);
     hipLaunchKernelGGL(polar::k_count_errors, dim3(grid), dim3(64 * waves_per_block), 0, c->stream, P);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
@@ -218,7 +218,7 @@ int polar_generate_device(polar_ctx *c, unsigned long long seed, unsigned long l
     if (c->is_dyn) return polar_tu::dyn_generate(c, P);                    // the dynamic bits filled in before the encode
     const int waves = 4;
     const size_t lds = (size_t)waves * (g.N + 2 * 1024);
-    int grid = (int)std::min<size_t>((B + waves - 1) / waves, (size_t)c->num_cu * 8);
+    const int grid = stride_grid(c, (long long)((B + waves - 1) / waves), (long long)c->num_cu * 8);
     hipLaunchKernelGGL(polar::k_generate, dim3(grid), dim3(64 * waves), lds, c->stream, P);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;

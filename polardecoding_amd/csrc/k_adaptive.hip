@@ -7,7 +7,7 @@ namespace {
 int grid_for(polar_ctx *c, long long items)
 {
     const long long blocks = (items + polar::AD_THREADS - 1) / polar::AD_THREADS;
-    return (int)std::max<long long>(1, std::min<long long>(blocks, (long long)c->num_cu * 16));
+    return stride_grid(c, blocks, (long long)c->num_cu * 16);
 }
 
 int log2i(long long v)

@@ -54,8 +54,8 @@ int launch_bp(polar_ctx *c, const polar::BpParams &P)
     if (lds > 160 * 1024) {   // messages do not fit a CU's LDS: rows in global scratch
         auto kg = stop ? polar::k_bp_global<R, IN, true> : polar::k_bp_global<R, IN>;
         const size_t lds_g = 4 * (size_t)(P.N / 32) * (stop ? 2 : 1) + (stop ? 16 : 0) + 16 + polar::Lut<R>::bytes;
-        int grid = (int)std::min<long long>((long long)P.B, (long long)2 * c->num_cu);
-        if (grid < 1) grid = 1;
+        const int grid = stride_grid(c, P.B, (long long)2 * c->num_cu);
+        record_plan(c, grid, P.B, 1, false);
         int rc = ensure(c, c->scratch, sizeof(R) * 2 * (size_t)(P.n + 1) * P.N * (size_t)grid);
         if (rc) return rc;
         hipLaunchKernelGGL(kg, dim3(grid), dim3(512), lds_g, c->stream, P, reinterpret_cast<R *>(c->scratch.p));
@@ -85,8 +85,8 @@ int launch_bp_readout(polar_ctx *c, const polar::BpReadoutParams &P)
     int occ = 0;
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, lds));
     if (occ < 1) occ = 1;
-    int grid = (int)std::min<long long>((long long)P.B, (long long)occ * c->num_cu);
-    if (grid < 1) grid = 1;
+    const int grid = stride_grid(c, P.B, (long long)occ * c->num_cu);
+    record_plan(c, grid, P.B, 1, false);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, c->stream, P);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;

@@ -7,7 +7,7 @@ namespace {
 int grid_for(polar_ctx *c, long long items)
 {
     const long long blocks = (items + polar::BPL_THREADS - 1) / polar::BPL_THREADS;
-    return (int)std::max<long long>(1, std::min<long long>(blocks, (long long)c->num_cu * 16));
+    return stride_grid(c, blocks, (long long)c->num_cu * 16);
 }
 
 }  // namespace

@@ -34,7 +34,7 @@ int polar_tu::dyn_generate(polar_ctx *c, const polar::GenParams &G)
     R.D = (int)c->dyn_pos.size();
     const int waves = 4;
     const size_t lds = (size_t)waves * (G.N + 2 * 1024);
-    const int grid = (int)std::min<size_t>(((size_t)G.B + waves - 1) / waves, (size_t)c->num_cu * 8);
+    const int grid = stride_grid(c, ((long long)G.B + waves - 1) / waves, (long long)c->num_cu * 8);
     hipLaunchKernelGGL(polar::k_generate_dyn, dim3(grid), dim3(64 * waves), lds, c->stream, R);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;

@@ -48,7 +48,7 @@ int polar_tu::genie_rows(polar_ctx *c, unsigned long long seed, unsigned long lo
     P.out = d_out; P.seed = seed; P.first_frame = first_frame; P.sigma = sigma;
     P.N = c->cfg.N; P.B = (int)B;
     const size_t pairs = B * (size_t)(P.N / 2);
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((pairs + 255) / 256, (size_t)c->num_cu * 16));
+    const int grid = stride_grid(c, (long long)((pairs + 255) / 256), (long long)c->num_cu * 16);
     if (out32) hipLaunchKernelGGL(polar::k_genie_rows<float>, dim3(grid), dim3(256), 0, c->stream, P);
     else hipLaunchKernelGGL(polar::k_genie_rows<double>, dim3(grid), dim3(256), 0, c->stream, P);
     HIP_TRY(c, hipGetLastError());

@@ -14,7 +14,7 @@ int launch_recover(polar_ctx *c, const polar::RmParams &P)
     int occ = 0;
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, polar::RM_THREADS, lds));
     if (occ < 1) occ = 1;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(P.B, (long long)occ * c->num_cu));
+    const int grid = stride_grid(c, P.B, (long long)occ * c->num_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(polar::RM_THREADS), lds, c->stream, P);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;
@@ -49,7 +49,7 @@ int polar_tu::rm_generate(polar_ctx *c, const polar::GenParams &G)
     R.E = c->rm_E; R.logS = log2i(c->cfg.N / 32); R.mode = c->rm_mode;
     const int waves = 4;
     const size_t lds = (size_t)waves * (G.N + 2 * 1024);
-    const int grid = (int)std::min<size_t>(((size_t)G.B + waves - 1) / waves, (size_t)c->num_cu * 8);
+    const int grid = stride_grid(c, ((long long)G.B + waves - 1) / waves, (long long)c->num_cu * 8);
     hipLaunchKernelGGL(polar::k_generate_rm, dim3(grid), dim3(64 * waves), lds, c->stream, R);
     HIP_TRY(c, hipGetLastError());
     return POLAR_OK;

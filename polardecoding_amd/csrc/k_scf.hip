@@ -56,7 +56,7 @@ int polar_tu::scf_resolve(polar_ctx *c, const uint32_t *d_pass, const uint32_t *
     int lw = 0;
     while ((1 << lw) < c->NW) ++lw;
     const long long items = (long long)n << lw;
-    const int grid = (int)std::max<long long>(1, std::min<long long>((items + 255) / 256, (long long)c->num_cu * 16));
+    const int grid = stride_grid(c, (items + 255) / 256, (long long)c->num_cu * 16);
     hipLaunchKernelGGL(polar::k_scf_resolve, dim3(grid), dim3(256), 0, c->stream, d_pass, d_pbits, d_idx, (long long)n, T, lw,
                        d_bits, d_flags, d_attempts);
     HIP_TRY(c, hipGetLastError());
@@ -71,7 +71,7 @@ int polar_tu::scf_resolve_sets(polar_ctx *c, const uint32_t *d_pass, const uint3
     int lw = 0;
     while ((1 << lw) < c->NW) ++lw;
     const long long items = (long long)n << lw;
-    const int grid = (int)std::max<long long>(1, std::min<long long>((items + 255) / 256, (long long)c->num_cu * 16));
+    const int grid = stride_grid(c, (items + 255) / 256, (long long)c->num_cu * 16);
     hipLaunchKernelGGL(polar::k_scf_resolve_sets, dim3(grid), dim3(256), 0, c->stream, d_pass, d_pbits, d_idx, (long long)n, T,
                        lw, d_sets_in, stride, width, base, d_bits, d_flags, d_attempts, d_sets, d_slot_pass);
     HIP_TRY(c, hipGetLastError());
@@ -83,7 +83,7 @@ int polar_tu::scf_merge(polar_ctx *c, bool r32, const void *d_lkey, const uint16
                         uint16_t *d_out_sets, uint32_t *d_idx_out)
 {
     if (n == 0) return POLAR_OK;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(((long long)n + 255) / 256, (long long)c->num_cu * 16));
+    const int grid = stride_grid(c, ((long long)n + 255) / 256, (long long)c->num_cu * 16);
     if (r32)
         hipLaunchKernelGGL(polar::k_scf_merge<float>, dim3(grid), dim3(256), 0, c->stream, (const float *)d_lkey, d_lpos, d_lcnt,
                            d_psets, d_surv, d_idx_in, (long long)n, Tk, Tn, d_out_sets, d_idx_out);

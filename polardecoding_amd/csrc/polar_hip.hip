@@ -202,6 +202,7 @@ void sync_stage_ctx(polar_ctx *c)
         s->use_fast4 = c->use_fast4;
         s->big_split = c->big_split;
         s->chunk_bytes = c->chunk_bytes;
+        s->resident_blocks = c->resident_blocks;
     }
 }
 
@@ -762,6 +763,32 @@ int polar_testing_chunk_bytes(polar_ctx *c, size_t bytes)
 {
     if (!c) return POLAR_EINVAL;
     c->chunk_bytes = bytes ? bytes : kChunkBytes;
+    return POLAR_OK;
+}
+
+int polar_testing_resident_blocks(polar_ctx *c, int blocks)
+{
+    if (!c || blocks < 0) return POLAR_EINVAL;
+    c->resident_blocks = blocks;
+    sync_stage_ctx(c);
+    return POLAR_OK;
+}
+
+int polar_testing_last_plan(const polar_ctx *c, int *grid, long long *jobs, int *jobs_per_block, int *queued)
+{
+    if (!c) return POLAR_EINVAL;
+    if (grid) *grid = c->last_plan.grid;
+    if (jobs) *jobs = c->last_plan.jobs;
+    if (jobs_per_block) *jobs_per_block = c->last_plan.jobs_per_block;
+    if (queued) *queued = c->last_plan.queued;
+    return POLAR_OK;
+}
+
+int polar_testing_last_stride(const polar_ctx *c, int *grid, long long *need)
+{
+    if (!c) return POLAR_EINVAL;
+    if (grid) *grid = c->last_stride.grid;
+    if (need) *need = c->last_stride.need;
     return POLAR_OK;
 }
 #endif  // POLAR_TESTING

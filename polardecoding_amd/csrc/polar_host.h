@@ -129,6 +129,17 @@ struct polar_ctx : Lane {
     bool force_spill = false;   // no tuned L = 8 kernel; with force_generic: the global-scratch variant of k_scl_generic
     int big_split = 0;          // 35 | 46 | 57: LDS / scratch split of k_scl_big; 0 = the measured best
     size_t chunk_bytes = kChunkBytes;   // bytes of rows per pass of the chunked loops (chunk_rows, polar_hip.hip)
+    int resident_blocks = 0;    // at most this many blocks per launch (cap_grid below); 0: the launcher's own choice
+    struct {
+        int grid;
+        long long jobs;
+        int jobs_per_block;
+        int queued;
+    } last_plan{};              // what record_plan() saw last (polar_testing_last_plan)
+    struct {
+        int grid;
+        long long need;
+    } last_stride{};            // what stride_grid() saw last (polar_testing_last_stride)
     // list output (polar_list_decode): the D = 0 constraint tables a ctx without dynamic bits runs k_scl_list with
     // (row = -1 at every leaf, one zero mask row), built on first use; staging of polar_list_decode_host
     DevMem<uint32_t> d_list_mask;
@@ -223,6 +234,32 @@ inline int work_queue(polar_ctx *c, Buf &scratch, unsigned **counter)
     return POLAR_OK;
 }
 
+// The test-only cap on the resident grid (include/polar_hip_testing.h, polar_testing_resident_blocks): every launcher whose
+// kernel loops over its jobs, by the work queue (plan_launch) or by a fixed stride (stride_grid), passes its grid through
+// here, so that a few dozen frames reach a wavefront's second and later jobs.  Launchers with one thread per element and no loop (k_q8_quantize,
+// k_q8_pm_f64, the encoder kernels, k_list_select / k_list_gather, the compaction of adaptive CA-SCL) do not.
+inline long long cap_grid(const polar_ctx *c, long long grid)
+{
+    if (c->resident_blocks) grid = std::min<long long>(grid, c->resident_blocks);
+    return std::max<long long>(grid, 1);
+}
+
+// Grid of a launcher that sizes it itself for a kernel that loops by a fixed stride: the `need` blocks of the work, at most
+// `limit` (what the launcher allows itself) and at most the cap; kept for polar_testing_last_stride (need > grid: the loop
+// makes a second trip)
+inline int stride_grid(polar_ctx *c, long long need, long long limit)
+{
+    const long long grid = cap_grid(c, std::min(need, limit));
+    c->last_stride = {(int)grid, need};
+    return (int)grid;
+}
+
+// The plan of a decoder kernel's launch, kept for polar_testing_last_plan
+inline void record_plan(polar_ctx *c, long long grid, long long jobs, int jobs_per_block, bool queued)
+{
+    c->last_plan = {(int)grid, jobs, jobs_per_block, queued ? 1 : 0};
+}
+
 // Launch of a persistent kernel: as many blocks as are resident at once (or as the jobs need, if fewer), each block's
 // slice of c->scratch, and the work queue when there are more jobs than the resident blocks take by their index.  A
 // k_*.hip launcher states what is particular to its kernel in a LaunchShape; plan_launch() does the rest.
@@ -253,7 +290,9 @@ inline int plan_launch(polar_ctx *c, const void *kern, const LaunchShape &s, Lau
     if (s.occ_cap && occ > s.occ_cap) occ = s.occ_cap;
     long long grid = std::min<long long>((s.jobs + s.jobs_per_block - 1) / s.jobs_per_block, (long long)occ * c->num_cu);
     if (s.grid_cap) grid = std::min(grid, s.grid_cap);
-    if (grid < 1) grid = 1;
+    grid = cap_grid(c, grid);
+    const bool queued = s.use_queue && s.jobs > grid * s.jobs_per_block;
+    record_plan(c, grid, s.jobs, s.jobs_per_block, queued);
     *out = LaunchPlan{(int)grid, nullptr, nullptr};
     if (s.scratch_per_block) {
         const size_t bytes = s.scratch_per_block * (size_t)grid;
@@ -261,7 +300,7 @@ inline int plan_launch(polar_ctx *c, const void *kern, const LaunchShape &s, Lau
         if (rc) return rc;
         out->scratch = c->scratch.p;
     }
-    if (s.use_queue && s.jobs > grid * s.jobs_per_block) return work_queue(c, c->scratch, &out->queue);
+    if (queued) return work_queue(c, c->scratch, &out->queue);
     return POLAR_OK;
 }
 

@@ -46,6 +46,46 @@ def chunk_bytes(dec, nbytes):
     return dec
 
 
+def resident_blocks(dec, blocks):
+    """The cap on the resident grid (polar_testing_resident_blocks): every launch of dec whose kernel loops over its jobs
+    starts at most `blocks` blocks, so a few dozen frames reach a wavefront's later jobs.  0 restores the library's choice.
+    The decoder keeps the cap across a later rebind."""
+    lib = load_library(testing=True)
+    dec._rebind(lib)
+    lib.polar_testing_resident_blocks.argtypes = [C.c_void_p, C.c_int]
+    rc = lib.polar_testing_resident_blocks(dec._h, int(blocks))
+    if rc != 0:
+        raise PolarError(f"polar_testing_resident_blocks rc={rc}")
+    dec._resident_blocks = int(blocks)
+    return dec
+
+
+def last_plan(dec):
+    """(grid, jobs, jobs_per_block, queued) of dec's most recent decoder-kernel launch (polar_testing_last_plan)."""
+    lib = load_library(testing=True)
+    dec._rebind(lib)
+    lib.polar_testing_last_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int)]
+    g, j, p, q = C.c_int(), C.c_longlong(), C.c_int(), C.c_int()
+    rc = lib.polar_testing_last_plan(dec._h, C.byref(g), C.byref(j), C.byref(p), C.byref(q))
+    if rc != 0:
+        raise PolarError(f"polar_testing_last_plan rc={rc}")
+    return g.value, j.value, p.value, q.value
+
+
+def last_stride(dec):
+    """(grid, blocks the work needs) of dec's most recent fixed-stride launch that sizes its own grid
+    (polar_testing_last_stride)"""
+    lib = load_library(testing=True)
+    dec._rebind(lib)
+    lib.polar_testing_last_stride.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    g, n = C.c_int(), C.c_longlong()
+    rc = lib.polar_testing_last_stride(dec._h, C.byref(g), C.byref(n))
+    if rc != 0:
+        raise PolarError(f"polar_testing_last_stride rc={rc}")
+    return g.value, n.value
+
+
 def math(op, a, b, dtype=np.float64, device=0):
     """The device functions of csrc/polar_math.h / polar_lut.h applied element-wise on the GPU."""
     lib = load_library(testing=True)
