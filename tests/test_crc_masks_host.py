@@ -26,6 +26,11 @@ CODES = [
     ("r11", 1024, 512, [0, 5, 9, 10, 11]),           # CRC-11 of 5G NR: D^11 + D^10 + D^9 + D^5 + 1
     ("crc24c_k128", 1024, 128, list(O.CRC24C_TAPS)),
     ("crc24c_k896", 1024, 896, list(O.CRC24C_TAPS)),
+    ("r16", 1024, 480, [0, 5, 12, 16]),              # CRC-16: D^16 + D^12 + D^5 + 1
+    ("r25", 1024, 480, [0, 3, 25]),                  # past CRC-24C: rows = 28 of the pair kernel's mask loop
+    ("r31", 1024, 480, [0, 3, 31]),
+    ("r32", 1024, 480, [0, 1, 2, 4, 5, 7, 8, 10, 11, 12, 16, 22, 23, 26, 32]),   # CRC-32: every mask row, bit 31 of the table
+    ("r32_n128", 128, 33, [0, 1, 2, 4, 5, 7, 8, 10, 11, 12, 16, 22, 23, 26, 32]),
 ]
 
 

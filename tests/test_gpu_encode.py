@@ -21,6 +21,7 @@ import test_rm_host as R  # noqa: E402
 
 F64, F32 = 0, 1
 FLAG_CRC_PASS = 0x2
+CRC32 = (0, 1, 2, 4, 5, 7, 8, 10, 11, 12, 16, 22, 23, 26, 32)
 
 
 def _cuda(x):
@@ -58,6 +59,8 @@ def _make(name):
         return pa.CASCL(128, 64, L=8, crc_taps=pa.CRC6_TAPS, systematic=True), None
     if name == "cascl1024":
         return pa.CASCL(1024, 500, L=8, crc_taps=pa.CRC24C_TAPS), None
+    if name == "cascl128-crc32":   # r = 32: the tap-32 branch, a shift by a whole word
+        return pa.CASCL(128, 33, L=8, crc_taps=CRC32), None
     if name == "cascl1024-syscrc":
         return pa.CASCL(1024, 500, L=8, crc_taps=pa.CRC24C_TAPS, systematic=True), None
     if name == "scl4096":
@@ -162,7 +165,7 @@ def test_encode_equals_the_model(name, B):
 
 
 @pytest.mark.parametrize("name", ["cascl128", "cascl128-syscrc", "cascl1024", "pac128", "pc64", "rm-repeat", "rm-puncture",
-                                  "rm-shorten"])
+                                  "rm-shorten", "cascl128-crc32"])
 def test_encode_reproduces_the_generator(name):
     import torch
     dec, _ = _make(name)
