@@ -40,6 +40,10 @@ struct Fast2Cfg {
     // f32 keeps the rows in element order and one access per element: the permuted order measured 1.4 % slower there,
     // with 8-byte paired accesses and without
     static constexpr bool PAIRED = sizeof(R) == 8;
+    // from_top() reads its partial-sum words once per eight passes and keeps them in registers.  f64 only: in f32, at
+    // 128 VGPRs, the twelve words cost 4 to 18 more spilled registers and the kernel measured slower (DESIGN.md 4.0,
+    // round 22)
+    static constexpr bool TOP_WORDS_ONCE = sizeof(R) == 8;
     // block-shared LDS
     static constexpr size_t off_lut = 0;
     static constexpr size_t off_frz = off_lut + ((Lut<R>::bytes + 15) / 16) * 16;
@@ -278,11 +282,25 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         R *pre = A + 4;    // levels 2..5 are dead during this step (recomputed below): reuse their registers
 #pragma unroll
         for (int m = 0; m < 8; ++m) pre[m] = (m < nld) ? top_src(right, w32 + 32 * m, 0) : R(0);
+        // the step's partial-sum words, shifted to the lane's bits.  Pass rr reads word wq = rr >> 3 of each, so with
+        // TOP_WORDS_ONCE they are read once per eight passes (two chunks), else in every pass
+        uint32_t wt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wh[4] = {0, 0, 0, 0};
         for (int q = 0; q < 4; ++q) {
             lds_fence();
 #pragma unroll
             for (int m = 0; m < 8; ++m)
                 if (m < nld) stg[w32 + 32 * m] = pre[m];
+            if (C::TOP_WORDS_ONCE && (q & 1) == 0) {
+                const int wq = q >> 1;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (right) {
+                        wt[k] = bt[2 * k + wq] >> pos;
+                        wt[4 + k] = bt[8 + 2 * k + wq] >> pos;
+                    }
+                    if (gstep) wh[k] = bh[2 * k + wq] >> pos;
+                }
+            }
             lds_fence();
             if (q < 3) {
 #pragma unroll
@@ -300,14 +318,15 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
                 for (int k = 0; k < 4; ++k) {
                     R x, y;
                     if (right) {
-                        const uint32_t w0 = bt[2 * k + wq] >> pos, w1 = bt[8 + 2 * k + wq] >> pos;
+                        const uint32_t w0 = C::TOP_WORDS_ONCE ? wt[k] : bt[2 * k + wq] >> pos;
+                        const uint32_t w1 = C::TOP_WORDS_ONCE ? wt[4 + k] : bt[8 + 2 * k + wq] >> pos;
                         x = g_bit<R>(stg[(k + 0) * 16 + wi], stg[(k + 8) * 16 + wi], w0, sh);    // ch[e], ch[e+512]
                         y = g_bit<R>(stg[(k + 4) * 16 + wi], stg[(k + 12) * 16 + wi], w1, sh);   // ch[e+256], ch[e+768]
                     } else {
                         x = stg[(k + 0) * 16 + wi];   // tl[e]
                         y = stg[(k + 4) * 16 + wi];   // tl[e+256]
                     }
-                    if (gstep) v8[k] = g_bit<R>(x, y, bh[2 * k + wq] >> pos, sh);
+                    if (gstep) v8[k] = g_bit<R>(x, y, C::TOP_WORDS_ONCE ? wh[k] : bh[2 * k + wq] >> pos, sh);
                     else v8[k] = chk(x, y);
                     o8[s0 + 64 * k] = v8[k];   // element e0 + 64 k
                 }
@@ -868,16 +887,6 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
     // either way, it never prunes trivially, and c0 == c1 in the ranking).  T(|s|), T(|d|) are the staircase values the
     // odd leaf's PHI needs.  So inside an octet every g step and every second table look-up is a by-product.
     struct ChkBp { R v, s, d, ts, td; };
-    __device__ __forceinline__ ChkBp chk_bp(R x, R y) const
-    {
-        ChkBp r;
-        r.s = x + y;
-        r.d = x - y;
-        r.ts = lut.tabv(r.s);
-        r.td = lut.tabv(r.d);
-        r.v = xor_sign(minabs(x, y), x, y) + (r.ts - r.td);
-        return r;
-    }
     // s or -d by the partner bit at position sh of w.  The selects of the by-product g steps go by sign mask + v_bfi_b32
     // rather than v_cmp + v_cndmask: +-0 while the wavefronts took their jobs by a fixed stride
     // (profiles/r03_ab_experiments.txt run 24), + 1.3 % since the work queue (run 34).
@@ -887,10 +896,36 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
         const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)w, sh, 1);
         return Lut<R>::sel_mask(m, -dif, sum);
     }
+    // The node itself.  Only the lower lane of each pair (lane, lane ^ B) is read: B = 1 at level 0 (QP = 0xB1, data in
+    // pos 0), B = 2 at level 1 (QP = 0x4E, data in pos 0, 1).  The upper lane holds the partner operand and would look up
+    // values nobody reads, so it takes the lower lane's second look-up instead: with the sign of ITS partner flipped, the
+    // one addition gives s = x + y in the lower lane and y - x = -d in the upper one, and T(|-d|) is T(|d|) bit for bit
+    // (tabv() reads exponent and mantissa bits and compares |.|).  One tabv() then serves both; the lower lane takes
+    // T(|d|) from its neighbour.  In the lower lane the flip is zero, so x, y, s, d, v and both table values there are
+    // those of two look-ups in the lane; d is computed in the lane, never taken from the neighbour (-0 for +0).
+    // (-12 LDS and -24 VALU instructions per octet.)
+    static __device__ __forceinline__ double flip_sign(double y, uint32_t m) { return __hiloint2double(__double2hiint(y) ^ (int)m, __double2loint(y)); }
+    static __device__ __forceinline__ float flip_sign(float y, uint32_t m) { return __int_as_float(__float_as_int(y) ^ (int)m); }
+    template <int QP>
+    __device__ __forceinline__ ChkBp chk_narrow(R x) const
+    {
+        static_assert(QP == 0xB1 || QP == 0x4E, "partner in lane ^ 1 or lane ^ 2");
+        // the sign bit in the upper lane of a pair: the compiler keeps it as a lane constant per level and folds the flip
+        // into the partner's DPP move (v_xor_b32 with a DPP source)
+        const uint32_t up = QP == 0xB1 ? (uint32_t)pos << 31 : ((uint32_t)pos << 30) & 0x80000000u;
+        const R y = flip_sign(quadp<QP>(x), up);
+        ChkBp r;
+        r.s = x + y;
+        r.d = x - y;
+        r.ts = lut.tabv(r.s);
+        r.td = quadp<QP>(r.ts);
+        r.v = xor_sign(minabs(x, y), x, y) + (r.ts - r.td);
+        return r;
+    }
     template <int K, bool FULL>   // leaves K (even) and K + 1 from the level-1 pair in a1 (pos 0: x, pos 1: y)
     __device__ __forceinline__ void leaf_pair(int o, uint32_t fm, R x1)
     {
-        const ChkBp q = chk_bp(x1, quadp<0xB1>(x1));
+        const ChkBp q = chk_narrow<0xB1>(x1);
         bp_d = q.d;
         bp_td = q.td;
         decide<K, FULL>(o, (fm >> K) & 1, q.v);
@@ -908,24 +943,20 @@ struct Fast2Dec : Fast2Sigma<FROM_Y> {
             const R v2 = xor_sign(minabs(A[2], A[3]), A[2], A[3]) + (lut.tabv(s2) - lut.tabv(d2));
             A[2] = s2;
             A[3] = d2;
-            // level 1: f; sum / difference in (A[1], a1) for the g steps at leaves 2 and 6
-            const R y2 = quadp<0x4E>(v2);
-            const R s1 = v2 + y2, d1 = v2 - y2;
-            const R v1 = xor_sign(minabs(v2, y2), v2, y2) + (lut.tabv(s1) - lut.tabv(d1));
-            A[1] = s1;
-            a1 = d1;
-            leaf_pair<0, FULL>(o, fm, v1);
+            // level 1: f; sum / difference in (A[1], a1) for the g steps at leaves 2 and 6 (read at pos 0, 1)
+            const ChkBp q1 = chk_narrow<0x4E>(v2);
+            A[1] = q1.s;
+            a1 = q1.d;
+            leaf_pair<0, FULL>(o, fm, q1.v);
         }
         // the partner sums of the g steps come from the octet's raw bits (bits 0..7 of bl0) where they are read
         leaf_pair<2, FULL>(o, fm, g_sel(A[1], a1, octet_bits::level1_lo(bl0), pos));
         {
             const R v2 = g_sel(A[2], A[3], octet_bits::level2(bl0), pos);   // level 2, g
-            const R y2 = quadp<0x4E>(v2);
-            const R s1 = v2 + y2, d1 = v2 - y2;
-            const R v1 = xor_sign(minabs(v2, y2), v2, y2) + (lut.tabv(s1) - lut.tabv(d1));
-            A[1] = s1;
-            a1 = d1;
-            leaf_pair<4, FULL>(o, fm, v1);
+            const ChkBp q1 = chk_narrow<0x4E>(v2);
+            A[1] = q1.s;
+            a1 = q1.d;
+            leaf_pair<4, FULL>(o, fm, q1.v);
         }
         leaf_pair<6, FULL>(o, fm, g_sel(A[1], a1, octet_bits::level1_hi(bl0), pos));
     }
