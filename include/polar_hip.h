@@ -138,7 +138,20 @@ int polar_decode_batch_y(polar_ctx *ctx, const double *y, double sigma, size_t B
 /* --- batched, device buffers (the measured path; asynchronous on the ctx stream) ---------------------
  * d_in: [B][N] of double (in_is_f32 = 0) or float (in_is_f32 = 1), LLRs, or y when sigma > 0.
  * d_uhat_bits: [B][N/32] uint32, bit (j & 31) of word j >> 5 = u_hat[j].
- * d_pm (nullable): [B] double.  d_flags (nullable): [B] uint32. */
+ * d_pm (nullable): [B] double.  d_flags (nullable): [B] uint32.
+ * Input rows -- the one rule for every entry point that takes `d_in, in_is_f32` (each refers to this paragraph).  With R the
+ * arithmetic type of the ctx (cfg.dtype) and row the frame's N values, the decoder works on
+ *     v = (double)row[i];  if (sigma > 0) v = 2 * v / sigma / sigma;  working value = (R)v
+ * for every i: the conversion and both divisions are done in double, in that order (SCL_1024.c:576), and the result is rounded
+ * once to R.  A float row on an F64 ctx is therefore exact, a double row on an F32 ctx is rounded once, and a y row is never
+ * scaled in float.  (A Q8 ctx quantises v instead: rule 1 of its section.)
+ * d_in needs the alignment of its element type only (4 bytes for float, 8 for double): rows need not start on a 16-byte
+ * boundary, and a kernel that reads several elements at once does so only after testing the address.  No result depends on
+ * anything outside the B rows.
+ * The kernel that runs may depend on in_is_f32, while the result obeys the rule above all the same: an F64 ctx with L = 8 on
+ * float rows does not run its tuned kernel but k_scl_big<double, float> at N = 1024 (instead of k_scl_fast2) and
+ * k_scl_generic<double, float> at N = 128 (instead of k_scl_fast); polar_kernel_name names the kernel for rows of the ctx's own
+ * type.  tests/input_forms.py lists a case per kernel, tests/test_gpu_input_forms.py holds each to the rule. */
 int polar_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                         uint32_t *d_uhat_bits, double *d_pm, uint32_t *d_flags);
 
@@ -172,7 +185,8 @@ int polar_stop_rule_batch_y(polar_ctx *ctx, const double *y, double sigma, const
  * iteration counts checkpoints[0..ncp) (ascending, <= 8; the program uses 3, 6, 10, 20, 40, 80, :18-23) the hard
  * decisions of l + r at every stage i = 0..n are carried back to the u side and compared with the sent bits on the
  * information set; d_E[c*(n+1) + i] accumulates the mismatches over the B frames (the program's E[c][i], :437).
- * d_u_bits: [B][N/32] sent bits; d_uhat_bits (may be NULL): [B][N/32] final decisions.  N <= 512 (f64), 1024 (f32). */
+ * d_u_bits: [B][N/32] sent bits; d_uhat_bits (may be NULL): [B][N/32] final decisions.  N <= 512 (f64), 1024 (f32).
+ * d_in: "Input rows" at polar_decode_device. */
 int polar_bp_readout_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                             const uint32_t *d_u_bits, const int *checkpoints, int ncp, unsigned long long *d_E,
                             uint32_t *d_uhat_bits);
@@ -202,7 +216,8 @@ int polar_bp_readout_batch(polar_ctx *ctx, const double *in, double sigma, size_
 /* POLAR_EINVAL: not a BP ctx, or an unknown rule */
 int polar_bp_set_stop(polar_ctx *ctx, int rule);
 /* polar_decode_device for a BP ctx, plus per frame: d_iters (nullable) [B] round trips run, d_flags (nullable) [B]
- * POLAR_FLAG_BP_CONVERGED or 0.  With POLAR_BP_STOP_NONE d_iters is filled with iterMax and d_flags with 0. */
+ * POLAR_FLAG_BP_CONVERGED or 0.  With POLAR_BP_STOP_NONE d_iters is filled with iterMax and d_flags with 0.  d_in: "Input rows"
+ * at polar_decode_device. */
 int polar_bp_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                            uint32_t *d_uhat_bits, uint32_t *d_iters, uint32_t *d_flags);
 /* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N], iters / flags (nullable) [B]. */
@@ -230,7 +245,8 @@ int polar_bp_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int *u
 /* POLAR_EINVAL: not a CA-SCL ctx, or a malformed list.  n = 0 restores the default. */
 int polar_cascl_set_stages(polar_ctx *ctx, const int *stages, int n);
 /* polar_decode_device for a CA-SCL ctx, plus per frame d_list (nullable) [B]: the list size of the stage that decided it
- * (1 for SC; cfg.L without a rule).  d_pm, d_flags, d_list are nullable. */
+ * (1 for SC; cfg.L without a rule).  d_pm, d_flags, d_list are nullable.  d_in: "Input rows" at polar_decode_device; a later
+ * stage reads the rows of its frames from d_in again. */
 int polar_cascl_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                               uint32_t *d_uhat_bits, double *d_pm, uint32_t *d_flags, uint32_t *d_list);
 /* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N]; pm, flags, list (nullable) [B]. */
@@ -264,7 +280,8 @@ int polar_cascl_decode_batch(polar_ctx *ctx, const double *llr_in, size_t B, int
  * not an SCF ctx, or T out of range. */
 int polar_scf_set_flips(polar_ctx *ctx, int T);
 /* polar_decode_device for an SCF ctx, plus per frame d_attempts (nullable) [B]: the attempt that decided it (0 = plain SC;
- * T when no attempt passed).  d_flags and d_attempts are nullable. */
+ * T when no attempt passed).  d_flags and d_attempts are nullable.  d_in: "Input rows" at polar_decode_device; every attempt
+ * reads its frame's row from d_in. */
 int polar_scf_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                             uint32_t *d_uhat_bits, uint32_t *d_flags, uint32_t *d_attempts);
 /* Host-buffer form: llr_in [B][N] LLRs, u_hat [B][N]; flags, attempts (nullable) [B]. */
@@ -319,7 +336,7 @@ int polar_scf_set_dynamic(polar_ctx *ctx, const int *budgets, int omega, double 
 int polar_scf_get_dynamic(const polar_ctx *ctx, int *omega, int *budgets, double *c, double *tau);
 /* polar_scf_decode_device plus d_sets (nullable) [B][3]: the reported set in ascending order, -1 padded (all -1: attempt 0
  * is the output).  On a static ctx it holds at most one entry, the flipped position.  d_flags, d_attempts and d_sets are
- * nullable. */
+ * nullable.  d_in: "Input rows" at polar_decode_device. */
 int polar_scf_decode_sets_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                                  uint32_t *d_uhat_bits, uint32_t *d_flags, uint32_t *d_attempts, int32_t *d_sets);
 /* Host-buffer form: sets (nullable) [B][3]. */
@@ -368,7 +385,8 @@ int polar_scf_decode_sets_batch(polar_ctx *ctx, const double *llr_in, size_t B, 
 /* I: 1 <= I <= 64; default 4.  POLAR_EINVAL (ctx unchanged): not a SCAN ctx, or I out of range. */
 int polar_scan_set_iters(polar_ctx *ctx, int I);
 /* d_uhat_bits [B][N/32], d_llr_u and d_ext_x [B][N] of the ctx dtype (double or float); each of the three may be NULL.
- * Asynchronous on the ctx stream, no host read-back: after a warm-up at the same B it can be captured into a graph. */
+ * Asynchronous on the ctx stream, no host read-back: after a warm-up at the same B it can be captured into a graph.
+ * d_in: "Input rows" at polar_decode_device. */
 int polar_scan_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                              uint32_t *d_uhat_bits, void *d_llr_u, void *d_ext_x);
 /* Host-buffer form: llr_in [B][N] LLRs (E per row on a rate-matched ctx); u_hat [B][N], llr_u and ext_x [B][N] of the ctx
@@ -427,7 +445,8 @@ int polar_bpl_get_graphs(const polar_ctx *ctx, int *P, int *perms);
 /* the cyclic shifts out[s][b] = (b + s) mod n, s = 0 .. P-1; 5 <= n <= 12, 1 <= P <= 32.  Host only. */
 int polar_bpl_cyclic_graphs(int n, int P, int *out);
 /* polar_decode_device for a BPL ctx, plus per frame ([B] uint32 each): d_iters and d_flags of rule 6, d_graph of rule 5
- * and d_total_iters of rule 6.  d_iters, d_flags, d_graph and d_total_iters are nullable. */
+ * and d_total_iters of rule 6.  d_iters, d_flags, d_graph and d_total_iters are nullable.  d_in: "Input rows" at
+ * polar_decode_device; a permuted attempt gathers the elements of a row one by one. */
 int polar_bpl_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_uhat_bits,
                             uint32_t *d_iters, uint32_t *d_flags, uint32_t *d_graph, uint32_t *d_total_iters);
 /* Host-buffer form: llr_in [B][N] LLRs (E per row on a rate-matched ctx), u_hat [B][N]; iters, flags, graph, total_iters
@@ -489,7 +508,8 @@ int polar_create_rm(const polar_cfg *cfg, int E, int ibil, polar_ctx **out);
 /* E, POLAR_RM_* mode and ibil of a ctx (each nullable); a plain ctx reports E = N, POLAR_RM_NONE, 0. */
 int polar_rm_info(const polar_ctx *ctx, int *E, int *mode, int *ibil);
 /* rule 6 on the ctx stream: d_in [B][E] double (in_is_f32 = 0) or float, LLRs or y when sigma > 0 -> d_out [B][N] of the
- * same type.  POLAR_EINVAL on a ctx not made by polar_create_rm. */
+ * same type.  POLAR_EINVAL on a ctx not made by polar_create_rm.  Alignment and the y form as in "Input rows" at
+ * polar_decode_device; the type the sums are rounded to is rule 6's. */
 int polar_rm_recover_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, void *d_out);
 
 /* --- Monte-Carlo code construction: genie-aided SC on the device (Arikan 2009, section IX) ---------------------------
@@ -517,7 +537,8 @@ int polar_rm_recover_device(polar_ctx *ctx, const void *d_in, int in_is_f32, dou
  * Out of scope: Gaussian-approximation / density-evolution construction, soft statistics (sums of 1/(1+e^lambda): float
  * sums depend on order), rate-matched construction, polar_group_* wrappers (counters add, so a caller can shard frames over
  * GPUs by first_frame and sum). */
-/* rules 1-2 on caller rows d_in [B][N] (double, or float when in_is_f32; LLRs, or y when sigma > 0) */
+/* rules 1-2 on caller rows d_in [B][N] (double, or float when in_is_f32; LLRs, or y when sigma > 0: "Input rows" at
+ * polar_decode_device) */
 int polar_genie_count_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint64_t *d_counts);
 /* rule 3: d_out [B][N] double, or float when out_is_f32 */
 int polar_genie_rows_device(polar_ctx *ctx, unsigned long long seed, unsigned long long first_frame, double sigma, size_t B,
@@ -742,8 +763,8 @@ int polar_fill_phase_end(int N, const int *info_order, int A);
  * Names: the four calls on device pointers are polar_list_decode, _select, _gather and _soft; polar_list_decode_host is the
  * host-buffer form of the first.  Their output extents (guard words around every output at ragged batches, NULL outputs) are
  * held by tests/test_gpu_list.py. */
-/* d_in as polar_decode_device ([B][E] on a rate-matched ctx).  Outputs, each nullable but not all: d_paths [B][L][N/32],
- * d_pm [B][L], d_rem [B][L], d_count [B], d_flags [B]. */
+/* d_in as polar_decode_device ("Input rows" there; [B][E] on a rate-matched ctx).  Outputs, each nullable but not all:
+ * d_paths [B][L][N/32], d_pm [B][L], d_rem [B][L], d_count [B], d_flags [B]. */
 int polar_list_decode(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, uint32_t *d_paths,
                       double *d_pm, uint32_t *d_rem, uint32_t *d_count, uint32_t *d_flags);
 /* host-buffer form: llr_in [B][N] ([B][E]), paths [B][L][N] ints 0/1, pm and rem [B][L], count and flags [B]; each output
@@ -880,7 +901,8 @@ int polar_q8_set_quant(polar_ctx *ctx, double scale, int qc, int qi);
 int polar_q8_get_quant(const polar_ctx *ctx, double *scale, int *qc, int *qi);   /* each output nullable */
 /* rule 1 on n host values.  Host only, touches no device.  POLAR_EINVAL: scale or qc out of range, a NaN sigma. */
 int polar_q8_quantize_host(const double *in, size_t n, double sigma, double scale, int qc, int8_t *out);
-/* rule 1 with the ctx's quantiser, asynchronous on the ctx stream: d_in [B][N] double (in_is_f32 = 0) or float -> d_out [B][N] */
+/* rule 1 with the ctx's quantiser, asynchronous on the ctx stream: d_in [B][N] double (in_is_f32 = 0) or float -> d_out [B][N].
+ * Alignment and the y form as in "Input rows" at polar_decode_device; rule 1 takes the place of the rounding to R. */
 int polar_q8_quantize_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B, int8_t *d_out);
 /* rules 2-6 on quantised rows d_q [B][N] (4-byte aligned).  Asynchronous on the ctx stream, no read-back: after a warm-up at
  * the same B it can be captured into a graph.  d_uhat_bits [B][N/32]; d_pm (nullable) [B] int32; d_flags (nullable) [B]. */
@@ -951,7 +973,8 @@ void *polar_get_stream(polar_ctx *ctx);
 int polar_synchronize(polar_ctx *ctx);
 
 /* Time `reps` launches of the decode kernel on B resident frames with HIP events on the ctx stream
- * (bench.py's roofline leg).  Returns average milliseconds per launch in *ms_per_launch. */
+ * (bench.py's roofline leg).  Returns average milliseconds per launch in *ms_per_launch.  d_in: "Input rows" at
+ * polar_decode_device. */
 int polar_time_decode_device(polar_ctx *ctx, const void *d_in, int in_is_f32, double sigma, size_t B,
                              uint32_t *d_uhat_bits, int reps, float *ms_per_launch);
 
