@@ -456,6 +456,12 @@ class Decoder:
             didx = np.ascontiguousarray(np.concatenate(sets + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
             self._dyn = (dpos, dptr, didx)
         self._create()
+        if crc_file is not None:
+            # g(D) lives only inside polar_create_crc_file: every other consumer of the cfg (polar_group_create,
+            # polar_fer_multi_gpu) must see it too
+            ftaps = np.asarray(load_crc_matrix(crc_file)[0], dtype=np.int32)
+            cfg.crc_r, cfg.crc_taps, cfg.n_taps = int(ftaps.max()), _ptr(ftaps, C.c_int), int(ftaps.size)
+            self._cfg_keep = (ftaps, io)
         A, Lr = C.c_int(), C.c_int()
         self._lib.polar_ctx_info(self._h, None, None, C.byref(A), C.byref(Lr), None, None)
         self.A, self.L = A.value, Lr.value
