@@ -781,6 +781,57 @@ int polar_list_gather(polar_ctx *ctx, const uint32_t *d_paths, const int32_t *d_
 int polar_list_soft(polar_ctx *ctx, const uint32_t *d_paths, const double *d_pm, const uint32_t *d_count,
                     const uint32_t *d_rem, uint32_t want_rem, int domain, double clamp, size_t B, double *d_out);
 
+/* --- Sent-path trace: where the list loses the sent word (no reference counterpart) ----------------------------------------
+ * A list decoder ends a frame correct (the sent word is in the list and is chosen), with a selection error (it is in the list,
+ * another path is chosen) or with a list loss (it was pruned at some leaf).  polar_list_trace is a genie-aided list decode: it
+ * takes the rows and the sent u and says, per frame, which of the three happened, at which leaf the sent path left the list
+ * and how far from surviving it was.  polar_list_trace_count adds that into a loss-per-leaf histogram and three class counters.
+ * tests/trace_model.py restates the rules below in numpy; tests/test_gpu_trace.py holds the kernels to it with ==.
+ * Setting: a context that polar_list_decode accepts (rule 6 of "List output"): POLAR_ALGO_SCL or POLAR_ALGO_CASCL, POLAR_F64 or
+ * POLAR_F32, 32 <= N <= 1024, every L the context was created with (1 .. 256); plain, dynamic, CRC-file, systematic and
+ * rate-matched contexts (rows of E values are recovered first, as everywhere else).  The refusals are those of rule 7 of "List
+ * output", plus POLAR_EINVAL for a NULL d_u_bits.
+ * Inputs: d_rows follows "Input rows" at polar_decode_device (rows_are_f32 is in_is_f32 there).  d_u_bits [B][N/32] holds the
+ * sent u, packed like d_uhat_bits: what
+ * polar_generate_device / polar_encode_device write, dynamic bits included.
+ *   1. the decode is the context's own: leaf by leaf the list is that of polar_list_decode (rule 1 there).  Tracing changes no
+ *      decision, metric or flag.
+ *   2. match: after the decision at leaf j a live slot matches iff its decided bits 0 .. j equal the sent bits 0 .. j at every
+ *      position, frozen, dynamic or information.  At most one live slot matches.
+ *   3. loss leaf: loss_leaf is the smallest j after whose decision no live slot matches, N if there is none.  A sent u that
+ *      disagrees with a forced bit (a 1 at a plain frozen leaf, a wrong dynamic bit) is lost at that leaf: defined behaviour,
+ *      not an error.
+ *   4. loss rank: where the loss leaf is a ranking leaf -- an information leaf reached with act == L, where the 2L candidates c
+ *      are formed -- let c_sent be the candidate of the slot that matched after leaf j - 1, with the sent bit.  Then
+ *      loss_rank = #{m < 2L : c_m <= c_sent}, compared in R: the count the survivor test compares with L (so loss_rank > L).
+ *      Otherwise (never lost, or lost at a frozen or dynamic leaf) loss_rank = 0.
+ *   5. final rank: rank is the smallest k below count whose row in list-output order (rule 3 of "List output": ascending
+ *      (PM, slot)) equals the sent u, -1 if there is none.  loss_leaf == N <=> rank >= 0.
+ *   6. chosen rank and class: chosen is k* of rule 5 of "List output".  Class 0 (correct): rank == chosen.  Class 1 (selection
+ *      error): rank >= 0 and rank != chosen.  Class 2 (list loss): rank < 0.
+ *   7. flags: d_flags is the flags word of the ordinary decode, as rule 4 of "List output".
+ *   8. reduce: polar_list_trace_count adds into d_hist, uint64_t [N + 4]: hist[j] += the frames with loss_leaf == j for j < N,
+ *      hist[N + c] += the frames of class c, hist[N + 3] += B.  It ADDS to what the buffer holds; the sums are integers, so
+ *      the result does not depend on launch shape or order, and calls and GPUs add.
+ *   9. asynchronous: every call runs on the ctx stream and reads nothing back (graph capture as rule 7 of "List output").
+ *      Every per-frame output is nullable, but not all at once.  Nothing outside [B] per output is written.
+ * The kernels are scl_generic_body<..., DYN, TRACE> (k_scl_trace) and k_scl_wide<..., DYN, false, TRACE>: the
+ * decode of k_scl_list / k_scl_wide with one flag per slot and another epilogue, under the same limit (POLAR_ENOKERNEL where
+ * log2(L) * log2(N) > 64), and k_trace_count.  polar_kernel_name keeps naming the ordinary decode's kernel.
+ * Out of scope: tracing in the tuned kernels (their lists are the same lists by rule 5 of "List output"), code books, POLAR_Q8,
+ * polar_group_* (the counters add: a caller shards the frames and sums), N > 1024, a rank histogram of the live path. */
+/* d_rows, rows_are_f32, sigma as d_in, in_is_f32, sigma of polar_decode_device ("Input rows" there; [B][E] on a rate-matched
+ * ctx), d_u_bits [B][N/32].  Outputs [B], each nullable but not all.  tests/test_gpu_trace_rows.py holds the load stage. */
+int polar_list_trace(polar_ctx *ctx, const void *d_rows, int rows_are_f32, double sigma, const uint32_t *d_u_bits, size_t B,
+                     int32_t *d_loss_leaf, uint32_t *d_loss_rank, int32_t *d_rank, int32_t *d_chosen, uint32_t *d_flags);
+/* rule 8: d_loss_leaf, d_rank, d_chosen [B] as polar_list_trace wrote them (all required) -> d_hist [N + 4], added to */
+int polar_list_trace_count(polar_ctx *ctx, const int32_t *d_loss_leaf, const int32_t *d_rank, const int32_t *d_chosen,
+                           size_t B, uint64_t *d_hist);
+/* host-buffer form: llr_in [B][N] ([B][E]), u [B][N] ints 0/1; outputs [B], each nullable, not all.  POLAR_ENOMEM (ctx usable)
+ * if the device buffers cannot be had. */
+int polar_list_trace_host(polar_ctx *ctx, const double *llr_in, const int *u, size_t B, int *loss_leaf, unsigned *loss_rank,
+                          int *rank, int *chosen, unsigned *flags);
+
 /* --- Code books: one launch decodes frames of different codes (no reference counterpart) -----------------------------------
  * Every decode above binds one launch to one context, that is to one (N, frozen set, CRC, E) for all B frames.  A receiver
  * sees a few dozen candidates per slot at several lengths and payload sizes.  A code book holds C contexts' codes; each frame

@@ -169,6 +169,9 @@ def load_library(testing=False):
     L.polar_list_select.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
     L.polar_list_gather.argtypes = [vp, vp, vp, C.c_int, C.c_size_t, vp]
     L.polar_list_soft.argtypes = [vp, vp, vp, vp, vp, C.c_uint, C.c_int, C.c_double, C.c_size_t, vp]
+    L.polar_list_trace.argtypes = [vp, vp, C.c_int, C.c_double, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.polar_list_trace_count.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    L.polar_list_trace_host.argtypes = [vp, dp, ip, C.c_size_t, ip, up, ip, ip, up]
     L.polar_codebook_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
     L.polar_codebook_destroy.argtypes = [vp]
     L.polar_codebook_destroy.restype = None
@@ -1232,6 +1235,61 @@ class Decoder:
         self._check(self._lib.polar_rm_recover_device(self._h, C.c_void_p(d_in.data_ptr()), 1 if d_in.dtype == torch.float32 else 0,
                                                       float(sigma), B, C.c_void_p(out.data_ptr())), "polar_rm_recover_device")
         return out
+
+    # ---- sent-path trace (include/polar_hip.h, "Sent-path trace") ---------------------------------------------------
+    def trace_list_device(self, d_in, u_bits, sigma=0.0, want_loss_leaf=True, want_loss_rank=True, want_rank=True,
+                          want_chosen=True, want_flags=True):
+        """polar_list_trace: d_in as decode_device, u_bits [B][N/32] int32 (the sent u, packed like decode_device's output)
+        -> (loss_leaf, loss_rank, rank, chosen, flags), int32 CUDA tensors [B]: the leaf where the sent path left the list (N:
+        it never did), the sent candidate's count among the 2L candidates there, its rank in the final list (-1: not there),
+        the rank of the path the ordinary decode returns, and that decode's flags.  An output not asked for is None and is not
+        computed (at least one must be asked for)."""
+        import torch
+        B = self._dev_rows(d_in)
+        f32 = 1 if d_in.dtype == torch.float32 else 0
+        if not f32 and d_in.dtype != torch.float64:
+            raise ValueError("input must be float64 or float32")
+        if self._list_t(u_bits, (self.NW,), torch.int32, "u_bits") != B:
+            raise ValueError("u_bits and the rows disagree on B")
+        outs = [torch.empty(B, dtype=torch.int32, device=d_in.device) if w else None
+                for w in (want_loss_leaf, want_loss_rank, want_rank, want_chosen, want_flags)]
+        self._check(self._lib.polar_list_trace(
+            self._h, C.c_void_p(d_in.data_ptr()), f32, float(sigma), C.c_void_p(u_bits.data_ptr()), B,
+            *[C.c_void_p(t.data_ptr()) if t is not None else None for t in outs]), "polar_list_trace")
+        return tuple(outs)
+
+    def trace_count_device(self, loss_leaf, rank, chosen, hist):
+        """polar_list_trace_count: loss_leaf, rank, chosen [B] as trace_list_device returned them; adds per leaf the frames
+        lost there (hist[:N]), the frames of class 0 (correct), 1 (selection error), 2 (list loss) (hist[N:N+3]) and B
+        (hist[N+3]).  hist: int64 CUDA tensor [N + 4] holding the library's uint64 counters.  Asynchronous on the ctx stream."""
+        import torch
+        B = self._list_t(loss_leaf, (), torch.int32, "loss_leaf")
+        if self._list_t(rank, (), torch.int32, "rank") != B or self._list_t(chosen, (), torch.int32, "chosen") != B:
+            raise ValueError("loss_leaf, rank and chosen disagree on B")
+        if not (hist.is_cuda and hist.is_contiguous() and hist.dtype == torch.int64 and hist.numel() == self.N + 4):
+            raise ValueError("hist must be a contiguous int64 CUDA tensor of N + 4 elements")
+        self._check(self._lib.polar_list_trace_count(self._h, C.c_void_p(loss_leaf.data_ptr()), C.c_void_p(rank.data_ptr()),
+                                                     C.c_void_p(chosen.data_ptr()), B, C.c_void_p(hist.data_ptr())),
+                    "polar_list_trace_count")
+        return hist
+
+    def trace_list_batch(self, llr, u):
+        """polar_list_trace_host: host rows and the sent u [B][N] of 0/1 -> (loss_leaf int32, loss_rank uint32, rank int32,
+        chosen int32, flags uint32), each [B]."""
+        llr = self._rows(llr)
+        B = llr.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        if u.shape != (B, self.N):
+            raise ValueError(f"u must have shape [{B}][{self.N}]")
+        loss_leaf = np.empty(B, dtype=np.int32)
+        loss_rank = np.empty(B, dtype=np.uint32)
+        rank = np.empty(B, dtype=np.int32)
+        chosen = np.empty(B, dtype=np.int32)
+        flags = np.empty(B, dtype=np.uint32)
+        self._check(self._lib.polar_list_trace_host(self._h, _ptr(llr, C.c_double), _ptr(u, C.c_int), B, _ptr(loss_leaf, C.c_int),
+                                                    _ptr(loss_rank, C.c_uint), _ptr(rank, C.c_int), _ptr(chosen, C.c_int),
+                                                    _ptr(flags, C.c_uint)), "polar_list_trace_host")
+        return loss_leaf, loss_rank, rank, chosen, flags
 
     # ---- Monte-Carlo construction (include/polar_hip.h: genie-aided SC, rules 1-3) -----------------------------------
     @staticmethod

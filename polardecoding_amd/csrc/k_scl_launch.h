@@ -5,9 +5,12 @@
 //     K::kernel<R, IN, LOGL, GA>()               the instantiation
 //     K::lds_bytes<R, LOGL>(N, ga)               its dynamic LDS
 //     K::scl(Params &)                           the SclParams inside the parameter struct
+//     K::Wide (optional)                         the trait of the k_scl_wide instantiation that takes L = 64, 128, 256 for K
 // The parameter struct travels down the ladder by value; launch_scl_v fills in scratch and queue.
 #pragma once
 #include "polar_host.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -42,9 +45,25 @@ int launch_scl(polar_ctx *c, typename K::Params P)
     return launch_scl_v<K, R, IN, LOGL, true>(c, P);
 }
 
+template <typename K, typename = void>
+struct WideOf {
+    static constexpr bool present = false;
+};
+template <typename K>
+struct WideOf<K, std::void_t<typename K::Wide>> {
+    static constexpr bool present = true;
+};
+
 template <typename K, typename R, typename IN>
 int launch_scl_l(polar_ctx *c, typename K::Params P)
 {
+    if constexpr (WideOf<K>::present) {
+        switch (c->logL) {
+        case 6: return launch_scl<typename K::Wide, R, IN, 6>(c, P);
+        case 7: return launch_scl<typename K::Wide, R, IN, 7>(c, P);
+        case 8: return launch_scl<typename K::Wide, R, IN, 8>(c, P);
+        }
+    }
     switch (c->logL) {
     case 0: return launch_scl<K, R, IN, 0>(c, P);
     case 1: return launch_scl<K, R, IN, 1>(c, P);

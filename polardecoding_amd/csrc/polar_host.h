@@ -17,6 +17,7 @@
 #include "polar_params.h"
 
 namespace polar {
+struct TraceOut;    // trace_out.h
 struct ScfParams;   // scf_params.h
 struct GenParams;   // gen_common.h
 struct ScanParams;  // scan_lanes.h
@@ -141,7 +142,8 @@ struct polar_ctx : Lane {
         long long need;
     } last_stride{};            // what stride_grid() saw last (polar_testing_last_stride)
     // list output (polar_list_decode): the D = 0 constraint tables a ctx without dynamic bits runs k_scl_list with
-    // (row = -1 at every leaf, one zero mask row), built on first use; staging of polar_list_decode_host
+    // (row = -1 at every leaf, one zero mask row), built on first use; staging of polar_list_decode_host, and of
+    // polar_list_trace_host (u in list_paths, loss_leaf in list_cnt, loss_rank in list_rem, rank and chosen in list_pm)
     DevMem<uint32_t> d_list_mask;
     DevMem<int> d_list_row;
     Buf list_paths, list_pm, list_rem, list_cnt;
@@ -376,6 +378,11 @@ int list_select(polar_ctx *c, const uint32_t *d_rem, const uint32_t *d_count, si
 int list_gather(polar_ctx *c, const uint32_t *d_paths, const int32_t *d_idx, int idx_stride, size_t B, uint32_t *d_out);
 int list_soft(polar_ctx *c, const uint32_t *d_paths, const double *d_pm, const uint32_t *d_count, const uint32_t *d_rem,
               uint32_t want_rem, int domain, double clamp, size_t B, double *d_out);
+// k_trace.hip: sent-path trace (trace_out.h): the list decode of list_decode with the TRACE hook and epilogue, and the reduce
+int list_trace(polar_ctx *c, const polar::SclParams &P, const uint32_t *d_mask, const int *d_row, bool r32, bool in32,
+               const polar::TraceOut &T);
+int trace_count(polar_ctx *c, const int32_t *d_loss_leaf, const int32_t *d_rank, const int32_t *d_chosen, size_t B,
+                unsigned long long *d_hist);
 // k_book.hip: code books (scl_book.h): c is the book's internal context (the largest member's N, the book's L); P.N / P.n
 // are that member's, K names the descriptors, the frames' code indices and the input's row stride
 int book_decode(polar_ctx *c, const polar::SclParams &P, const polar::BookArgs &K, bool r32, bool in32);

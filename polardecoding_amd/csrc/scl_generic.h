@@ -26,6 +26,7 @@
 #include "polar_lut.h"
 #include "polar_params.h"
 #include "list_out.h"
+#include "trace_out.h"
 #include "book_desc.h"
 #include "scl_wave_ops.h"
 
@@ -43,12 +44,18 @@ namespace polar {
 // run on its own N.  Whatever a longer earlier frame left in LDS lies outside this frame's rows or is rewritten before it
 // is read; hist, the one array read before it is written, is cleared over this frame's rows.  Output words from N / 32 up
 // to P.N / 32 are written as 0, and every output is nullable.  BOOK = false: BK is never read.
-template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false, bool BOOK = false>
+// TRACE = true (needs DYN, not with LIST or BOOK; k_trace.hip): the decode is the same; every slot carries the match flag of
+// trace_out.h, and the epilogue writes the frame's five trace words to *TO instead of the chosen path.  Every __ballot and
+// __shfl it adds sits in wave-uniform control flow; the lanes choose what they contribute with ?:.  TRACE = false: TO is
+// never read.
+template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false, bool BOOK = false, bool TRACE = false>
 __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint32_t *dyn_mask, const int *dyn_row,
-                                                 const ListOut *LO = nullptr, const BookArgs *BK = nullptr)
+                                                 const ListOut *LO = nullptr, const BookArgs *BK = nullptr,
+                                                 const TraceOut *TO = nullptr)
 {
     static_assert(DYN || !LIST, "the list epilogue reads the per-path history");
     static_assert(DYN || !BOOK, "a code book runs the dynamic leaf of every member");
+    static_assert(!TRACE || (DYN && !LIST && !BOOK), "the trace runs the list decode of one code and has its own epilogue");
     constexpr int L = 1 << LOGL;
     constexpr int S = 64 / L;
     const int NL = P.N, NWL = NL >> 5;   // the layout's N: the frame's own N but in a code book
@@ -133,8 +140,14 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
         uint32_t h0 = 0;   // DYN: word 0 of the path's history, shuffled with the path like bl0
         uint32_t fl = 0;
         int act = 1;
+        // TRACE: slot 0 has decided nothing yet and matches; the sent word of the 32 leaves at hand; the loss leaf and its count
+        bool match = TRACE && p == 0;
+        uint32_t sent_w = 0, loss_rank = 0;
+        int loss_leaf = N;
 
         for (int j = 0; j < N; ++j) {
+            if constexpr (TRACE)
+                if ((j & 31) == 0) sent_w = TO->u[(size_t)frame * NW + (j >> 5)];
             // ================= LLR of leaf j for every active path =================
             int tf;
             if (j > 0) {
@@ -172,6 +185,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
             int row = -1;   // DYN: row of leaf j in the constraint matrix, -1 = not dynamic (wave-uniform, like j)
             if constexpr (DYN) row = dyn_row[j];
             int bit = 0;
+            uint32_t sent_n = 0;   // TRACE: at a ranking leaf the count of the sent candidate, taken before the pruning
             if (row >= 0) {
                 // dynamic frozen leaf: b = parity of (history AND mask row) over the words 0 .. j >> 5, on every lane of the
                 // wave (lanes of dead paths compute and discard); no fork, no ranking, no tie flag
@@ -202,6 +216,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                 crc = __shfl(crc, sl);
                 bl0 = __shfl(bl0, sl);
                 if constexpr (DYN) h0 = __shfl(h0, sl);
+                if constexpr (TRACE) match = __shfl((int)match, sl) != 0;
                 if (is_new) {
                     for (int w = 1 + pos; w < NW; w += S) {
                         blw[p * NW + w] = blw[sg * NW + w];
@@ -232,6 +247,13 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                     n1 += (v <= c1);
                 }
                 const bool s0 = n0 <= L, s1 = n1 <= L;
+                if constexpr (TRACE) {
+                    // the slot that matched after leaf j - 1 (at most one does): its count for the sent bit
+                    const uint64_t m_match = __ballot(match);
+                    const int n_sent = trace_sent_bit(sent_w, j) ? n1 : n0;
+                    const int n_first = __shfl(n_sent, m_match ? __ffsll((unsigned long long)m_match) - 1 : 0);
+                    sent_n = m_match ? (uint32_t)n_first : 0u;
+                }
                 const bool lead = pos == 0;
                 const uint64_t m_s0 = __ballot(lead && s0);
                 const uint64_t m_s1 = __ballot(lead && s1);
@@ -247,6 +269,7 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                 crc = __shfl(crc, sl);
                 bl0 = __shfl(bl0, sl);
                 if constexpr (DYN) h0 = __shfl(h0, sl);
+                if constexpr (TRACE) match = __shfl((int)match, sl) != 0;
                 if (refilled) {
                     for (int w = 1 + pos; w < NW; w += S) {
                         blw[p * NW + w] = blw[sg * NW + w];
@@ -265,6 +288,16 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                     PM = c0;
                 }
                 __syncthreads();
+            }
+
+            // ================= TRACE: the match flag after the decision; the first leaf nobody matches after =================
+            if constexpr (TRACE) {
+                match = match && p < act && bit == trace_sent_bit(sent_w, j);
+                const bool none = __ballot(match) == 0ull;
+                if (none && loss_leaf == N) {
+                    loss_leaf = j;
+                    loss_rank = sent_n;
+                }
             }
 
             // ================= DYN: bit j of the path's history =================
@@ -331,6 +364,18 @@ __device__ __forceinline__ void scl_generic_body(const SclParams &P, const uint3
                 if (LO->rem) LO->rem[row] = live ? crc : 0u;
             }
             if (lane == 0 && LO->count) LO->count[frame] = (uint32_t)act;
+        }
+        // TRACE: the rank of the LIST epilogue, read from the matching slot (at most one) and from the chosen one
+        else if constexpr (TRACE) {
+            int rank = 0;
+            for (int q = 0; q < act; ++q) {
+                const R pq = __shfl(PM, q * S);
+                rank += (pq < PM || (pq == PM && q < p)) ? 1 : 0;
+            }
+            const uint64_t m_match = __ballot(match);
+            const int r_first = __shfl(rank, m_match ? __ffsll((unsigned long long)m_match) - 1 : 0);
+            const int r_best = __shfl(rank, best * S);
+            if (lane == 0) trace_write(*TO, frame, loss_leaf, loss_rank, m_match ? r_first : -1, r_best);
         }
         // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
         else if constexpr (DYN) {

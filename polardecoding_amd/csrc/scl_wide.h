@@ -83,15 +83,31 @@ struct ListParams {
     DynParams d;
     ListOut o;
 };
+
+// TRACE = true (needs DYN, not with LIST; launched by k_trace.hip): the kernel takes a TraceParams, the decode is the same,
+// every thread carries the match flag of trace_out.h for its slot, and the epilogue writes the frame's five trace words to its
+// TraceOut instead of the chosen path.  At most one slot matches, so the flag crosses threads as a slot number: at an
+// information leaf every wavefront ballots its flags and writes the matching slot (or -1) to its word wtr[wave] before the leaf's first barrier, every thread
+// reads the words behind it, and the thread whose path comes from that slot with the sent bit matches afterwards.  The thread
+// that matched knows from its own s0 / s1 / refill whether the sent candidate goes on, and keeps the loss leaf and the count;
+// the epilogue collects them through four more words.  All eight words lie in MISC_WORDS.  The ballot sits in control flow
+// that is uniform for the workgroup; the lanes choose what they contribute with ?:.
+struct TraceParams {
+    DynParams d;
+    TraceOut t;
+};
 __device__ __forceinline__ const DynParams &wide_dyn(const DynParams &P) { return P; }
 __device__ __forceinline__ const DynParams &wide_dyn(const ListParams &P) { return P.d; }
+__device__ __forceinline__ const DynParams &wide_dyn(const TraceParams &P) { return P.d; }
 
-template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false>
-__global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditional<LIST, ListParams, DynParams>::type KP)
+template <typename R, typename IN, int LOGL, bool GA, bool DYN, bool LIST = false, bool TRACE = false>
+__global__ __launch_bounds__(1 << LOGL) void k_scl_wide(
+    typename std::conditional<TRACE, TraceParams, typename std::conditional<LIST, ListParams, DynParams>::type>::type KP)
 {
     const DynParams &DP = wide_dyn(KP);
     static_assert(LOGL >= 6 && LOGL <= 8, "one thread per path: 1, 2 or 4 wavefronts");
     static_assert(DYN || !LIST, "the list epilogue reads the per-path history");
+    static_assert(!TRACE || (DYN && !LIST), "the trace runs the list decode and has its own epilogue");
     constexpr int L = 1 << LOGL;
     constexpr int NWAVES = L / 64;
     using Lay = WideLds<R, LOGL, DYN>;
@@ -121,6 +137,8 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
     int *blist = reinterpret_cast<int *>(xh0 + L);
     int *wcnt = blist + L;               // [NWAVES][4]: both-survivors, dead slots, surviving candidates
     int *job_slot = wcnt + 16;
+    int *wtr = wcnt + 20;                // TRACE: [NWAVES] the matching slot of each wavefront, -1 if it has none
+    int *wout = wcnt + 24;               // TRACE: loss leaf, its count, rank of the sent word, rank of the chosen path
     unsigned char *lut_mem = reinterpret_cast<unsigned char *>(wcnt + Lay::MISC_WORDS);
     lut_mem += (16 - (reinterpret_cast<uintptr_t>(lut_mem) & 15)) & 15;
     Lut<R>::build(lut_mem, p, L);
@@ -148,8 +166,14 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
         uint32_t h0 = 0;
         uint32_t fl = 0;
         int act = 1;
+        // TRACE: slot 0 has decided nothing yet and matches; the sent word of the 32 leaves at hand; the loss leaf and its count
+        bool match = TRACE && p == 0;
+        uint32_t sent_w = 0, loss_rank = 0;
+        int loss_leaf = N;
 
         for (int j = 0; j < N; ++j) {
+            if constexpr (TRACE)
+                if ((j & 31) == 0) sent_w = KP.t.u[(size_t)frame * NW + (j >> 5)];
             // ================= LLR of leaf j for every active path: the path's thread walks every level =================
             R lam = R(0);
             if (p < act) {
@@ -190,6 +214,10 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
             int row = -1;   // DYN: row of leaf j in the constraint matrix, -1 = not dynamic (uniform, like j)
             if constexpr (DYN) row = DP.row[j];
             int bit = 0;
+            bool forked = false;     // TRACE: an information leaf, where paths move between slots
+            bool sent_on = true;     // TRACE, on the thread that matches: the sent candidate goes on after this leaf's pruning
+            uint32_t sent_n = 0;     // TRACE: at a ranking leaf the count of this thread's candidate with the sent bit
+            bool from_match = match; // TRACE: the slot this thread's path comes from matched after leaf j - 1
             if (row >= 0) {
                 // dynamic frozen leaf: b = parity of (history AND mask row) over the words 0 .. j >> 5; no fork, no ranking
                 if constexpr (DYN) {
@@ -215,7 +243,16 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
                 xcrc[p] = crc;
                 xbl0[p] = bl0;
                 if constexpr (DYN) xh0[p] = h0;
+                if constexpr (TRACE) {
+                    const uint64_t m_match = __ballot(match);
+                    if (wlane == 0) wtr[wave] = m_match ? wave * 64 + __ffsll((unsigned long long)m_match) - 1 : -1;
+                }
                 __syncthreads();
+                int m_slot = -1;      // TRACE: the slot that matched after leaf j - 1
+                if constexpr (TRACE) {
+                    forked = true;
+                    for (int w = 0; w < NWAVES; ++w) m_slot = max(m_slot, wtr[w]);
+                }
                 int sg = p;           // the slot this thread's path comes from
                 bool moved = false;   // it takes the 1-branch of slot sg
                 if (act < L) {
@@ -269,7 +306,15 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
                     } else {
                         PM = c0;  // tie rule: an un-refilled dead slot continues as its 0-branch
                     }
+                    if constexpr (TRACE) {
+                        // the 1-branch goes on iff it survives (in place, or as a both-survivor's fork: there are never more
+                        // both-survivors than dead slots); the 0-branch iff it survives or the slot stays dead and un-refilled
+                        const bool sent1 = trace_sent_bit(sent_w, j) != 0;
+                        sent_on = sent1 ? s1 : (s0 || (dead && !moved));
+                        sent_n = (uint32_t)(sent1 ? n1 : n0);
+                    }
                 }
+                if constexpr (TRACE) from_match = sg == m_slot;
                 if (moved) {
                     bit = 1;
                     PM = cand[sg + L];
@@ -283,6 +328,16 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
                     }
                 }
                 __syncthreads();   // the copies read their sources before the owners go on
+            }
+
+            // ================= TRACE: the match flag after the decision; the leaf the sent path is lost at =================
+            if constexpr (TRACE) {
+                const int sent = trace_sent_bit(sent_w, j);
+                if (match && (forked ? !sent_on : bit != sent)) {   // at most one thread, at most once per frame
+                    loss_leaf = j;
+                    loss_rank = sent_n;
+                }
+                match = from_match && p < act && bit == sent;
             }
 
             // ================= DYN: bit j of the path's history (the thread's own words) =================
@@ -363,6 +418,30 @@ __global__ __launch_bounds__(1 << LOGL) void k_scl_wide(typename std::conditiona
             if (LO->pm) LO->pm[row] = live ? (double)PM : __builtin_huge_val();
             if (LO->rem) LO->rem[row] = live ? crc : 0u;
             if (p == 0 && LO->count) LO->count[frame] = (uint32_t)act;
+        }
+        // TRACE: the rank of the LIST epilogue, taken from the matching thread (at most one) and from the chosen one; the
+        // thread that saw the loss hands over its leaf and count
+        else if constexpr (TRACE) {
+            const TraceOut *TO = &KP.t;
+            int rank = 0;
+            for (int q = 0; q < act; ++q) {
+                const R pq = cand[q];
+                rank += (pq < PM || (pq == PM && q < p)) ? 1 : 0;
+            }
+            if (p == 0) {
+                wout[0] = N;
+                wout[1] = 0;
+                wout[2] = -1;
+            }
+            __syncthreads();
+            if (loss_leaf < N) {
+                wout[0] = loss_leaf;
+                wout[1] = (int)loss_rank;
+            }
+            if (match) wout[2] = rank;
+            if (p == best) wout[3] = rank;
+            __syncthreads();
+            if (p == 0) trace_write(*TO, frame, wout[0], (uint32_t)wout[1], wout[2], wout[3]);
         }
         // x_hat of the chosen path: root partial sums; u_hat = x_hat * F^{(x)n}.  DYN: u_hat is the chosen path's history
         else if constexpr (DYN) {
